@@ -19,6 +19,11 @@ default (--pairs per GPU); --total-pairs T shards T pairs over the ranks (strong
 
 --backend gloo --dry runs the same multi-rank control flow on CPU tensors without the kernels (tests/test_bench_gloo.py).
 
+A plain run sets up, warms up, times the steps and prints its line.  --full adds everything else the bench measures,
+after the timed region: the roofline accounting (an untimed census pass, the committed PMC profile), the shader clock
+and sysfs telemetry, the CPU baseline, the host-to-host entry, single-pair latency and (default run) the legs of the
+other configurations.  --dump-outputs DIR writes what the last timed step computed (dump_outputs()).
+
 Prints ONE JSON line (rank 0).  `value` = pairs aligned by all ranks / max-over-ranks wall time of K steps.
 """
 import argparse
@@ -79,11 +84,17 @@ def parse_args(argv=None):
     ap.add_argument("--semi-global", action="store_true", default=None)
     ap.add_argument("--no-adaptive", action="store_true", default=None)
     ap.add_argument("--penalties", default=None, help="mismatch,gap_open,gap_ext (default: the configuration's, 4,6,2)")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="pairs timed on host cores (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need: roofline accounting, "
+                         "clock and telemetry, and the CPU baseline / host entry / latency / other-configuration legs by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float64; --gpus 1 only)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="pairs timed on host cores (0 = skip; default: the configuration's with --full, else 0)")
     ap.add_argument("--cpu-threads", type=int, default=None, help="threads of the cpu_baseline leg (default 1; c5s: 8, one pair each)")
     ap.add_argument("--cpu-all-cores", type=int, default=1, help="1: also time the oracle on every host core (N = 1 only)")
-    ap.add_argument("--host-entry", type=int, default=1, help="1: also time wfahip_align_batch (host blobs -> host results), N = 1 only")
-    ap.add_argument("--latency", type=int, default=1, help="1: also time single-pair Align round trips, N = 1 only")
+    ap.add_argument("--host-entry", type=int, default=None,
+                    help="1: also time wfahip_align_batch (host blobs -> host results), N = 1 only (default: 1 with --full, else 0)")
+    ap.add_argument("--latency", type=int, default=None, help="1: also time single-pair Align round trips, N = 1 only (default: 1 with --full, else 0)")
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (experiments)")
     ap.add_argument("--gather-ops", action="store_true", help="multi-GPU: gather the CIGAR op arrays onto rank 0 too")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
@@ -99,7 +110,7 @@ def parse_args(argv=None):
                          "device tensors, so the `nccl` lines of this file execute on a 1-GPU box")
     ap.add_argument("--other-configs", type=int, default=None,
                     help="1: after the timed region of the default (c3, N = 1) run, short legs of c2, k10, l5 and c5s on the same "
-                         "GPU, reported under config.other_configs (default: 1 for the default run, else 0)")
+                         "GPU, reported under config.other_configs (default: 1 for the default run with --full, else 0)")
     ap.add_argument("--plan", action="store_true",
                     help="no GPU, no processes: print ONE JSON line with what each of the --gpus ranks would hold in HBM for this "
                          "configuration (input blob, records, CIGAR ops, wavefront arenas per chunk) -- an out-of-memory condition shows "
@@ -108,6 +119,8 @@ def parse_args(argv=None):
     ap.add_argument("--dump-records", default=None,
                     help="rank 0 writes the records gathered in the last timed step (all ranks, pair order) to this .npy file")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the outputs of one rank: use it with --gpus 1")
     c = CONFIGS[args.config]
     if args.pairs is None:
         args.pairs = c["pairs"]
@@ -125,7 +138,11 @@ def parse_args(argv=None):
         args.no_adaptive = not c["adaptive"]
     args.pen = tuple(int(v) for v in args.penalties.split(",")) if args.penalties else tuple(c.get("pen", (4, 6, 2)))
     if args.cpu_sample is None:
-        args.cpu_sample = c["cpu"]
+        args.cpu_sample = c["cpu"] if args.full else 0
+    if args.host_entry is None:
+        args.host_entry = int(args.full)
+    if args.latency is None:
+        args.latency = int(args.full)
     if args.cpu_threads is None:
         args.cpu_threads = 8 if args.config in ("c5s", "c5s32") else 1  # (a 100 kbp semi-global pair is minutes of one core)
     if args.steps is None:
@@ -135,7 +152,7 @@ def parse_args(argv=None):
     if args.other_configs is None:
         plain = (args.config == "c3" and args.gpus == 1 and not args.dry and not args.opt and args.pairs == c["pairs"] and
                  args.total_pairs == c["total"] and args.length == c["length"] and args.error == c["error"])
-        args.other_configs = 1 if plain else 0
+        args.other_configs = 1 if (plain and args.full) else 0
     return args
 
 
@@ -359,7 +376,8 @@ def run_rank(args):
     kernel_ms, main_ms = [], []
     n_ops = 0
     sync_all()
-    smi_before = gpu_telemetry(dev_index) if (rank == 0 and not dry) else None
+    full = args.full and not dry
+    smi_before = gpu_telemetry(dev_index) if (rank == 0 and full) else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         n_ops = step()
@@ -371,9 +389,9 @@ def run_rank(args):
     # what the run ran AT (round 5: the round-4 driver measured the unchanged headline kernel 7 % slower than the builder's box and
     # nothing in the line could say why): rocm-smi's clocks / power / temperature right before and right after the timed region,
     # and the shader clock under load by the library's own probe (s_memtime against the 100 MHz s_memrealtime on every SIMD)
-    smi_after = gpu_telemetry(dev_index) if (rank == 0 and not dry) else None
+    smi_after = gpu_telemetry(dev_index) if (rank == 0 and full) else None
     clock = None
-    if rank == 0 and not dry:
+    if rank == 0 and full:
         f0, f1, f2 = C.c_double(), C.c_double(), C.c_double()
         if lib.wfahip_debug_clock(al._ctx, C.byref(f0), C.byref(f1), C.byref(f2)) == 0:
             clock = {"mean": f0.value, "min": f1.value, "max": f2.value}
@@ -414,11 +432,13 @@ def run_rank(args):
         pairs_per_rank, n_seen, gathered_ok = [n], 1, None
         if args.dump_records and rank == 0:
             np.save(args.dump_records, d_rec[:, :L.REC_OPS_OFF_LO].cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_rec, d_ops, n, args.seed, L)
 
     # ---- accounting for the roofline (algorithmic bytes): one more pass, untimed, with the forward
     # kernel's count of stored wavefront words switched on (instrumentation: off in the timed steps, where it would
     # cost 4 % of the forward pass; the dataset is the same, so the count is that of every timed step)
-    if not dry:
+    if full:
         L.check(lib.wfahip_set_option(al._ctx, b"census", 1), "census")
         step()
         drain()
@@ -426,18 +446,18 @@ def run_rank(args):
         L.check(lib.wfahip_set_option(al._ctx, b"census", 0), "census")
     rec = d_rec.cpu().numpy().view(np.uint32)
     ok = rec[:, L.REC_STATUS] == 0
-    cells = int(rec[:, L.REC_CELLS_LO].astype(np.uint64).sum()) + (int(rec[:, L.REC_CELLS_HI].astype(np.uint64).sum()) << 32)
     n_ops_total = int(rec[:, L.REC_OPS_LEN].astype(np.uint64).sum())
-    alg_bytes = 4 * cells + sum_len + 64 * n + 8 * n_ops_total
     k_ms = float(np.mean(kernel_ms)) if kernel_ms else 0.0
     main_k_ms = float(np.mean(main_ms)) if main_ms else 0.0
-    achieved = alg_bytes / (main_k_ms * 1e-3) / 1e9 if main_k_ms > 0 else 0.0  # GB/s over the dominant kernel's launches of one step
-
-    kname = KNAMES[min(int(timing.main_kernel_kind), len(KNAMES) - 1)]
-    if kname == "wfa_duo_kernel":  # (round 5: an instance per penalty shape -- x/g and (o+e)/g are its template arguments; <false: without the census)
-        import math
-        g = math.gcd(math.gcd(args.pen[0], args.pen[1] + args.pen[2]), args.pen[2])
-        kname = f"wfa_duo_kernel<false, {args.pen[0] // g}, {(args.pen[1] + args.pen[2]) // g}>"
+    if full:
+        cells = int(rec[:, L.REC_CELLS_LO].astype(np.uint64).sum()) + (int(rec[:, L.REC_CELLS_HI].astype(np.uint64).sum()) << 32)
+        alg_bytes = 4 * cells + sum_len + 64 * n + 8 * n_ops_total
+        achieved = alg_bytes / (main_k_ms * 1e-3) / 1e9 if main_k_ms > 0 else 0.0  # GB/s over the dominant kernel's launches of one step
+        kname = KNAMES[min(int(timing.main_kernel_kind), len(KNAMES) - 1)]
+        if kname == "wfa_duo_kernel":  # (round 5: an instance per penalty shape -- x/g and (o+e)/g are its template arguments; <false: without the census)
+            import math
+            g = math.gcd(math.gcd(args.pen[0], args.pen[1] + args.pen[2]), args.pen[2])
+            kname = f"wfa_duo_kernel<false, {args.pen[0] // g}, {(args.pen[1] + args.pen[2]) // g}>"
 
     out = None
     if rank == 0:
@@ -446,7 +466,7 @@ def run_rank(args):
         # bench).  gfx950: FETCH_SIZE counts half the bytes of the coalesced input reads (checked against the known
         # 2.0 GB of sequence bytes the forward kernel must read: it reports 1.12 GB), so it is doubled; WRITE_SIZE is
         # taken as is.  `stale` says whether the profile was taken on another build of the kernels.
-        pm = find_profile(args.config, kname) if (not dry and n == CONFIGS[args.config]["pairs"] and not args.opt) else None
+        pm = find_profile(args.config, kname) if (full and n == CONFIGS[args.config]["pairs"] and not args.opt) else None
         traffic = pm["traffic"] if pm else None
         total_pairs = n_all * args.steps
         value = total_pairs / elapsed
@@ -467,14 +487,17 @@ def run_rank(args):
                "kernel_ms_per_step": k_ms, "main_kernel_ms": main_k_ms, "launches_per_step": int(timing.n_launches),
                "packed_pairs": int(timing.n_packed_pairs),
                "retried_pairs": int(timing.n_retried_pairs), "arena_gib": timing.arena_bytes / 2 ** 30,
-               "wf_cells_per_pair": cells / max(n, 1), "cigar_ops_per_pair": n_ops_total / max(n, 1),
+               "cigar_ops_per_pair": n_ops_total / max(n, 1),
                "timed_region_s": elapsed,
-               "clock_mhz_under_load": clock["mean"] if clock else None, "clock_mhz_under_load_range": [clock["min"], clock["max"]] if clock else None,
-               "clock_note": "shader MHz while the library's probe kernel keeps every SIMD issuing (s_memtime / s_memrealtime), right after the timed region",
-               "gpu_sysfs_before": smi_before, "gpu_sysfs_after": smi_after,
                "steady_state": f"the timed steps re-align the resident batch after {args.warmup + setup_steps} untimed call(s) of the same workload class: "
                                "what the context learns per class (rows per pair, first window, arena level) is in place; a first call "
                                "of a class also allocates its arenas (seconds, include/wfa_hip.h)"}
+        if full:
+            cfg.update({"wf_cells_per_pair": cells / max(n, 1),
+                        "clock_mhz_under_load": clock["mean"] if clock else None,
+                        "clock_mhz_under_load_range": [clock["min"], clock["max"]] if clock else None,
+                        "clock_note": "shader MHz while the library's probe kernel keeps every SIMD issuing (s_memtime / s_memrealtime), right after the timed region",
+                        "gpu_sysfs_before": smi_before, "gpu_sysfs_after": smi_after})
         if dry:
             cfg["dry"] = True
         metric = METRIC if args.config in ("c3", "c4") else (
@@ -482,7 +505,7 @@ def run_rank(args):
         out = {"metric": metric, "value": value, "unit": "pairs/s", "n_gpus": n_seen, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
                "vs_baseline": None, "dtype": "u32", "data": "synthetic", "config": cfg}
-        if not dry:
+        if full:
             roof = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
                     "frac": achieved / 8000.0, "traffic": traffic,
                     "traffic_source": pm["source"] if pm else None, "traffic_stale": pm["stale"] if pm else None,
@@ -633,6 +656,38 @@ def other_configs(w, L, torch, dev, dev_index):
             torch.cuda.empty_cache()
         res[name]["leg_s"] = time.perf_counter() - t_leg
     return res
+
+
+DUMP_PAIRS = 1 << 18   # records of at most this many pairs: 23 MB
+DUMP_OPS = 1 << 21     # CIGAR ops of at most this many entries: 34 MB
+
+
+def dump_outputs(out_dir, d_rec, d_ops, n, seed, L):
+    """--dump-outputs: what a caller of the timed path receives from its last step, so that two builds can be compared
+    output for output.  Every value is an integer below 2**53, so float64 holds it exactly.
+      records.npy     (k, 11): status, score, tbegin, tend, qbegin, qend, align_len, matches, gaps, gap_regions, ops_len
+      pair_index.npy  (k,):    the pairs those rows belong to -- all n, or a sample of DUMP_PAIRS drawn with the
+                               workload's seed, in pair order
+      cigar_ops.npy   (m, 2):  (op character code, run length) of the CIGARs of the first rows of records.npy, row after
+                               row, as many whole CIGARs as fit DUMP_OPS entries
+    (The records' op offsets and census words are left out: they say where the ops lie in the buffer, not what they are.)"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.arange(n) if n <= DUMP_PAIRS else np.sort(np.random.default_rng(seed).choice(n, DUMP_PAIRS, replace=False))
+    rec = d_rec[torch.from_numpy(idx).to(d_rec.device)].cpu().numpy()
+    u = rec.view(np.uint32)
+    off = (u[:, L.REC_OPS_OFF_LO].astype(np.uint64) | (u[:, L.REC_OPS_OFF_HI].astype(np.uint64) << np.uint64(32))).astype(np.int64)
+    cnt = u[:, L.REC_OPS_LEN].astype(np.int64)
+    keep = int(np.searchsorted(np.cumsum(cnt), DUMP_OPS, side="right"))
+    off, cnt = off[:keep], cnt[:keep]
+    if (off < 0).any() or int((off + cnt).max(initial=0)) > d_ops.numel():
+        raise RuntimeError("--dump-outputs: a record's CIGAR ops lie outside the op buffer")
+    where = np.arange(int(cnt.sum()), dtype=np.int64) + np.repeat(off - (np.cumsum(cnt) - cnt), cnt)
+    ops = d_ops[torch.from_numpy(where).to(d_ops.device)].cpu().numpy().view(np.uint64)
+    np.save(os.path.join(out_dir, "records.npy"), rec[:, :L.REC_OPS_OFF_LO].astype(np.float64))
+    np.save(os.path.join(out_dir, "pair_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "cigar_ops.npy"), np.stack([ops >> np.uint64(32), ops & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
 
 
 def gpu_telemetry(dev_index):

@@ -20,14 +20,14 @@ print('$1', 'value', round(d['value'],2), 'ms', round(d['ms_per_step'],3), 'fwd'
       'h2h', c.get('host_to_host_ms'), 'packed', c.get('host_to_host_packed_ms'), 'align_us', c.get('single_pair_align_us'), 'kernel', r['kernel'], 'frac', round(r['frac'],4), 'traffic', r.get('traffic'), 'stale', r.get('traffic_stale'),
       'cpu1', cb.get('value'), 'cpuall', cb.get('all_cores',{}).get('value'), 'others', {k: (round(v.get('value', 0), 1), v.get('status_ok')) for k, v in c.get('other_configs', {}).items()})" || tail -5 $OUT/bench_$1.err; }
 if has lines; then
-  timeout 900 python bench.py > $OUT/bench_c3.json 2> $OUT/bench_c3.err; summ c3
-  for c in c2 c2m p242; do timeout 600 python bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err; summ $c; done
-  timeout 1200 python bench.py --config g3 --host-entry 0 --latency 0 > $OUT/bench_g3.json 2> $OUT/bench_g3.err; summ g3
-  timeout 900 python bench.py --config c4 --host-entry 0 --latency 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; summ c4
-  timeout 900 python bench.py --config c5s > $OUT/bench_c5s.json 2> $OUT/bench_c5s.err; summ c5s
+  timeout 900 python bench.py --full > $OUT/bench_c3.json 2> $OUT/bench_c3.err; summ c3
+  for c in c2 c2m p242; do timeout 600 python bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err; summ $c; done
+  timeout 1200 python bench.py --full --config g3 --host-entry 0 --latency 0 > $OUT/bench_g3.json 2> $OUT/bench_g3.err; summ g3
+  timeout 900 python bench.py --full --config c4 --host-entry 0 --latency 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; summ c4
+  timeout 900 python bench.py --full --config c5s > $OUT/bench_c5s.json 2> $OUT/bench_c5s.err; summ c5s
   timeout 900 python bench.py --config c5s --pairs 32 --steps 1 --cpu-sample 0 --host-entry 0 --latency 0 > $OUT/bench_c5s32.json 2> $OUT/bench_c5s32.err; cp $OUT/bench_c5s32.json $OUT/bench_x.json; python3 -c "
 import json; d=json.load(open('$OUT/bench_c5s32.json')); print('c5s x 32 pairs: value', round(d['value'],2), 'ms', round(d['ms_per_step'],1), 'ok', d['config']['status_ok'])"
-  for c in k10 k20 l5 L5 l10 l20; do timeout 900 python bench.py --config $c --host-entry 0 --latency 0 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; summ $c; done
+  for c in k10 k20 l5 L5 l10 l20; do timeout 900 python bench.py --full --config $c --host-entry 0 --latency 0 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; summ $c; done
   timeout 300 python scripts/align_latency.py 2>&1 | grep pair_fast | tee $OUT/align_latency.txt
   timeout 600 python bench.py --gpus 1 --force-collective --steps 20 --warmup 3 --host-entry 0 --latency 0 --cpu-sample 0 > $OUT/bench_c3_nccl1.json 2> $OUT/bench_c3_nccl1.err; python3 -c "
 import json; d=json.loads([l for l in open('$OUT/bench_c3_nccl1.json') if l.startswith('{')][0]); c=d['config']; print('c3 with the RCCL process group (1 rank): value', round(d['value'],1), 'backend', c['backend'], 'gather ms', c['gather_ms_standalone'], 'complete', c['gathered_records_complete'])"

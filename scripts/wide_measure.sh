@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-wide}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_parity_gpu.py -m gpu -q -x --timeout 240 -k "wide_kernel" > $OUT/pytest.log 2>&1; tail -5 $OUT/pytest.log | cut -c1-300
-B="--cpu-sample 0 --host-entry 0 --latency 0 --other-configs 0"
+B="--full --cpu-sample 0 --host-entry 0 --latency 0 --other-configs 0"
 s() { python3 -c "
 import json,sys
 d=json.loads([l for l in open('$1') if l.startswith('{')][-1]); c=d['config']

@@ -70,6 +70,32 @@ def test_eight_ranks_uneven_total(built):
     assert c["gathered_records_complete"] is True
 
 
+@pytest.mark.timeout(300)
+def test_dump_outputs_writes_the_last_step(built, tmp_path):
+    """--dump-outputs DIR: the records and CIGAR ops of the last timed step as float64 .npy files, a seeded sample of the
+    pairs when there are more than bench.DUMP_PAIRS (here the dry stand-in: score = pair index, one op per pair)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    for n in (700, bench.DUMP_PAIRS + 1000):
+        d = tmp_path / str(n)
+        out = _run(["--gpus", "1", "--pairs", str(n), "--dump-outputs", str(d)])
+        assert out["steps"] == 3 and out["config"]["pairs_per_rank"] == [n]
+        rec, idx, ops = (np.load(d / f"{f}.npy") for f in ("records", "pair_index", "cigar_ops"))
+        assert rec.dtype == idx.dtype == ops.dtype == np.float64
+        k = min(n, bench.DUMP_PAIRS)
+        assert rec.shape == (k, 11) and idx.shape == (k,) and ops.shape == (k, 2)
+        assert (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < n
+        assert (rec[:, 1] == idx).all() and (rec[:, 10] == 1).all() and (rec[:, 0] == 0).all()
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64e6
+    # the same arguments draw the same sample
+    _run(["--gpus", "1", "--pairs", str(bench.DUMP_PAIRS + 1000), "--dump-outputs", str(tmp_path / "again")])
+    assert np.array_equal(np.load(tmp_path / "again" / "pair_index.npy"), idx)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=60)
+    assert p.returncode == 2 and "--gpus 1" in p.stderr
+
+
 def test_plan_prints_the_per_rank_footprint():
     """`bench.py --plan`: no GPU, no child processes -- what each rank of the configs[3] run holds in HBM, and whether it fits."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--plan", "--gpus", "8", "--config", "c4"], capture_output=True, text=True, timeout=60)
@@ -97,9 +123,14 @@ def test_configs_name_the_baseline_workloads():
     assert (a.total_pairs, a.length, a.seed) == (10_000_000, 1000, 4)
     a = bench.parse_args(["--config", "c5s"])
     assert (a.pairs, a.length, a.error, a.semi_global, a.no_adaptive) == (8, 100_000, 0.10, True, False)
-    # the default run also measures short legs of the other configurations (config.other_configs); any other run does not
-    assert bench.parse_args([]).other_configs == 1 and bench.parse_args(["--config", "c2"]).other_configs == 0
-    assert bench.parse_args(["--pairs", "1000"]).other_configs == 0 and bench.parse_args(["--gpus", "2"]).other_configs == 0
+    # the default run with --full also measures short legs of the other configurations (config.other_configs); any other run does not
+    assert bench.parse_args(["--full"]).other_configs == 1 and bench.parse_args(["--full", "--config", "c2"]).other_configs == 0
+    assert bench.parse_args(["--full", "--pairs", "1000"]).other_configs == 0 and bench.parse_args(["--full", "--gpus", "2"]).other_configs == 0
+    # ... and --full turns the CPU baseline, host-entry and latency legs on by default; a plain run has none of them
+    a = bench.parse_args(["--full"])
+    assert (a.cpu_sample, a.host_entry, a.latency) == (150_000, 1, 1)
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.other_configs, a.cpu_sample, a.host_entry, a.latency, a.full) == (0, 0, 0, 0, False) and (a.steps, a.warmup) == (7, 2)
     # (round 5: every configuration that used to have a line only under profiles/ is a driver-observed leg)
     legs = [name for name, _, _ in bench.OTHER_LEGS]
     assert len(legs) >= 10 and {"c2", "c2m", "p242", "k10", "k20", "l5", "l20", "L5", "c4", "c5s", "c5s32"} <= set(legs)

@@ -35,7 +35,7 @@ def test_two_ranks_share_one_gpu_against_oracle(built, tmp_path, total):
     from oracle import oracle as O
     dump = str(tmp_path / "records.npy")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpus", "--config", "c4",
-                        "--total-pairs", str(total), "--steps", "2", "--warmup", "1", "--dump-records", dump],
+                        "--total-pairs", str(total), "--steps", "2", "--warmup", "1", "--dump-records", dump, "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=850)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -129,6 +129,32 @@ def test_bench_force_collective_runs_the_nccl_lines(built, tmp_path):
                    ("qend", L.REC_QEND), ("align_len", L.REC_ALIGN_LEN), ("matches", L.REC_MATCHES), ("gaps", L.REC_GAPS),
                    ("gap_regions", L.REC_GAP_REGIONS)):
         assert np.array_equal(rec[:, col].astype(np.int64), getattr(want, f).astype(np.int64)), f
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_against_oracle(built, tmp_path):
+    """bench.py --dump-outputs on the real kernels: the records and CIGAR ops it writes for the last timed step are the
+    oracle's, pair by pair and op by op."""
+    import wfa_amd as w
+    from wfa_amd import _lib as L
+    from oracle import oracle as O
+    n, seed = 3000, 61
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pairs", str(n), "--seed", str(seed),
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=_clean_env(), capture_output=True, text=True, timeout=550)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["config"]["status_ok"] == n and "roofline" not in out and "cpu_baseline" not in out
+    rec, idx, ops = (np.load(tmp_path / f"{f}.npy") for f in ("records", "pair_index", "cigar_ops"))
+    assert np.array_equal(idx, np.arange(n)) and rec.shape == (n, L.REC_OPS_OFF_LO)
+    want = O.align_batch(O.make_params(adaptive=(10, 50, 1)), *w.generate_pairs(seed=seed, n_pairs=n, length=1000, error_rate=0.05),
+                         n_threads=8, want_ops=True)
+    for f, col in (("status", L.REC_STATUS), ("score", L.REC_SCORE), ("tbegin", L.REC_TBEGIN), ("tend", L.REC_TEND),
+                   ("qbegin", L.REC_QBEGIN), ("qend", L.REC_QEND), ("align_len", L.REC_ALIGN_LEN), ("matches", L.REC_MATCHES),
+                   ("gaps", L.REC_GAPS), ("gap_regions", L.REC_GAP_REGIONS), ("ops_len", L.REC_OPS_LEN)):
+        assert np.array_equal(rec[:, col], getattr(want, f).astype(np.float64)), f
+    words = np.concatenate([want.pair_ops(i) for i in range(n)]).astype(np.uint64)
+    assert np.array_equal(ops, np.stack([words >> np.uint64(32), words & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
 
 
 @pytest.mark.timeout(1500)
