@@ -61,7 +61,8 @@ enum {
     WFAHIP_PAIR_OK        = 0,
     WFAHIP_PAIR_EMPTY     = 1, /* ErrEmptySeq,   wfa.go:204-206 */
     WFAHIP_PAIR_TOO_LONG  = 2, /* ErrSeqTooLong, wfa.go:207-209 */
-    WFAHIP_PAIR_NO_MEMORY = 4  /* wavefront arena could not be grown enough for this pair */
+    WFAHIP_PAIR_NO_MEMORY = 4, /* wavefront arena could not be grown enough for this pair */
+    WFAHIP_PAIR_OVER_MAX  = 8  /* wfahip_score_batch only: the pair's score exceeds max_score */
 };
 
 /* wfa.go:190 MaxSeqLen */
@@ -123,7 +124,9 @@ typedef struct {
                                   (a wave per pair, one / two diagonals per lane: batches too small to fill the GPU),
                                   16 = wfa_blk_kernel<64, 1, false, 1, false, false> (wfahip_align_pair: one launch, forward pass and backtrace),
                                   18 = wfa_wide_kernel (round 6: semi-global reads up to 2 047 bases, a workgroup per pair with the rows in 16-bit LDS rings),
-                                  17 = wfa_teamc_kernel (wide wavefronts: a team of workgroups per pair, one backtrace word per diagonal) */
+                                  17 = wfa_teamc_kernel (wide wavefronts: a team of workgroups per pair, one backtrace word per diagonal),
+                                  19 = wfa_score_kernel (wfahip_score_batch, global pairs), 20 = wfa_wide_kernel<.., SCORE> (wfahip_score_batch,
+                                  semi-global pairs) */
     uint32_t ladder_start_level; /* arena level the long-pair ladder of this call started on (0 unless a learned hint applied) */
 } wfahip_timing;
 
@@ -154,6 +157,30 @@ int  wfahip_align_batch(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *
                         const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs,
                         wfahip_results *out);
 void wfahip_results_free(wfahip_results *r);
+
+/* Score only: the AlignmentResult.Score of every pair (wfa_cigar.go:30-48, set from the forward pass at wfa.go:714) without
+ * the CIGAR, the match region or the statistics -- WFA2-lib's "score only" alignment scope.  Inputs as wfahip_align_batch.
+ * For every pair, status and score equal what wfahip_align_batch returns for the same pair and params (score 0 unless
+ * status is WFAHIP_PAIR_OK), global or semi-global, with wf-adaptive on or off, any penalties that entry takes, any bytes.
+ * max_score (0 = no bound): a pair whose score would exceed it stops as soon as the score step passes it and gets
+ * WFAHIP_PAIR_OVER_MAX -- exactly: global pairs when no M[s][m - n] reached the end by s = max_score, semi-global pairs when no
+ * row up to max_score held an end cell (wfa.go:270-375) and none terminated.  Whole-call errors are those of wfahip_align_batch.
+ * Only the forward pass runs, with the last rows on chip: no wavefront arena is allocated, nothing is kept for a backtrace.
+ * Global pairs of reads up to 2 047 bases with e / g == 1 and x / g, (o+e) / g up to 7 (g = gcd(x, o+e, e)) run on
+ * wfa_score_kernel; semi-global pairs up to 2 047 bases of the shapes wfahip_align_pair lists run on the score instances of
+ * wfa_wide_kernel; every other pair -- a shape without an instance, a byte outside ACGT, a longer read, a band wider than the
+ * kernel's 248 diagonals -- is aligned by the full path of wfahip_align_batch and only its score kept.  wfahip_last_timing:
+ * main_kernel_kind 19 (wfa_score_kernel) or 20 (wfa_wide_kernel, score instances), n_retried_pairs = pairs that took the
+ * full path, arena_bytes = 0 unless some did.  Release out with wfahip_scores_free (the arrays are malloc'd). */
+typedef struct {
+    uint64_t  n;
+    int32_t  *status; /* WFAHIP_PAIR_OK / _EMPTY / _TOO_LONG / _NO_MEMORY / _OVER_MAX */
+    uint32_t *score;  /* == AlignmentResult.Score of the same pair; 0 unless status is OK */
+} wfahip_scores;
+int  wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
+                        const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
+                        uint64_t n_pairs, uint32_t max_score, wfahip_scores *out);
+void wfahip_scores_free(wfahip_scores *s);
 
 /* Device-resident variant: every pointer is a device address on the context's GPU (caller-owned).
  * d_rec receives n_pairs records of WFAHIP_REC_WORDS u32; d_ops receives the CIGAR ops

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libwfahip.so")
 # whole-call codes / per-pair status (include/wfa_hip.h)
 OK, ERR_NO_DEVICE, ERR_BAD_ARG, ERR_OOM, ERR_HIP, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 PAIR_OK, PAIR_EMPTY, PAIR_TOO_LONG, PAIR_NO_MEMORY = 0, 1, 2, 4
+PAIR_OVER_MAX = 8  # wfahip_score_batch: the pair's score exceeds max_score
 MAX_SEQ_LEN = (1 << 29) - 1
 REC_WORDS = 16
 (REC_STATUS, REC_SCORE, REC_TBEGIN, REC_TEND, REC_QBEGIN, REC_QEND, REC_ALIGN_LEN, REC_MATCHES, REC_GAPS,
@@ -25,7 +26,7 @@ EXPORTS = [
     "wfahip_pending", "wfahip_collect", "wfahip_create_multi", "wfahip_destroy_multi", "wfahip_multi_size",
     "wfahip_multi_ctx", "wfahip_align_batch_multi", "wfahip_debug_compact_arena",
     "wfahip_generate_pairs_device", "wfahip_align_pair", "wfahip_last_error", "wfahip_debug_clock",
-    "wfahip_debug_team_compact",
+    "wfahip_debug_team_compact", "wfahip_score_batch", "wfahip_scores_free",
 ]
 
 
@@ -43,6 +44,10 @@ class Results(C.Structure):
                 ("gaps", C.POINTER(C.c_uint32)), ("gap_regions", C.POINTER(C.c_uint32)),
                 ("ops_off", C.POINTER(C.c_uint64)), ("ops_len", C.POINTER(C.c_uint32)),
                 ("ops", C.POINTER(C.c_uint64)), ("n_ops", C.c_uint64)]
+
+
+class Scores(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("status", C.POINTER(C.c_int32)), ("score", C.POINTER(C.c_uint32))]
 
 
 class Timing(C.Structure):
@@ -79,6 +84,9 @@ def lib():
         L.wfahip_align_batch.restype = C.c_int
         L.wfahip_align_batch.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, C.POINTER(Results)]
         L.wfahip_results_free.argtypes = [C.POINTER(Results)]
+        L.wfahip_score_batch.restype = C.c_int
+        L.wfahip_score_batch.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, C.POINTER(Scores)]
+        L.wfahip_scores_free.argtypes = [C.POINTER(Scores)]
         L.wfahip_align_batch_device.restype = C.c_int
         L.wfahip_align_batch_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, vp, vp,
                                                 u64, C.POINTER(u64), vp]

@@ -273,6 +273,53 @@ class Aligner:
                                                   vp(t_woff), vp(t_len), n, C.byref(res)), "wfahip_align_batch_packed")
         return _take_results(res, n)
 
+    # -- new: score only (include/wfa_hip.h: wfahip_score_batch) -----------------------------------
+    def score_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0):
+        """(status: np.int32[n], score: np.uint32[n]) of every pair -- the AlignmentResult.Score and status align_arrays would
+        give, from the forward pass alone (no CIGAR, no arena).  max_score > 0: a pair whose score exceeds it gets status
+        PAIR_OVER_MAX (8) and score 0."""
+        n = int(len(q_len))
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+        if len(q_off) != n or len(t_off) != n or len(t_len) != n:
+            raise ValueError("offset and length arrays differ in length")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        res = L.Scores()
+        prm = self._params()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = L.lib().wfahip_score_batch(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len), n,
+                                        int(max_score), C.byref(res))
+        L.check(rc, "wfahip_score_batch" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        try:
+            if n == 0:
+                return np.zeros(0, np.int32), np.zeros(0, np.uint32)
+            return (np.ctypeslib.as_array(res.status, shape=(n,)).copy(), np.ctypeslib.as_array(res.score, shape=(n,)).copy())
+        finally:
+            L.lib().wfahip_scores_free(C.byref(res))
+
+    def ScoreBatch(self, qs: Sequence[bytes], ts: Sequence[bytes], max_score: int = 0):
+        """(status, score) arrays of the pairs (qs[i], ts[i]): see score_arrays."""
+        if len(qs) != len(ts):
+            raise ValueError("qs and ts differ in length")
+        if not qs:
+            return np.zeros(0, np.int32), np.zeros(0, np.uint32)
+        return self.score_arrays(*make_blob(qs, ts), max_score=max_score)
+
+    def Score(self, q: bytes, t: bytes) -> int:
+        """AlignmentResult.Score of Align(q, t) without the alignment; raises ErrEmptySeq / ErrSeqTooLong like Align."""
+        if len(q) == 0 or len(t) == 0:
+            raise ErrEmptySeq
+        if len(q) > MaxSeqLen or len(t) > MaxSeqLen:
+            raise ErrSeqTooLong
+        st, sc = self.ScoreBatch([bytes(q)], [bytes(t)])
+        if st[0] != L.PAIR_OK:
+            raise WfaError("pair could not be aligned (out of device memory)")
+        return int(sc[0])
+
     # -- new: one pair at a time behind the batch ----------------------------------------------------
     def Submit(self, q: bytes, t: bytes) -> int:
         """Hand in one pair (copied) and return its ticket; Collect() aligns everything submitted as ONE batch.  This is

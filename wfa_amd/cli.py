@@ -7,6 +7,7 @@ the alignments computed by the HIP path -- all pairs of the file in ONE batch ca
 
 Options:  -g  do not use global alignment          -a  do not use adaptive reduction
           -N  do not output alignment (benchmark)  -t  only show the aligned region
+          -s  score only: print "align-score : N" per pair (no alignment is computed)
 """
 from __future__ import annotations
 
@@ -54,6 +55,7 @@ def main(argv=None) -> int:
     ap.add_argument("-a", dest="no_adaptive", action="store_true", help="do not use adaptive reduction")
     ap.add_argument("-N", dest="no_output", action="store_true", help="do not output alignment (for benchmark)")
     ap.add_argument("-t", dest="trim", action="store_true", help="only show the aligned region")
+    ap.add_argument("-s", dest="score_only", action="store_true", help="score only: print the alignment score of each pair")
     ap.add_argument("seqs", nargs="*")
     args = ap.parse_args(argv)
 
@@ -74,6 +76,18 @@ def main(argv=None) -> int:
     if not args.no_adaptive:
         algn.AdaptiveReduction(wfa.AdaptiveReductionOption(10, 50, 1))  # wfa-go.go:100-106
     try:
+        if args.score_only:  # wfahip_score_batch: the forward pass alone
+            status, scores = algn.ScoreBatch([p[0] for p in pairs], [p[1] for p in pairs])
+            out = sys.stdout
+            for st, sc in zip(status, scores):
+                if st != wfa._lib.PAIR_OK:
+                    print(wfa.ErrEmptySeq if st == wfa._lib.PAIR_EMPTY else wfa.ErrSeqTooLong if st == wfa._lib.PAIR_TOO_LONG
+                          else "pair could not be aligned (out of device memory)", file=sys.stderr)
+                    return 1
+                if not args.no_output:
+                    out.write(f"align-score : {int(sc)}\n")
+            out.flush()
+            return 0
         results, errors = algn.AlignBatch([p[0] for p in pairs], [p[1] for p in pairs])
         out = sys.stdout
         for (q, t), r, err in zip(pairs, results, errors):

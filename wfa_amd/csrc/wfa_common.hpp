@@ -28,6 +28,7 @@ constexpr uint32_t TAG_BITS = 3, TAG_MASK = 7;
 // internal per-pair status values written to rec[STATUS] while a batch is in flight
 enum : uint32_t {
     ST_OK = 0, ST_EMPTY = 1, ST_TOO_LONG = 2, ST_NO_MEMORY = 4,
+    ST_OVER_MAX = 8,           // score-only kernels: the pair's score exceeds the caller's bound (WFAHIP_PAIR_OVER_MAX)
     ST_PENDING = 0xFFFFFFFFu,  // not processed yet
     DONE_NOT_OK = 0x80000000u, // done_q entry .x = (index in chunk + 1) | DONE_NOT_OK for pairs without a backtrace
     DONE_TAKEN  = 0xFFFFFFFFu, // done_q entry .x after the streaming backtrace kernel has processed it
@@ -127,6 +128,9 @@ struct KParams {
     uint32_t  compact_fmt;           // compact arena layout (CompactView): 0 = rows + directory; no directory: 1 = 64 words
                                      // per score, diagonal k at slot k & 63; 3 = tiles of 8 scores x 64 diagonals;
                                      // 4 = 256 words per score, slot k & 255; 5 = 32 words per score, slot k & 31
+    // ---- score-only kernels (wfa_score.hpp, wfa_wide_kernel<.., SCORE = true>): no arena, no backtrace
+    uint2    *score_out;             // per pair of the batch (index = pair id): {status, score}
+    uint32_t  max_score;             // a pair whose score would exceed it stops with ST_OVER_MAX (0 = no bound)
 };
 
 }  // namespace wfa

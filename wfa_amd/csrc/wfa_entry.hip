@@ -11,6 +11,8 @@
 #include "wfa_fwd.hpp"
 #include "wfa_long.hpp"
 #include "wfa_finalize.hpp"
+#include "wfa_wide.hpp"
+#include "wfa_score.hpp"
 
 using namespace wfa;
 
@@ -818,6 +820,147 @@ extern "C" int wfahip_align_batch(wfahip_ctx *ctx, const wfahip_params *p, const
                                   const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs,
                                   wfahip_results *out) {
     WFAHIP_GUARD(align_batch_entry(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, out))
+}
+
+// ---- score only (wfahip_score_batch): the forward pass without arena or backtrace -- wfa_score_kernel for global pairs, the score
+// instances of wfa_wide_kernel for semi-global ones (wfa_score.hip); whatever they hand back goes through the full path above
+namespace wfa {
+hipError_t wfa_launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+}  // namespace wfa
+
+extern "C" void wfahip_scores_free(wfahip_scores *s) {
+    if (!s) return;
+    std::free(s->status), std::free(s->score);
+    s->status = nullptr, s->score = nullptr, s->n = 0;
+}
+
+static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                            const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
+                            wfahip_scores *out) {
+    if (!ctx || !out) return WFAHIP_ERR_BAD_ARG;
+    std::memset(out, 0, sizeof *out);
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_pairs == 0) return WFAHIP_OK;
+    if (!q_off || !q_len || !t_off || !t_len || (!seq_blob && blob_bytes)) return WFAHIP_ERR_BAD_ARG;
+    // the checks of align_batch_impl: every pair that is neither empty nor too long lies inside the blob
+    uint32_t max_len = 1;
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (q_len[i] <= WFAHIP_MAX_SEQ_LEN && t_len[i] <= WFAHIP_MAX_SEQ_LEN && q_len[i] && t_len[i]) {
+            if (q_off[i] > blob_bytes || q_len[i] > blob_bytes - q_off[i] || t_off[i] > blob_bytes || t_len[i] > blob_bytes - t_off[i])
+                return WFAHIP_ERR_BAD_ARG;
+            max_len = std::max(max_len, std::max(q_len[i], t_len[i]));
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const auto t_start = std::chrono::steady_clock::now();
+    std::vector<uint2> res(n_pairs);
+    wfahip_timing      tm{};
+
+    KParams P{};
+    P.x = p->mismatch, P.o = p->gap_open, P.e = p->gap_ext, P.oe = p->gap_open + p->gap_ext;
+    P.g = gcd_u32(gcd_u32(P.x, P.oe), P.e);
+    P.global_alignment = p->global_alignment ? 1u : 0u, P.adaptive = p->adaptive ? 1u : 0u;
+    P.min_wf_len = p->min_wf_len, P.max_dist_diff = p->max_dist_diff;
+    const uint32_t dx = P.x / P.g, doe = P.oe / P.g, de = P.e / P.g;
+    const bool     glob  = P.global_alignment != 0u;
+    const int      shape = fwd_shape(dx, doe, de);
+    const bool     on_kernel = glob ? score_shape_ok(dx, doe, de) : shape >= 0;
+    if (on_kernel) {
+        hipStream_t st = ctx->stream;
+        if ((rc = ensure(ctx, ctx->in_blob, blob_bytes + 32))) return rc;
+        if ((rc = ensure(ctx, ctx->in_qoff, n_pairs * 8))) return rc;
+        if ((rc = ensure(ctx, ctx->in_toff, n_pairs * 8))) return rc;
+        if ((rc = ensure(ctx, ctx->in_qlen, n_pairs * 4))) return rc;
+        if ((rc = ensure(ctx, ctx->in_tlen, n_pairs * 4))) return rc;
+        if ((rc = ensure(ctx, ctx->score_out, n_pairs * 8))) return rc;
+        if (blob_bytes) HIP_TRY(hipMemcpyAsync(ctx->in_blob.p, seq_blob, blob_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->in_qoff.p, q_off, n_pairs * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->in_toff.p, t_off, n_pairs * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+        P.blob = static_cast<const uint8_t *>(ctx->in_blob.p), P.blob_bytes = blob_bytes;
+        P.q_off = static_cast<const uint64_t *>(ctx->in_qoff.p), P.t_off = static_cast<const uint64_t *>(ctx->in_toff.p);
+        P.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), P.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p);
+        P.score_out = static_cast<uint2 *>(ctx->score_out.p), P.max_score = max_score;
+        P.dx = dx, P.doe = doe, P.de = de, P.census = 0u, P.wide_exact = 0u, P.work = nullptr;
+        const uint32_t L = std::min<uint32_t>(max_len, glob ? SCORE_MAX_LEN : WIDE_MAX_LEN);  // (longer pairs come back ST_REDO_LDS)
+        const uint32_t seq_words = (L + 15) / 16 + 1;
+        P.lds_seq_words = seq_words;
+        // chunks: the wide kernel's checkpoints take WIDE_CKPT_WORDS words per pair of a chunk
+        const uint64_t chunk = glob ? (1ull << 24) : (1ull << 18);
+        const bool     two_phase = !glob && P.adaptive != 0u;
+        if (two_phase && (rc = ensure(ctx, ctx->wide_ckpt, (size_t)std::min<uint64_t>(chunk, n_pairs) * WIDE_CKPT_WORDS * 4))) return rc;
+        P.wide_ckpt = static_cast<uint32_t *>(ctx->wide_ckpt.p), P.wide_ckpt_on = two_phase ? 1u : 0u;
+        const size_t lds_g = (size_t)score_lds_words(seq_words) * 4;
+        const size_t lds_w = (size_t)wide_lds_words(seq_words, L) * 4, lds_n = (size_t)wide_lds_words_narrow(seq_words) * 4;
+        const int    waves = lds_w > 12 * 1024 ? 4 : 1;  // (as the full path: rings above 12 KB are shared by four waves)
+        P.sub_lds_words = wide_row_hw(L);
+        if (!ctx->ev0) HIP_TRY(hipEventCreate(&ctx->ev0));
+        if (!ctx->ev1) HIP_TRY(hipEventCreate(&ctx->ev1));
+        HIP_TRY(hipEventRecord(ctx->ev0, st));
+        for (uint64_t c0 = 0; c0 < n_pairs; c0 += chunk) {
+            const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_pairs - c0);
+            P.chunk_first = (uint32_t)c0, P.chunk_n = cn;
+            if (glob) {
+                HIP_TRY(wfa_launch_score(P, cn, lds_g, st));
+            } else {
+                HIP_TRY(wfa_launch_wide_score(shape, 0, waves, P, cn, lds_w, st));
+                if (two_phase) {
+                    HIP_TRY(wfa_launch_wide_score(shape, 1, 1, P, cn, lds_n, st));
+                    tm.n_launches++;
+                }
+            }
+            tm.n_launches++, tm.n_main_launches++;
+        }
+        HIP_TRY(hipEventRecord(ctx->ev1, st));
+        HIP_TRY(hipMemcpyAsync(res.data(), ctx->score_out.p, n_pairs * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        tm.kernel_ms = tm.main_kernel_ms = ms;
+        tm.main_kernel_kind = glob ? 19u : 20u;
+    } else {
+        for (uint64_t i = 0; i < n_pairs; i++) res[i] = make_uint2(ST_REDO_BAND, 0u);
+    }
+    // what the kernels handed back (bytes outside ACGT, a band or a length they cannot hold, a shape without an instance): the full path
+    std::vector<uint64_t> fb;
+    for (uint64_t i = 0; i < n_pairs; i++)
+        if (res[i].x >= ST_REDO_BYTES) fb.push_back(i);
+    if (!fb.empty()) {
+        std::vector<uint64_t> qo(fb.size()), to(fb.size());
+        std::vector<uint32_t> ql(fb.size()), tl(fb.size());
+        for (size_t j = 0; j < fb.size(); j++) qo[j] = q_off[fb[j]], to[j] = t_off[fb[j]], ql[j] = q_len[fb[j]], tl[j] = t_len[fb[j]];
+        wfahip_results r;
+        if ((rc = align_batch_entry(ctx, p, seq_blob, blob_bytes, qo.data(), ql.data(), to.data(), tl.data(), fb.size(), &r))) return rc;
+        for (size_t j = 0; j < fb.size(); j++) {
+            const uint32_t st = (uint32_t)r.status[j], sc = r.score[j];
+            res[fb[j]] = (st == ST_OK && max_score != 0u && sc > max_score) ? make_uint2(ST_OVER_MAX, 0u) : make_uint2(st, sc);
+        }
+        wfahip_results_free(&r);
+        const wfahip_timing &f = ctx->timing;
+        tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = f.arena_bytes;
+        if (!on_kernel) tm.main_kernel_ms = f.main_kernel_ms, tm.n_main_launches = f.n_main_launches, tm.main_kernel_kind = f.main_kernel_kind;
+    }
+    tm.n_retried_pairs = (uint32_t)fb.size();
+    out->status = static_cast<int32_t *>(std::malloc(n_pairs * 4));
+    out->score  = static_cast<uint32_t *>(std::malloc(n_pairs * 4));
+    if (!out->status || !out->score) {
+        wfahip_scores_free(out);
+        return WFAHIP_ERR_OOM;
+    }
+    out->n = n_pairs;
+    for (uint64_t i = 0; i < n_pairs; i++) out->status[i] = (int32_t)res[i].x, out->score[i] = res[i].x == ST_OK ? res[i].y : 0u;
+    tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    ctx->timing = tm;
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                                  const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
+                                  wfahip_scores *out) {
+    WFAHIP_GUARD(score_batch_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, max_score, out))
 }
 
 // ---- pre-packed input (a quarter of the bytes cross PCIe)

@@ -87,7 +87,10 @@ WFA_DEV void wide_next2(wide_us2 a, wide_us2 b, wide_us2 c, wide_us2 d, wide_us2
 #endif
 // NW: waves of the pair's workgroup (PHASE 0: the rings of a 1 kbp pair are 25 KB, six workgroups a CU -- with one wave each the SIMDs would
 // hold a wave and a half; the waves of a workgroup take a row's rounds side by side)
-template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1>
+// SCORE (wfahip_score_batch): the score only -- no arena rows, no directory, no census; a semi-global pair stops at the first
+// row whose end-cell search finds a hit (the lowest score with one, wfa.go:270-375: a row's M is final after its extend and
+// reduce), and one {status, score} per pair goes to P.score_out
+template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1, bool SCORE = false>
 __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(const KParams P) {
     static_assert(DX >= 1 && DOE >= 1 && DX <= 4 && DOE <= 4, "ring depths of one to four score steps");
     static_assert(NW == 1 || (PHASE == 0 && (NW == 2 || NW == 4)), "the narrow phase is one wave");
@@ -164,8 +167,12 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
         }
         if (status != ST_PENDING) {
             if (tid == 0) {
-                P.pair_meta[idx] = make_uint4(status, 0u, 0u, 0u);
-                if (status >= ST_REDO_BYTES) push_redo(P, pair, status);
+                if constexpr (SCORE) {
+                    P.score_out[pair] = make_uint2(status, 0u);
+                } else {
+                    P.pair_meta[idx] = make_uint4(status, 0u, 0u, 0u);
+                    if (status >= ST_REDO_BYTES) push_redo(P, pair, status);
+                }
             }
             return;
         }
@@ -203,6 +210,7 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
         int      fk = 0, fh = 0;
         int      hf = 0;  // extended offset of M[s_final][Ak]
         uint32_t si0 = 0u;
+        bool     over_max = false;
         if constexpr (PHASE == 1) {
             si0 = rfl(ck[1]), top = rfl(ck[2]), cells = rfl(ck[3]), found = rfl(ck[4]) != 0u, fs = rfl(ck[5]), fk = (int)rfl(ck[6]), fh = (int)rfl(ck[7]);
             blo0 = (int)rfl(ck[8]), blo1 = (int)rfl(ck[9]), blo2 = (int)rfl(ck[10]), blo3 = (int)rfl(ck[11]);
@@ -212,6 +220,12 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
 
         for (uint32_t si = si0;; si++) {
             const uint32_t s = si * g;
+            if constexpr (SCORE) {
+                if (P.max_score != 0u && s > P.max_score) {  // every row below s was computed: no hit, no termination
+                    over_max = true;
+                    break;
+                }
+            }
             // ---- the range of next(s) (wfa.go:557-563) and of the seeds
             int lo = BIG, hi = -BIG;
             if (si != 0u) {
@@ -232,7 +246,7 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
             const uint32_t slot = si & 3u;
             const int ulo = imin2(lo, imin2(get_lo(slot), plo)), uhi = imax2(hi, imax2(get_hi(slot), phi));
             const int W = hi >= lo ? hi - lo + 1 : 0;
-            if ((uint64_t)(top + (uint32_t)W + 4u) / 2u + 4ull * (si + 2u) > cap) {
+            if (!SCORE && (uint64_t)(top + (uint32_t)W + 4u) / 2u + 4ull * (si + 2u) > cap) {
                 overflow = true, ovf_si = si, ovf_why = 1u, ovf_span = (uint32_t)W;
                 break;
             }
@@ -250,7 +264,7 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
             int      mlo = BIG, mhi = -BIG, mind = BIG, maxd = -BIG;
             bool     term = false;
             uint32_t ncell = 0u;
-            const bool census = P.census != 0u;  // (REC_CELLS: the stored words are only counted when somebody asks)
+            const bool census = !SCORE && P.census != 0u;  // (REC_CELLS: the stored words are only counted when somebody asks)
             uint32_t carryM = 0u, carryI = 0u;  // M[s-o-e][t0 - 1], I[s-e][t0 - 1] as they were before the previous tile overwrote them
             const bool ecs = !glob && !found;   // the end-cell search is on: the wide rows note its candidates while they are computed
             int        cdn = -BIG, cup = BIG;
@@ -463,7 +477,7 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
                                 st4(Mn, r0, nM);
                                 *reinterpret_cast<uint2 *>(rowI + r0) = make_uint2(I0, I1);
                                 *reinterpret_cast<uint2 *>(rowD + r0) = make_uint2(D0, D1);
-                                *reinterpret_cast<uint2 *>(arow + ((int64_t)top + (int64_t)(k0 - lo))) = make_uint2(W0, W1);
+                                if constexpr (!SCORE) *reinterpret_cast<uint2 *>(arow + ((int64_t)top + (int64_t)(k0 - lo))) = make_uint2(W0, W1);
                             }
                             if constexpr (NW == 1) lds_sync();
                             continue;
@@ -481,13 +495,15 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
                     finish4(k0, nM);
                     if (lin) {
                         st4(Mn, r0, nM), st4(rowI, r0, nI), st4(rowD, r0, nD);
-                        uint16_t *const ap = arow + ((int64_t)top + (int64_t)(k0 - lo));  // (only dereferenced where act)
-                        if (act[0] && act[3]) {
-                            *reinterpret_cast<uint2 *>(ap) = make_uint2(wd[0] | (wd[1] << 16), wd[2] | (wd[3] << 16));
-                        } else {
+                        if constexpr (!SCORE) {
+                            uint16_t *const ap = arow + ((int64_t)top + (int64_t)(k0 - lo));  // (only dereferenced where act)
+                            if (act[0] && act[3]) {
+                                *reinterpret_cast<uint2 *>(ap) = make_uint2(wd[0] | (wd[1] << 16), wd[2] | (wd[3] << 16));
+                            } else {
 #pragma unroll
-                            for (int u = 0; u < 4; u++)
-                                if (act[u]) ap[u] = (uint16_t)wd[u];
+                                for (int u = 0; u < 4; u++)
+                                    if (act[u]) ap[u] = (uint16_t)wd[u];
+                            }
                         }
                     }
                     if constexpr (NW == 1) lds_sync();  // (several waves: the next round touches other diagonals, and the carry has its own slots)
@@ -521,7 +537,7 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
                     if (single) sM = nM, sI = nI, sD = nD;
                     else cell_stats(k, nM, nI, nD);
                     if (in) Mn[ri] = (uint16_t)nM, rowI[ri] = (uint16_t)nI, rowD[ri] = (uint16_t)nD;
-                    if (act) arow[top + (uint32_t)(k - lo)] = (uint16_t)wd;
+                    if (!SCORE && act) arow[top + (uint32_t)(k - lo)] = (uint16_t)wd;
                     lds_sync();
                 }
             }
@@ -714,8 +730,11 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
                 cells += c;
             }
             }  // (rows of more than one tile)
+            if constexpr (SCORE) {
+                if (found) break;  // the lowest score with an end cell: nothing above it can lower it
+            }
             // ---- the row's directory entry
-            if (tid == 0) {
+            if (!SCORE && tid == 0) {
                 const bool any = nhi >= nlo;
                 *reinterpret_cast<uint4 *>(adir - 4u * (si + 1u)) = make_uint4(any ? top + (uint32_t)(nlo - lo) : 0u, any ? (uint32_t)nlo : 0u, any ? (uint32_t)(nhi - nlo + 1) : 0u, 0u);
             }
@@ -752,12 +771,19 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
                             ck[12] = (uint32_t)bhi0, ck[13] = (uint32_t)bhi1, ck[14] = (uint32_t)bhi2, ck[15] = (uint32_t)bhi3;
                             ck[16] = (uint32_t)plo, ck[17] = (uint32_t)phi;
                             ck[0] = 1u;
-                            P.pair_meta[idx] = make_uint4(ST_PENDING, 0u, 0u, 0u);  // (the second launch writes the pair's record)
+                            if constexpr (!SCORE) P.pair_meta[idx] = make_uint4(ST_PENDING, 0u, 0u, 0u);  // (the second launch writes the pair's record)
                         }
                         return;
                     }
                 }
             }
+        }
+        if constexpr (SCORE) {
+            if (tid == 0) {
+                const uint32_t st = overflow ? ST_REDO_ARENA : (over_max ? ST_OVER_MAX : ST_OK);
+                P.score_out[pair] = make_uint2(st, st == ST_OK ? ((glob || !found) ? s_final : fs) : 0u);
+            }
+            return;
         }
         if (overflow) {
             if (tid == 0) {
