@@ -314,6 +314,8 @@ int  wfahip_last_timing(const wfahip_ctx *ctx, wfahip_timing *out);
  *                                 its write-through has landed (measured; wfa_team.hpp)
  *   "arena_poison"                tests: fill the arena with a pattern before every forward launch (no kernel may read a word
  *                                 it did not write in this launch)
+ *   "duo_pk"  0|1                 1 (default): wfa_duo_kernel holds its rings as 16-bit pairs; 0: its 32-bit-ring reference
+ *                                 wfa_duo32_kernel (tests and A/B runs: both write the same arena words, byte for byte)
  *   "team_paged"  0|1             1 (default): the teams of the long-pair kernel share ONE pool of arena pages -- a pair holds what it
  *                                 needs, up to eight teams run at once -- instead of a slot each sized for the worst pair
  *   "team_xcd"  0|1|2             teams of one XCD's 32 CUs (1); 2 (default): ... and a team that finds all its workgroups on one

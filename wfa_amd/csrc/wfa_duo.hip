@@ -9,24 +9,28 @@ namespace wfa {
 
 namespace {
 template <int DX, int DOE>
-hipError_t go_duo(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st, bool census) {
-    if (census)
+hipError_t go_duo(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st, bool census, bool pk) {
+    if (pk && census)
         hipLaunchKernelGGL((wfa_duo_kernel<true, DX, DOE>), dim3(grid), dim3(64), lds_bytes, st, P);
-    else
+    else if (pk)
         hipLaunchKernelGGL((wfa_duo_kernel<false, DX, DOE>), dim3(grid), dim3(64), lds_bytes, st, P);
+    else if (census)
+        hipLaunchKernelGGL((wfa_duo32_kernel<true, DX, DOE>), dim3(grid), dim3(64), lds_bytes, st, P);
+    else
+        hipLaunchKernelGGL((wfa_duo32_kernel<false, DX, DOE>), dim3(grid), dim3(64), lds_bytes, st, P);
     return hipGetLastError();
 }
 }  // namespace
 
-// shape: index of the penalty shape (wfa_fwd.hpp: fwd_shape())
-hipError_t wfa_launch_duo(int shape, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st, bool census) {
+// shape: index of the penalty shape (wfa_fwd.hpp: fwd_shape()); pk: the packed rings (wfa_duo_kernel), else wfa_duo32_kernel
+hipError_t wfa_launch_duo(int shape, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st, bool census, bool pk) {
     switch (shape) {
-    case 0: return go_duo<2, 4>(P, grid, lds_bytes, st, census);
-    case 1: return go_duo<1, 3>(P, grid, lds_bytes, st, census);
-    case 2: return go_duo<1, 2>(P, grid, lds_bytes, st, census);
-    case 3: return go_duo<2, 3>(P, grid, lds_bytes, st, census);
-    case 4: return go_duo<2, 2>(P, grid, lds_bytes, st, census);
-    case 5: return go_duo<3, 3>(P, grid, lds_bytes, st, census);
+    case 0: return go_duo<2, 4>(P, grid, lds_bytes, st, census, pk);
+    case 1: return go_duo<1, 3>(P, grid, lds_bytes, st, census, pk);
+    case 2: return go_duo<1, 2>(P, grid, lds_bytes, st, census, pk);
+    case 3: return go_duo<2, 3>(P, grid, lds_bytes, st, census, pk);
+    case 4: return go_duo<2, 2>(P, grid, lds_bytes, st, census, pk);
+    case 5: return go_duo<3, 3>(P, grid, lds_bytes, st, census, pk);
     }
     return hipErrorInvalidValue;
 }

@@ -36,6 +36,7 @@
 #pragma once
 #include "wfa_blk.hpp"
 #include "wfa_duo_cfg.hpp"
+#include "wfa_pk16.hpp"
 
 namespace wfa {
 
@@ -48,30 +49,33 @@ namespace wfa {
 struct DuoRed {
 #define WFA_DUO_3(opa, opb, opc)                                                                                    \
     unsigned long long sv;                                                                                          \
-    asm("s_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR1 "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_XOR1 "\n\t" opc      \
+    asm volatile("s_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR1 "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_XOR1 "\n\t" opc \
         " %2, %2, %2 " WFA_DPP_CTL_XOR1 "\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR2 "\n\t" opb " %1, %1, %1 "        \
         WFA_DPP_CTL_XOR2 "\n\t" opc " %2, %2, %2 " WFA_DPP_CTL_XOR2 "\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_HMIR "\n\t" \
         opb " %1, %1, %1 " WFA_DPP_CTL_HMIR "\n\t" opc " %2, %2, %2 " WFA_DPP_CTL_HMIR "\n\t"                         \
         "s_and_saveexec_b64 %3, %4\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_MIR "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_MIR    \
         "\n\t" opc " %2, %2, %2 " WFA_DPP_CTL_MIR "\n\ts_mov_b64 exec, %3"                                            \
         : "+v"(a), "+v"(b), "+v"(c), "=&s"(sv)                                                                      \
-        : "s"(wm));
+        : "s"(wm)                                                                                                   \
+        : "scc");
 #define WFA_DUO_2(opa, opb)                                                                                         \
     unsigned long long sv;                                                                                          \
-    asm("s_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR1 "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_XOR1 "\n\ts_nop 0\n\t" \
+    asm volatile("s_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR1 "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_XOR1 "\n\ts_nop 0\n\t" \
         opa " %0, %0, %0 " WFA_DPP_CTL_XOR2 "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_XOR2 "\n\ts_nop 0\n\t" opa        \
         " %0, %0, %0 " WFA_DPP_CTL_HMIR "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_HMIR "\n\t"                            \
         "s_and_saveexec_b64 %2, %3\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_MIR "\n\t" opb " %1, %1, %1 " WFA_DPP_CTL_MIR    \
         "\n\ts_mov_b64 exec, %2"                                                                                    \
         : "+v"(a), "+v"(b), "=&s"(sv)                                                                               \
-        : "s"(wm));
+        : "s"(wm)                                                                                                   \
+        : "scc");
 #define WFA_DUO_1(opa)                                                                                              \
     unsigned long long sv;                                                                                          \
-    asm("s_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR1 "\n\ts_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR2      \
+    asm volatile("s_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR1 "\n\ts_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_XOR2 \
         "\n\ts_nop 1\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_HMIR "\n\t"                                                \
         "s_and_saveexec_b64 %1, %2\n\ts_nop 0\n\t" opa " %0, %0, %0 " WFA_DPP_CTL_MIR "\n\ts_mov_b64 exec, %1"       \
         : "+v"(a), "=&s"(sv)                                                                                        \
-        : "s"(wm));
+        : "s"(wm)                                                                                                   \
+        : "scc");
     static WFA_DEV void min_max_min(int &a, int &b, int &c, unsigned long long wm) { WFA_DUO_3("v_min_i32_dpp", "v_max_i32_dpp", "v_min_i32_dpp") }
     static WFA_DEV void min_max(int &a, int &b, unsigned long long wm) { WFA_DUO_2("v_min_i32_dpp", "v_max_i32_dpp") }
     static WFA_DEV void max_add(int &a, int &b, unsigned long long wm) { WFA_DUO_2("v_max_i32_dpp", "v_add_u32_dpp") }
@@ -89,14 +93,15 @@ struct DuoRed {
 };
 
 // DX / DOE: the penalty shape, as in wfa_blk_kernel (R = max(DX, DOE) rows in the M ring)
-template <bool CENSUS, int DX = 2, int DOE = 4>
-#ifndef WFA_DUO_VGPRS
-#define WFA_DUO_VGPRS 64  // (the attribute counts register PAIRS on gfx90a and later: 64 = no cap below the 128 of four waves per SIMD; 60 = 120 VGPRs)
-#endif
-__global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(WFA_DUO_VGPRS))) void wfa_duo_kernel(const KParams P) {
+// PK: the rings as 16-bit pairs -- a lane's diagonals (p0, p1) in one register and (p2, p3) in another, the lower diagonal in the
+// low half -- and WF_NEXT's rejection-free path two diagonals per instruction (wide_next2()); wfa_duo_kernel runs this form.
+// PK = false (wfa_duo32_kernel) keeps one 32-bit register per diagonal: the reference the packed form is tested against, word for word.
+template <bool CENSUS, int DX, int DOE, bool PK>
+__device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) {
     constexpr int PP = 4;
     static_assert(DX >= 1 && DOE >= 1 && DX <= 4 && DOE <= 4, "ring depths of one to four score steps");
-    constexpr int R = DX > DOE ? DX : DOE;
+    constexpr int R  = DX > DOE ? DX : DOE;
+    constexpr int RW = PK ? 2 : PP;  // ring registers per row of a lane
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int  lane = threadIdx.x, l7 = lane & 7, l15 = lane & 15;
     const bool hi_half = (lane & 8) != 0;
@@ -109,6 +114,8 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
     const int       minwf    = (int)P.min_wf_len;
     const bool      adaptive = P.adaptive != 0;
     const uint32_t  seed_si  = P.dx;  // the mismatch seed M[x][0] belongs to step x/g
+    uint32_t        pk_one   = 0x00010001u;  // (1, 1) for wide_next2()
+    if constexpr (PK) asm volatile("" : "+s"(pk_one));
     const int       rows_cap = (int)(cap / 32);  // 16-bit words: a score's 64 diagonals are 32 words
 
     // ---- per-pair state (identical in the lanes of a pair)
@@ -123,17 +130,19 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
     const uint32_t *lq = lds + 4, *lt = lds + 4;
     uint32_t       *rowp = nullptr;
 
-    uint32_t M[R][PP], I[PP], D[PP];  // offsets, 0 = absent; M[i mod R] = row of step i
+    uint32_t M[R][RW], I[RW], D[RW];  // offsets, 0 = absent; M[i mod R] = row of step i (PK: two diagonals per register)
     int      rlo[R], rhi[R];          // band of each kept M row (absolute k); empty = (BIG, -BIG)
     int      lim[PP], lmx[PP];
 #pragma unroll
     for (int d = 0; d < R; d++) {
         rlo[d] = BK_BIG, rhi[d] = -BK_BIG;
 #pragma unroll
-        for (int p = 0; p < PP; p++) M[d][p] = 0u;
+        for (int p = 0; p < RW; p++) M[d][p] = 0u;
     }
 #pragma unroll
-    for (int p = 0; p < PP; p++) I[p] = D[p] = 0u, lim[p] = 0, lmx[p] = 0;
+    for (int p = 0; p < RW; p++) I[p] = D[p] = 0u;
+#pragma unroll
+    for (int p = 0; p < PP; p++) lim[p] = 0, lmx[p] = 0;
 
     // ---- wave-uniform state
     uint32_t buf_free  = (1u << NBUF) - 1u;      // sequence buffers nobody owns
@@ -178,10 +187,10 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
         for (int d = 0; d < R; d++) {
             rlo[d] = BK_BIG, rhi[d] = -BK_BIG;
 #pragma unroll
-            for (int p = 0; p < PP; p++) M[d][p] = 0u;
+            for (int p = 0; p < RW; p++) M[d][p] = 0u;
         }
 #pragma unroll
-        for (int p = 0; p < PP; p++) I[p] = D[p] = 0u;
+        for (int p = 0; p < RW; p++) I[p] = D[p] = 0u;
     };
     // OR over the wave of a value that is the same in the eight lanes of a half row
     const auto or_halves = [&](uint32_t v) {
@@ -302,18 +311,23 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
                 if (mine) {
                     // (record row r = the r-th oldest row of the ring, M[(ph + r) mod R]; a ring of fewer than four rows leaves the rest empty)
                     uint4 *const w = reinterpret_cast<uint4 *>(pr + 12 * l7);
-                    const auto pk = [](uint32_t lo, uint32_t hi) { return lo | (hi << 16); };
+                    // (PK: the rings are already the record's 16-bit pairs -- a plain copy)
+                    const auto pk  = [](uint32_t lo, uint32_t hi) { return lo | (hi << 16); };
+                    const auto pk2 = [&](const uint32_t(&v)[RW], int h) -> uint32_t {
+                        if constexpr (PK) return v[h];
+                        else return pk(v[2 * h], v[2 * h + 1]);
+                    };
                     uint32_t pw[8];
                     int      plo[4], phi[4];
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
-                        pw[2 * r]     = r < R ? pk(M[(ph + r) % R][0], M[(ph + r) % R][1]) : 0u;
-                        pw[2 * r + 1] = r < R ? pk(M[(ph + r) % R][2], M[(ph + r) % R][3]) : 0u;
+                        pw[2 * r]     = r < R ? pk2(M[(ph + r) % R], 0) : 0u;
+                        pw[2 * r + 1] = r < R ? pk2(M[(ph + r) % R], 1) : 0u;
                         plo[r] = r < R ? rlo[(ph + r) % R] : BK_BIG, phi[r] = r < R ? rhi[(ph + r) % R] : -BK_BIG;
                     }
                     w[0] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
                     if constexpr (R > 2) w[1] = make_uint4(pw[4], pw[5], pw[6], pw[7]);
-                    w[2] = make_uint4(pk(I[0], I[1]), pk(I[2], I[3]), pk(D[0], D[1]), pk(D[2], D[3]));
+                    w[2] = make_uint4(pk2(I, 0), pk2(I, 1), pk2(D, 0), pk2(D, 1));
                     if (l7 == 0) {
                         uint4 *const s4 = reinterpret_cast<uint4 *>(pr + 96);
                         s4[0] = make_uint4(pidx, si, cells, sbuf);
@@ -372,12 +386,12 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
 #pragma unroll
                 for (int d = 0; d < R; d++)
 #pragma unroll
-                    for (int p = 0; p < PP; p++) {
+                    for (int p = 0; p < RW; p++) {
                         const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, (int)M[d][p]);
                         M[d][p]          = src < 0 ? 0u : v;
                     }
 #pragma unroll
-                for (int p = 0; p < PP; p++) {
+                for (int p = 0; p < RW; p++) {
                     const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, (int)I[p]);
                     const uint32_t u = (uint32_t)__builtin_amdgcn_ds_bpermute(sl, (int)D[p]);
                     I[p] = src < 0 ? 0u : v, D[p] = src < 0 ? 0u : u;
@@ -429,12 +443,20 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
                         const uint32_t plo[4] = {a2.x, a2.y, a2.z, a2.w}, phi[4] = {a3.x, a3.y, a3.z, a3.w};
 #pragma unroll
                         for (int r = 0; r < R; r++) {
-                            M[(ph + r) % R][0] = pw[2 * r] & 0xFFFFu, M[(ph + r) % R][1] = pw[2 * r] >> 16;
-                            M[(ph + r) % R][2] = pw[2 * r + 1] & 0xFFFFu, M[(ph + r) % R][3] = pw[2 * r + 1] >> 16;
+                            if constexpr (PK) {
+                                M[(ph + r) % R][0] = pw[2 * r], M[(ph + r) % R][1] = pw[2 * r + 1];
+                            } else {
+                                M[(ph + r) % R][0] = pw[2 * r] & 0xFFFFu, M[(ph + r) % R][1] = pw[2 * r] >> 16;
+                                M[(ph + r) % R][2] = pw[2 * r + 1] & 0xFFFFu, M[(ph + r) % R][3] = pw[2 * r + 1] >> 16;
+                            }
                             rlo[(ph + r) % R] = (int)plo[r], rhi[(ph + r) % R] = (int)phi[r];
                         }
-                        I[0] = v2.x & 0xFFFFu, I[1] = v2.x >> 16, I[2] = v2.y & 0xFFFFu, I[3] = v2.y >> 16;
-                        D[0] = v2.z & 0xFFFFu, D[1] = v2.z >> 16, D[2] = v2.w & 0xFFFFu, D[3] = v2.w >> 16;
+                        if constexpr (PK) {
+                            I[0] = v2.x, I[1] = v2.y, D[0] = v2.z, D[1] = v2.w;
+                        } else {
+                            I[0] = v2.x & 0xFFFFu, I[1] = v2.x >> 16, I[2] = v2.y & 0xFFFFu, I[3] = v2.y >> 16;
+                            D[0] = v2.z & 0xFFFFu, D[1] = v2.z >> 16, D[2] = v2.w & 0xFFFFu, D[3] = v2.w >> 16;
+                        }
                         pidx = a0.x, si = a0.y, cells = a0.z, sbuf = a0.w;
                         n = (int)a1.x, m = (int)a1.y, kb = (int)a1.z, slow = (a1.w & 1u) != 0u, first_eq = (a1.w & 2u) != 0u;
                         st = 1, wide = false;
@@ -490,36 +512,28 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
         const unsigned long long wm = __ballot(wide);  // lanes of the 16-lane pairs (DuoRed's fourth stage)
         WFA_EVT(0, 1), WFA_EVT(6, __builtin_popcountll(__ballot(run)) / 8);
 
-        uint32_t(&Mo)[PP] = M[(ph + R - DOE) % R];  // M[s-o-e]
-        uint32_t(&Mx)[PP] = M[(ph + R - DX) % R];   // M[s-x]
-        uint32_t(&Mn)[PP] = M[ph];                  // the slot of the row being computed (the oldest row of the ring)
+        uint32_t(&Mo)[RW] = M[(ph + R - DOE) % R];  // M[s-o-e]
+        uint32_t(&Mx)[RW] = M[(ph + R - DX) % R];   // M[s-x]
+        uint32_t(&Mn)[RW] = M[ph];                  // the slot of the row being computed (the oldest row of the ring)
 
         // ------------------------------------------------------------ WF_NEXT (wfa.go:549-700)
-        uint32_t nM[PP], nI[PP], nD[PP], wd[PP], cc[PP];
-        const uint32_t a_edge = dn1(Mo[PP - 1]), b_edge = dn1(I[PP - 1]);
+        // (PK: nI, nD and wd as 16-bit pairs, nM as four 32-bit offsets -- WF_EXTEND, the termination test and the band read it per diagonal)
+        uint32_t nM[PP], nI[RW], nD[RW], wd[RW], cc[PP];
+        // (PK: the neighbours' registers hold two diagonals; k-1 of the lane's first diagonal is the high half of the lower lane's second
+        // register, k+1 of its last the low half of the upper lane's first)
+        const uint32_t a_edge = dn1(Mo[RW - 1]), b_edge = dn1(I[RW - 1]);
         const uint32_t c_edge = up1(Mo[0]), d_edge = up1(D[0]);
         const bool     slow_any = __ballot(run && slow) != 0ull;
-        if (__builtin_expect(!slow_any, 1)) {
-#pragma unroll
-            for (int p = 0; p < PP; p++) {
-                const uint32_t a = p ? Mo[p - 1] : a_edge, b = p ? I[p - 1] : b_edge;
-                const uint32_t c = p < PP - 1 ? Mo[p + 1] : c_edge, d = p < PP - 1 ? D[p + 1] : d_edge;
-                const uint32_t x = Mx[p];
-                const uint32_t mi = umax2(a, b), Isk = mi + (mi != 0u ? 1u : 0u);  // wfa.go:579-609
-                const uint32_t Dsk = umax2(c, d);                                   // wfa.go:614-645
-                const uint32_t x1  = x + (x != 0u ? 1u : 0u);
-                const uint32_t Msk = umax3(Isk, Dsk, x1);                           // wfa.go:655
-                nM[p] = Msk, nI[p] = Isk, nD[p] = Dsk;
-                wd[p] = blk_word_asm(Msk, a, b, c, d, x1, umax2(Isk, Dsk), Isk, Dsk);  // wfa.go:590-600,626-636,657-693
-                cc[p] = CENSUS ? (mi != 0u ? 1u : 0u) + (Dsk != 0u ? 1u : 0u) + (Msk != 0u ? 1u : 0u) : 0u;
-            }
-        } else {
+        // the path with rejections near a sequence end: 32-bit sources in, 32-bit cells out
+        const auto next_slow = [&](const uint32_t(&Mo4)[PP], const uint32_t(&I4)[PP], const uint32_t(&D4)[PP], const uint32_t(&Mx4)[PP],
+                                   uint32_t ae, uint32_t be, uint32_t ce, uint32_t de, uint32_t(&nI4)[PP], uint32_t(&nD4)[PP],
+                                   uint32_t(&wd4)[PP]) __attribute__((always_inline)) {
 #pragma unroll
             for (int p = 0; p < PP; p++) {
                 const int      k  = k0 + p;
-                const uint32_t a0 = p ? Mo[p - 1] : a_edge, b0 = p ? I[p - 1] : b_edge;
-                const uint32_t c0 = p < PP - 1 ? Mo[p + 1] : c_edge, d0 = p < PP - 1 ? D[p + 1] : d_edge;
-                const uint32_t x0 = Mx[p];
+                const uint32_t a0 = p ? Mo4[p - 1] : ae, b0 = p ? I4[p - 1] : be;
+                const uint32_t c0 = p < PP - 1 ? Mo4[p + 1] : ce, d0 = p < PP - 1 ? D4[p + 1] : de;
+                const uint32_t x0 = Mx4[p];
                 // rejections: > m (not >=) for I and X sources, offset - k > n for D and X sources
                 const uint32_t a = (int)a0 > m ? 0u : a0, b = (int)b0 > m ? 0u : b0;
                 const uint32_t c = (int)c0 - k > n ? 0u : c0, d = (int)d0 - k > n ? 0u : d0;
@@ -536,18 +550,73 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
                 const bool     iext = a < b, dext = c < d;
                 const uint32_t o0   = (fromI && iext) ? Iu : ((!fromX && !fromI && dext) ? Du : umax3(Iu, Du, Xu));
                 const bool     kin  = k >= -(n - 1) && k <= m - 1;  // wfa.go:562-563
-                nM[p] = kin ? Msk : 0u, nI[p] = kin ? Isk : 0u, nD[p] = kin ? Dsk : 0u;
-                wd[p] = blk_word(o0, iext, dext, fromX, fromI);
-                cc[p] = (CENSUS && kin) ? tI + tD + umin2(Msk, 1u) : 0u;
+                nM[p] = kin ? Msk : 0u, nI4[p] = kin ? Isk : 0u, nD4[p] = kin ? Dsk : 0u;
+                wd4[p] = blk_word(o0, iext, dext, fromX, fromI);
+                cc[p]  = (CENSUS && kin) ? tI + tD + umin2(Msk, 1u) : 0u;
             }
+        };
+        if constexpr (PK) {
+            if (__builtin_expect(!slow_any, 1)) {
+                // the sources of diagonals (p0, p1) and (p2, p3): k-1 of the M[s-o-e] / I rows, k+1 of the M[s-o-e] / D rows
+                const uint32_t a0 = __builtin_amdgcn_alignbit(Mo[0], a_edge, 16), a1 = __builtin_amdgcn_alignbit(Mo[1], Mo[0], 16);
+                const uint32_t c1 = __builtin_amdgcn_alignbit(c_edge, Mo[1], 16);
+                const uint32_t b0 = __builtin_amdgcn_alignbit(I[0], b_edge, 16), b1 = __builtin_amdgcn_alignbit(I[1], I[0], 16);
+                const uint32_t d0 = __builtin_amdgcn_alignbit(D[1], D[0], 16), d1 = __builtin_amdgcn_alignbit(d_edge, D[1], 16);
+                uint32_t M2[2];
+                wide_next2<true>(wide_pk(a0), wide_pk(b0), wide_pk(a1) /* = (M[k0+1], M[k0+2]) */, wide_pk(d0), wide_pk(Mx[0]), wide_pk(pk_one),
+                                  M2[0], nI[0], nD[0], wd[0]);
+                wide_next2<true>(wide_pk(a1), wide_pk(b1), wide_pk(c1), wide_pk(d1), wide_pk(Mx[1]), wide_pk(pk_one), M2[1], nI[1], nD[1], wd[1]);
+#pragma unroll
+                for (int p = 0; p < PP; p++) {
+                    const int sh = 16 * (p & 1);
+                    nM[p] = (M2[p >> 1] >> sh) & 0xFFFFu;
+                    // (an I or D cell exists iff its mi or Dsk source does; Isk = mi + 1)
+                    cc[p] = CENSUS ? (((nI[p >> 1] >> sh) & 0xFFFFu) != 0u ? 1u : 0u) + (((nD[p >> 1] >> sh) & 0xFFFFu) != 0u ? 1u : 0u) +
+                                         (nM[p] != 0u ? 1u : 0u)
+                                   : 0u;
+                }
+            } else {
+                uint32_t Mo4[PP], I4[PP], D4[PP], Mx4[PP], nI4[PP], nD4[PP], wd4[PP];
+#pragma unroll
+                for (int p = 0; p < PP; p++) {
+                    const int sh = 16 * (p & 1);
+                    Mo4[p] = (Mo[p >> 1] >> sh) & 0xFFFFu, I4[p] = (I[p >> 1] >> sh) & 0xFFFFu;
+                    D4[p] = (D[p >> 1] >> sh) & 0xFFFFu, Mx4[p] = (Mx[p >> 1] >> sh) & 0xFFFFu;
+                }
+                next_slow(Mo4, I4, D4, Mx4, a_edge >> 16, b_edge >> 16, c_edge & 0xFFFFu, d_edge & 0xFFFFu, nI4, nD4, wd4);
+#pragma unroll
+                for (int h = 0; h < 2; h++)
+                    nI[h] = nI4[2 * h] | (nI4[2 * h + 1] << 16), nD[h] = nD4[2 * h] | (nD4[2 * h + 1] << 16),
+                    wd[h] = wd4[2 * h] | (wd4[2 * h + 1] << 16);
+            }
+        } else if (__builtin_expect(!slow_any, 1)) {
+#pragma unroll
+            for (int p = 0; p < PP; p++) {
+                const uint32_t a = p ? Mo[p - 1] : a_edge, b = p ? I[p - 1] : b_edge;
+                const uint32_t c = p < PP - 1 ? Mo[p + 1] : c_edge, d = p < PP - 1 ? D[p + 1] : d_edge;
+                const uint32_t x = Mx[p];
+                const uint32_t mi = umax2(a, b), Isk = mi + (mi != 0u ? 1u : 0u);  // wfa.go:579-609
+                const uint32_t Dsk = umax2(c, d);                                   // wfa.go:614-645
+                const uint32_t x1  = x + (x != 0u ? 1u : 0u);
+                const uint32_t Msk = umax3(Isk, Dsk, x1);                           // wfa.go:655
+                nM[p] = Msk, nI[p] = Isk, nD[p] = Dsk;
+                wd[p] = blk_word_asm(Msk, a, b, c, d, x1, umax2(Isk, Dsk), Isk, Dsk);  // wfa.go:590-600,626-636,657-693
+                cc[p] = CENSUS ? (mi != 0u ? 1u : 0u) + (Dsk != 0u ? 1u : 0u) + (Msk != 0u ? 1u : 0u) : 0u;
+            }
+        } else {
+            next_slow(Mo, I, D, Mx, a_edge, b_edge, c_edge, d_edge, nI, nD, wd);
         }
         // seeds of initComponents (wfa.go:155-160): M[0][0] = 1/Match or M[x][0] = 1/Mismatch
         if (__builtin_expect(__ballot(run && si <= seed_si) != 0ull, 0)) {  // (ONE compare on the step's path; `want` below is the exact test)
             const bool want = run && ((si == 0u && first_eq) || (si == seed_si && !first_eq));
 #pragma unroll
             for (int p = 0; p < PP; p++)
-                if (want && k0 + p == 0 && nM[p] == 0u)
-                    nM[p] = 1u, wd[p] = first_eq ? BLK_SEED_MATCH : BLK_SEED_MISMATCH, cc[p] = CENSUS ? 1u : 0u;
+                if (want && k0 + p == 0 && nM[p] == 0u) {
+                    const uint32_t sw = first_eq ? BLK_SEED_MATCH : BLK_SEED_MISMATCH;
+                    nM[p] = 1u, cc[p] = CENSUS ? 1u : 0u;
+                    if constexpr (PK) wd[p >> 1] = (p & 1) ? (wd[p >> 1] & 0xFFFFu) | (sw << 16) : (wd[p >> 1] & 0xFFFF0000u) | sw;
+                    else wd[p] = sw;
+                }
         }
         // ------------------------------------------------------------ store the row's words (CompactView fmt 7)
         // 16-bit words -- a pre-extension offset below 4 096 and the four decisions: this kernel's reads are under 2 048
@@ -562,8 +631,10 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
             for (int p = 0; p < PP; p++) anyc |= nM[p];
             // (fmt 10: score index si -> word (si & ~7) * 4 + (si & 7) * 2 = 2 (si + (si & ~7)) behind the lane's base)
             const uint32_t row_off = DUO_ARENA_FMT == 10u ? 2u * (si + (si & ~7u)) : DUO_ARENA_FMT == 9u ? 0u : (((uint32_t)k0 & 60u) << 2);
-            if (run && !no_room && anyc != 0u)
-                *reinterpret_cast<uint2 *>(rowp + row_off) = make_uint2(wd[0] | (wd[1] << 16), wd[2] | (wd[3] << 16));
+            if (run && !no_room && anyc != 0u) {
+                if constexpr (PK) *reinterpret_cast<uint2 *>(rowp + row_off) = make_uint2(wd[0], wd[1]);
+                else *reinterpret_cast<uint2 *>(rowp + row_off) = make_uint2(wd[0] | (wd[1] << 16), wd[2] | (wd[3] << 16));
+            }
         }
         WFA_STAMP(2);  // next + store
 
@@ -652,7 +723,8 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
             for (int p = 0; p < PP; p++) {  // Delete of wfa.go:526-535: the words never exist
                 const int  ix   = PP * j + p;
                 const bool keep = ix >= ilo && ix <= ihi;
-                nM[p] = keep ? nM[p] : 0u, nI[p] = keep ? nI[p] : 0u, nD[p] = keep ? nD[p] : 0u;
+                nM[p] = keep ? nM[p] : 0u;
+                if constexpr (!PK) nI[p] = keep ? nI[p] : 0u, nD[p] = keep ? nD[p] : 0u;  // (PK: at the ring's entry)
                 csum += keep ? cc[p] : 0u;
             }
         } else {
@@ -700,7 +772,8 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
                     for (int p = 0; p < PP; p++) {
                         const int  ix   = PP * j + p;
                         const bool keep = ix >= ilo && ix <= ihi;
-                        nM[p] = keep ? nM[p] : 0u, nI[p] = keep ? nI[p] : 0u, nD[p] = keep ? nD[p] : 0u;
+                        nM[p] = keep ? nM[p] : 0u;
+                        if constexpr (!PK) nI[p] = keep ? nI[p] : 0u, nD[p] = keep ? nD[p] : 0u;
                         csum += keep ? cc[p] : 0u;
                     }
                 }
@@ -719,8 +792,19 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
         if constexpr (DUO_ARENA_FMT == 7u) rowp += (((uint32_t)(uintptr_t)rowp & 0x38u) == 0u) ? 240 : 0;  // past the tile's 8th score: next tile
 
         // ------------------------------------------------------------ the new row enters the rings
+        if constexpr (PK) {
+            // (every offset below 4 096.  An I or D cell outside the kept band needs no select: nM >= Msk >= Isk, Dsk in a cell that
+            // exists, and the band's Delete sets nM to 0 -- the minimum with the kept M offset keeps I and D exactly where M is kept)
 #pragma unroll
-        for (int p = 0; p < PP; p++) Mn[p] = nM[p], I[p] = nI[p], D[p] = nD[p];
+            for (int h = 0; h < 2; h++) {
+                Mn[h] = nM[2 * h] | (nM[2 * h + 1] << 16);
+                I[h]  = wide_u32(__builtin_elementwise_min(wide_pk(nI[h]), wide_pk(Mn[h])));
+                D[h]  = wide_u32(__builtin_elementwise_min(wide_pk(nD[h]), wide_pk(Mn[h])));
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < PP; p++) Mn[p] = nM[p], I[p] = nI[p], D[p] = nD[p];
+        }
         rlo[ph] = keepl ? kb + ilo : BK_BIG;
         rhi[ph] = keepl ? kb + ihi : -BK_BIG;
 
@@ -731,7 +815,7 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
             int hf   = 0;  // extended offset of the end cell M[s][Ak]: where the backtrace starts
 #pragma unroll
             for (int p = 0; p < PP; p++)
-                if (k0 + p == m - n) hf = (int)Mn[p];
+                if (k0 + p == m - n) hf = (int)nM[p];  // (= the ring's new row)
             hf = DuoRed::max1(hf, wm);
             if (fin && j == 0) {
                 if (no_room) {
@@ -774,6 +858,22 @@ __global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(W
         for (int i = 0; i < 8; i++) atomicAdd(acc + 8 + i, evt[i]);
     }
 #endif
+}
+
+#ifndef WFA_DUO_VGPRS
+#define WFA_DUO_VGPRS 64  // (the attribute counts register PAIRS on gfx90a and later: 64 = no cap below the 128 of four waves per SIMD; 60 = 120 VGPRs)
+#endif
+// The offsets of a pair fit 16 bits: wfa_duo_kernel only takes pairs whose prepacked slot fits 256 words (4 header words + 2 x 126 words
+// of 16 bases), so its reads are under 2 048 bases and every offset under 4 096 -- the 12 bits blk_word() gives it in a halfword.
+static_assert(16u * (256u - 4u) / 2u < 2048u, "wfa_duo_kernel's packed rings need offsets under 4 096");
+template <bool CENSUS, int DX = 2, int DOE = 4>
+__global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(WFA_DUO_VGPRS))) void wfa_duo_kernel(const KParams P) {
+    duo_run<CENSUS, DX, DOE, true>(P);
+}
+// the 32-bit rings: the reference of the packed kernel (debug option duo_pk = 0)
+template <bool CENSUS, int DX = 2, int DOE = 4>
+__global__ __launch_bounds__(64, WFA_DUO_WAVES) __attribute__((amdgpu_num_vgpr(WFA_DUO_VGPRS))) void wfa_duo32_kernel(const KParams P) {
+    duo_run<CENSUS, DX, DOE, false>(P);
 }
 
 }  // namespace wfa

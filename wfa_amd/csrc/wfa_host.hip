@@ -459,6 +459,8 @@ static int set_option_impl(wfahip_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_wide_waves = (value == 1 || value == 4) ? (int)value : 0;
     else if (k == "duo")
         ctx->opt_duo = value;
+    else if (k == "duo_pk")
+        ctx->opt_duo_pk = value != 0;
     else if (k == "duo_min_pairs")
         ctx->opt_duo_min_pairs = value;
     else if (k == "compact_call_bases")
@@ -959,7 +961,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 if (ctx->opt_arena_poison) HIP_TRY(hipMemsetAsync(P.arena, 0xA5, (size_t)(words * 4ull * cn), st));
                 HIP_TRY(hipEventRecord(evFa, st));
                 if (kind == 8) {
-                    HIP_TRY(wfa_launch_duo(shape, P, grid, lds_bytes, st, P.census != 0));
+                    HIP_TRY(wfa_launch_duo(shape, P, grid, lds_bytes, st, P.census != 0, ctx->opt_duo_pk));
                 } else if (kind >= 3) {
                     uint32_t fl = (P.census ? (uint32_t)FWD_CENSUS : 0u) | (P.adaptive ? (uint32_t)FWD_ADAPTIVE : 0u);
                     if (kind == 3 && stream_bt) fl |= FWD_STREAM;

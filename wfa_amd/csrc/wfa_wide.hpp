@@ -31,6 +31,7 @@
 // What the workgroup cannot hold (an arena that overflows) is handed to the generic ladder like every sub-wave kernel does.
 #pragma once
 #include "wfa_device.hpp"
+#include "wfa_pk16.hpp"  // wide_next2() and the packed helpers
 
 namespace wfa {
 
@@ -57,26 +58,6 @@ constexpr uint32_t WIDE_CKPT_HDR = 24u, WIDE_CKPT_WORDS = WIDE_CKPT_HDR + 6u * W
 __host__ __device__ inline uint32_t wide_lds_words_narrow(uint32_t seq_words) { return ((2u * seq_words + 3u) & ~3u) + 6u * WIDE_RW / 2u + WIDE_SCR_WORDS; }
 
 // DX / DOE: the penalty shape x/g : (o+e)/g (e/g == 1), as in the sub-wave kernels (wfa_fwd.hpp)
-// Two 16-bit offsets per register (the wide rows' interior: v_pk_max_u16 / v_pk_add_u16 / v_pk_sub_u16 with clamp / v_pk_min_u16)
-typedef unsigned short wide_us2 __attribute__((ext_vector_type(2)));
-WFA_DEV wide_us2 wide_pk(uint32_t x) { return __builtin_bit_cast(wide_us2, x); }
-WFA_DEV uint32_t wide_u32(wide_us2 x) { return __builtin_bit_cast(uint32_t, x); }
-WFA_DEV wide_us2 wide_max(wide_us2 a, wide_us2 b) { return __builtin_elementwise_max(a, b); }
-// (`one` = (1, 1) from a register the compiler cannot see through: it turns min(a, 1) into two compares, two selects and a permute otherwise)
-WFA_DEV wide_us2 wide_ind(wide_us2 a, wide_us2 one) { return __builtin_elementwise_min(a, one); }                             // 1 where a != 0
-WFA_DEV wide_us2 wide_lt(wide_us2 a, wide_us2 b, wide_us2 one) { return wide_ind(__builtin_elementwise_sub_sat(b, a), one); }  // 1 where a < b
-// WF_NEXT of two neighbouring diagonals whose sources need no rejection (wfa.go:572-699; the decisions as blk_word_asm() takes them: the mismatch
-// wins iff x1 >= max(Isk, Dsk), else the insertion iff Isk >= Dsk; backTrace's recomputed pre-extension offset is the M offset itself)
-WFA_DEV void wide_next2(wide_us2 a, wide_us2 b, wide_us2 c, wide_us2 d, wide_us2 x, wide_us2 one, uint32_t &M2, uint32_t &I2, uint32_t &D2, uint32_t &W2) {
-    const wide_us2 mi = wide_max(a, b), Isk = mi + wide_ind(mi, one), Dsk = wide_max(c, d), x1 = x + wide_ind(x, one);
-    const wide_us2 t = wide_max(Isk, Dsk), Msk = wide_max(t, x1);
-    const wide_us2 iext = wide_lt(a, b, one), dext = wide_lt(c, d, one), fx = one - wide_lt(x1, t, one), fi = one - wide_lt(Isk, Dsk, one);
-    wide_us2 w = Msk + Msk + iext;
-    w = w + w + dext, w = w + w + fx, w = w + w + fi;
-    w &= (wide_us2)(0) - wide_ind(Msk, one);  // (no cell: no word)
-    M2 = wide_u32(Msk), I2 = wide_u32(Isk), D2 = wide_u32(Dsk), W2 = wide_u32(w);
-}
-
 #ifndef WFA_WIDE_EU
 #define WFA_WIDE_EU 5  // waves per SIMD the register allocation aims at (0: the compiler's choice -- 110 registers with the packed path: four waves, 8 % slower on g3)
 #endif
