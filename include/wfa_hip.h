@@ -126,7 +126,8 @@ typedef struct {
                                   18 = wfa_wide_kernel (round 6: semi-global reads up to 2 047 bases, a workgroup per pair with the rows in 16-bit LDS rings),
                                   17 = wfa_teamc_kernel (wide wavefronts: a team of workgroups per pair, one backtrace word per diagonal),
                                   19 = wfa_score_kernel (wfahip_score_batch, global pairs), 20 = wfa_wide_kernel<.., SCORE> (wfahip_score_batch,
-                                  semi-global pairs) */
+                                  semi-global pairs), 21 = wfa_score_kernel<MATRIX> (wfahip_score_matrix, global alignment),
+                                  22 = wfa_wide_kernel<.., SCORE, MATRIX> (wfahip_score_matrix, semi-global alignment) */
     uint32_t ladder_start_level; /* arena level the long-pair ladder of this call started on (0 unless a learned hint applied) */
 } wfahip_timing;
 
@@ -181,6 +182,30 @@ int  wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *
                         const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
                         uint64_t n_pairs, uint32_t max_score, wfahip_scores *out);
 void wfahip_scores_free(wfahip_scores *s);
+
+/* Score matrix: every query against every target, score only.  Query i is seq_blob[q_off[i] .. +q_len[i]), target j is
+ * seq_blob[t_off[j] .. +t_len[j]); queries and targets may share sequences or be the same arrays (all against all).  Cell (i, j)
+ * is written to status[i * out_stride + j] and score[i * out_stride + j] (out_stride 0 = n_t) and equals what wfahip_score_batch
+ * returns for the pair (query i, target j) under the same p and max_score -- status, score and WFAHIP_PAIR_OVER_MAX alike, global
+ * or semi-global, with wf-adaptive on or off, any penalties, any bytes.  The full rectangle is computed: under wf-adaptive
+ * score(q, t) need not equal score(t, q).  Elements outside the n_q x n_t window of a strided output are never written, so a
+ * caller may fill one tile of a larger matrix per call (or per GPU).  The outputs are the caller's; nothing is allocated that
+ * the caller must free.  Whole-call errors, checked before any device work: WFAHIP_ERR_BAD_ARG for a null ctx, p, status or
+ * score, a null offset or length array whose count is non-zero, a non-empty sequence within WFAHIP_MAX_SEQ_LEN that lies
+ * outside the blob, 0 < out_stride < n_t, or (n_q - 1) * stride + n_t beyond 64 bits; then the params as wfahip_align_batch
+ * checks them.  n_q == 0 or n_t == 0 returns WFAHIP_OK and touches nothing.
+ * Each of the n_q + n_t sequences is 2-bit packed and checked once, and uploaded once (a quarter of its bytes); the cells run in
+ * rectangular tiles on the matrix instances of the score kernels, global alignments on wfa_score_kernel, semi-global ones on
+ * wfa_wide_kernel, each cell staging its two sequences from that table.  A tile's results download while the next tile runs.
+ * The cells the score kernels cannot take -- a sequence with a byte outside ACGT or longer than 2 047 bases, a band wider than
+ * wfa_score_kernel's 248 diagonals, every cell of a penalty shape without an instance -- are aligned by the full path of
+ * wfahip_align_batch in batches of bounded size, and only their score kept.  wfahip_last_timing: main_kernel_kind 21 (global) or
+ * 22 (semi-global) unless every cell took the full path, n_retried_pairs = cells that took the full path (saturating at
+ * UINT32_MAX), arena_bytes = 0 unless some did. */
+int  wfahip_score_matrix(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
+                         const uint64_t *q_off, const uint32_t *q_len, uint64_t n_q,
+                         const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t,
+                         uint32_t max_score, int32_t *status, uint32_t *score, uint64_t out_stride);
 
 /* Device-resident variant: every pointer is a device address on the context's GPU (caller-owned).
  * d_rec receives n_pairs records of WFAHIP_REC_WORDS u32; d_ops receives the CIGAR ops
@@ -295,6 +320,8 @@ int  wfahip_last_timing(const wfahip_ctx *ctx, wfahip_timing *out);
  *                          rows in 16-bit LDS rings of any width; two launches per chunk under wf-adaptive -- wide rows, then
  *                          the narrow tail from a checkpoint); 3: one launch per chunk; 0: on the generic ladder     default 1
  *   "wide_waves"  0|1|4    waves per pair in its first launch: 0 = by the rings' size (four above 12 KB)          default 0
+ *   "matrix_tile_cells"    wfahip_score_matrix: cells per tile (0 = automatic: 4 194 304 global, 262 144 semi-global; tests force
+ *                          small tiles so that the tiles split rows and columns)                                default 0
  *   "arena_bytes_per_slot", "slots", "threads_per_pair"   generic kernel (one workgroup per pair)
  *   "prepack"  0|1         the sequences of a chunk are 2-bit packed by a kernel of their own before the 16-lane forward
  *                          kernel, whose refill then is one round of loads (forward pass -2 %, packing kernel +4 %)   default 0

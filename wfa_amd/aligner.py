@@ -320,6 +320,66 @@ class Aligner:
             raise WfaError("pair could not be aligned (out of device memory)")
         return int(sc[0])
 
+    # -- new: score matrix (include/wfa_hip.h: wfahip_score_matrix) ------------------------------------
+    def score_matrix_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, out=None):
+        """(status: np.int32[n_q, n_t], score: np.uint32[n_q, n_t]) of every query against every target: cell (i, j) is what
+        score_arrays gives for the pair (query i, target j).  Pass the same arrays as queries and targets for all against all.
+        out: an optional pair of preallocated C-contiguous arrays of shape (n_q, n_t) -- or row-strided views of that shape into
+        larger ones (one row stride for both); nothing outside the window is written.  Returns the arrays written."""
+        same = q_off is t_off and q_len is t_len  # (all against all: the entry packs and uploads each sequence once)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+        if same:
+            t_off, t_len = q_off, q_len
+        n_q, n_t = int(len(q_len)), int(len(t_len))
+        if len(q_off) != n_q or len(t_off) != n_t:
+            raise ValueError("offset and length arrays differ in length")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        if out is None:
+            status, score = np.zeros((n_q, n_t), np.int32), np.zeros((n_q, n_t), np.uint32)
+            stride = n_t
+        else:
+            try:
+                status, score = out
+            except (TypeError, ValueError):
+                raise ValueError("out must be a pair (status, score) of arrays") from None
+            if not (isinstance(status, np.ndarray) and isinstance(score, np.ndarray)):
+                raise ValueError("out must be a pair (status, score) of arrays")
+            if status.dtype != np.int32 or score.dtype != np.uint32:
+                raise ValueError("out arrays must be int32 (status) and uint32 (score)")
+            if status.shape != (n_q, n_t) or score.shape != (n_q, n_t):
+                raise ValueError(f"out arrays must have shape ({n_q}, {n_t})")
+            if not (status.flags.writeable and score.flags.writeable):
+                raise ValueError("out arrays must be writeable")
+            rows = [a.strides[0] for a in (status, score)] if n_q > 1 else [4 * n_t, 4 * n_t]
+            if n_t > 1 and (status.strides[1] != 4 or score.strides[1] != 4):
+                raise ValueError("out arrays must be contiguous within a row")
+            if rows[0] != rows[1] or rows[0] % 4 or rows[0] < 4 * n_t:
+                raise ValueError("out arrays must share one row stride of at least n_t elements")
+            stride = rows[0] // 4
+        if n_q == 0 or n_t == 0:
+            return status, score
+        prm = self._params()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = L.lib().wfahip_score_matrix(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), n_q, vp(t_off), vp(t_len), n_t,
+                                         int(max_score), vp(status), vp(score), stride)
+        L.check(rc, "wfahip_score_matrix" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return status, score
+
+    def ScoreMatrix(self, qs: Sequence[bytes], ts: Optional[Sequence[bytes]] = None, max_score: int = 0):
+        """(status, score) arrays of shape (len(qs), len(ts)): every query against every target (see score_matrix_arrays).
+        ts=None: all against all (qs against qs; each sequence is uploaded once)."""
+        seqs = list(qs) if ts is None else list(qs) + list(ts)
+        blob, off, ln, _, _ = make_blob(seqs, [b""] * len(seqs))
+        n_q = len(qs)
+        if ts is None:
+            return self.score_matrix_arrays(blob, off, ln, off, ln, max_score=max_score)
+        return self.score_matrix_arrays(blob, off[:n_q], ln[:n_q], off[n_q:], ln[n_q:], max_score=max_score)
+
     # -- new: one pair at a time behind the batch ----------------------------------------------------
     def Submit(self, q: bytes, t: bytes) -> int:
         """Hand in one pair (copied) and return its ticket; Collect() aligns everything submitted as ONE batch.  This is

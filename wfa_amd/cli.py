@@ -8,6 +8,7 @@ the alignments computed by the HIP path -- all pairs of the file in ONE batch ca
 Options:  -g  do not use global alignment          -a  do not use adaptive reduction
           -N  do not output alignment (benchmark)  -t  only show the aligned region
           -s  score only: print "align-score : N" per pair (no alignment is computed)
+          -S  score matrix: every query against every target, one line of tab-separated scores per query
 """
 from __future__ import annotations
 
@@ -56,6 +57,8 @@ def main(argv=None) -> int:
     ap.add_argument("-N", dest="no_output", action="store_true", help="do not output alignment (for benchmark)")
     ap.add_argument("-t", dest="trim", action="store_true", help="only show the aligned region")
     ap.add_argument("-s", dest="score_only", action="store_true", help="score only: print the alignment score of each pair")
+    ap.add_argument("-S", dest="score_matrix", action="store_true",
+                    help="score matrix: every query against every target, one line of tab-separated scores per query")
     ap.add_argument("seqs", nargs="*")
     args = ap.parse_args(argv)
 
@@ -75,14 +78,28 @@ def main(argv=None) -> int:
     algn = wfa.New(wfa.DefaultPenalties, wfa.Options(GlobalAlignment=not args.no_global))  # wfa-go.go:96-98
     if not args.no_adaptive:
         algn.AdaptiveReduction(wfa.AdaptiveReductionOption(10, 50, 1))  # wfa-go.go:100-106
+
+    def pair_error(st) -> str:
+        return (wfa.ErrEmptySeq if st == wfa._lib.PAIR_EMPTY else wfa.ErrSeqTooLong if st == wfa._lib.PAIR_TOO_LONG
+                else "pair could not be aligned (out of device memory)")
+
     try:
+        if args.score_matrix:  # wfahip_score_matrix: every query line against every target line
+            status, scores = algn.ScoreMatrix([p[0] for p in pairs], [p[1] for p in pairs])
+            bad = status != wfa._lib.PAIR_OK
+            if bad.any():
+                print(pair_error(int(status[bad][0])), file=sys.stderr)
+                return 1
+            if not args.no_output:
+                sys.stdout.write("".join("\t".join(str(int(v)) for v in row) + "\n" for row in scores))
+            sys.stdout.flush()
+            return 0
         if args.score_only:  # wfahip_score_batch: the forward pass alone
             status, scores = algn.ScoreBatch([p[0] for p in pairs], [p[1] for p in pairs])
             out = sys.stdout
             for st, sc in zip(status, scores):
                 if st != wfa._lib.PAIR_OK:
-                    print(wfa.ErrEmptySeq if st == wfa._lib.PAIR_EMPTY else wfa.ErrSeqTooLong if st == wfa._lib.PAIR_TOO_LONG
-                          else "pair could not be aligned (out of device memory)", file=sys.stderr)
+                    print(pair_error(st), file=sys.stderr)
                     return 1
                 if not args.no_output:
                     out.write(f"align-score : {int(sc)}\n")

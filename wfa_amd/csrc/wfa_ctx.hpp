@@ -173,6 +173,12 @@ struct wfahip_ctx {
     int64_t       opt_narrow_long          = 0;   // experiment: reads of any length start on the 8-lanes-per-pair instance (32-diagonal windows)
     DevBuf        score_out;                      // wfahip_score_batch: {status, score} per pair
     DevBuf        wide_ckpt;                      // wfa_wide_kernel: what its first launch hands its second, per pair of the chunk
+    DevBuf        mx_seq, mx_words;               // wfahip_score_matrix: the call's sequence table (wfa_matrix.hpp)
+    DevBuf        mx_out;                         // ... {status, score} of two tiles (double-buffered: tile c downloads while tile c + 1 runs)
+    uint2        *mx_pin       = nullptr;         // ... their page-locked host copies
+    size_t        mx_pin_bytes = 0;
+    hipEvent_t    mx_ev[4]     = {};              // ... per buffer: its kernels are done, its download is done
+    int64_t       opt_matrix_tile_cells    = 0;   // ... cells per tile (0 = automatic; tests force small tiles to cross tile edges)
     int64_t       opt_wide                 = 1;   // semi-global batches of reads up to 2 047 bases (penalties of one of the sub-wave shapes) start on wfa_wide_kernel (round 6: a workgroup per
                                                   // pair, the rows in 16-bit LDS rings of any width, two launches per chunk under wf-adaptive); 3: one launch per chunk, every pair
                                                   // runs to its end in the wide rings; 0: on the generic ladder

@@ -963,6 +963,220 @@ extern "C" int wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const
     WFAHIP_GUARD(score_batch_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, max_score, out))
 }
 
+// ---- score matrix (wfahip_score_matrix): every query against every target, score only.  The n_q + n_t sequences are packed and
+// flagged once (host threads, pack_seq_fast) and uploaded as one table of 2-bit words; the matrix instances of the score kernels
+// take the cells of a rectangular tile, a workgroup per cell, and stage the cell's two sequences from the table.  Tiles are
+// double-buffered: tile c downloads on stream2 while tile c + 1 runs, and the host scatters it into the caller's arrays.  What the
+// kernels hand back goes through the full path of wfahip_align_batch, in batches of MX_FB_PAIRS cells.
+namespace wfa {
+hipError_t wfa_launch_score_matrix(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_wide_score_matrix(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+}  // namespace wfa
+
+namespace {
+constexpr uint64_t MX_TILE_GLOBAL = 1ull << 22;  // cells per tile of wfa_score_kernel<true>: 32 MB of {status, score}
+constexpr uint64_t MX_CKPT_BYTES  = 1ull << 30;  // the wide kernel's checkpoints of one tile (WIDE_CKPT_WORDS words per cell in flight)
+constexpr uint64_t MX_FB_PAIRS    = 1ull << 16;  // cells per call of the full path
+}  // namespace
+
+static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                             const uint32_t *q_len, uint64_t n_q, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t, uint32_t max_score,
+                             int32_t *status, uint32_t *score, uint64_t out_stride) {
+    // (every check before any device work, and none dereferences ctx)
+    if (!ctx || !p || !status || !score) return WFAHIP_ERR_BAD_ARG;
+    if ((n_q && (!q_off || !q_len)) || (n_t && (!t_off || !t_len)) || (!seq_blob && blob_bytes)) return WFAHIP_ERR_BAD_ARG;
+    const auto outside = [&](const uint64_t *off, const uint32_t *len, uint64_t n) {  // align_batch_impl's rule, per sequence
+        for (uint64_t i = 0; i < n; i++)
+            if (len[i] && len[i] <= WFAHIP_MAX_SEQ_LEN && (off[i] > blob_bytes || len[i] > blob_bytes - off[i])) return true;
+        return false;
+    };
+    if (outside(q_off, q_len, n_q) || outside(t_off, t_len, n_t)) return WFAHIP_ERR_BAD_ARG;
+    const uint64_t stride = out_stride ? out_stride : n_t;
+    if (out_stride && out_stride < n_t) return WFAHIP_ERR_BAD_ARG;
+    if (n_q > 1 && stride && n_q - 1 > (UINT64_MAX - n_t) / stride) return WFAHIP_ERR_BAD_ARG;  // (n_q - 1) * stride + n_t overflows
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_q == 0 || n_t == 0) return WFAHIP_OK;
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    const auto    t_start = std::chrono::steady_clock::now();
+    wfahip_timing tm{};
+    const auto    put = [&](uint64_t i, uint64_t j, uint32_t st, uint32_t sc) {
+        status[i * stride + j] = (int32_t)st, score[i * stride + j] = st == ST_OK ? sc : 0u;
+    };
+    KParams P{};
+    P.x = p->mismatch, P.o = p->gap_open, P.e = p->gap_ext, P.oe = p->gap_open + p->gap_ext;
+    P.g = gcd_u32(gcd_u32(P.x, P.oe), P.e);
+    P.global_alignment = p->global_alignment ? 1u : 0u, P.adaptive = p->adaptive ? 1u : 0u;
+    P.min_wf_len = p->min_wf_len, P.max_dist_diff = p->max_dist_diff;
+    const uint32_t dx = P.x / P.g, doe = P.oe / P.g, de = P.e / P.g;
+    const bool     glob      = P.global_alignment != 0u;
+    const int      shape     = fwd_shape(dx, doe, de);
+    const bool     on_kernel = glob ? score_shape_ok(dx, doe, de) : shape >= 0;
+    std::vector<uint64_t> fb;  // cells (i * n_t + j) the kernels handed back
+    if (on_kernel) {
+        hipStream_t st = ctx->stream, st_dn = ctx->stream2;
+        // ---- the sequence table: queries, then targets (none when they are the queries)
+        const bool     same  = q_off == t_off && q_len == t_len && n_q == n_t;
+        const uint64_t n_seq = same ? n_q : n_q + n_t;
+        const uint32_t kmax  = glob ? SCORE_MAX_LEN : WIDE_MAX_LEN;
+        std::vector<uint4> seq(n_seq);
+        uint64_t           pos = 0;
+        uint32_t           L   = 1;
+        for (uint64_t s = 0; s < n_seq; s++) {
+            const uint32_t len  = s < n_q ? q_len[s] : t_len[s - n_q];
+            const uint32_t flag = len == 0 ? MXF_EMPTY : len > WFAHIP_MAX_SEQ_LEN ? MXF_TOO_LONG : len > kmax ? MXF_LONG : 0u;
+            seq[s] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), len, flag);
+            if (flag == 0u) pos += wfahip_packed_words(len), L = std::max(L, len);
+        }
+        std::vector<uint32_t> words(pos + 4);
+        {
+            const auto range = [&](uint64_t a, uint64_t b) {
+                for (uint64_t s = a; s < b; s++) {
+                    if (seq[s].w != 0u) continue;
+                    const uint8_t *src = seq_blob + (s < n_q ? q_off[s] : t_off[s - n_q]);
+                    if (pack_seq_fast(src, seq[s].z, words.data() + ((uint64_t)seq[s].y << 32 | seq[s].x))) seq[s].w = MXF_BYTES;
+                }
+            };
+            const unsigned nt = (unsigned)std::min<uint64_t>(std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2)), n_seq / 4096 + 1);
+            std::vector<std::thread> th;
+            const uint64_t           per = (n_seq + nt - 1) / nt;
+            for (unsigned t = 0; t < nt; t++) {
+                const uint64_t a = std::min<uint64_t>(n_seq, (uint64_t)t * per), b = std::min<uint64_t>(n_seq, a + per);
+                bool inl = nt == 1;
+                if (!inl) {
+                    try {
+                        th.emplace_back(range, a, b);
+                    } catch (...) {
+                        inl = true;
+                    }
+                }
+                if (inl) range(a, b);
+            }
+            for (auto &t : th) t.join();
+        }
+        if ((rc = ensure(ctx, ctx->mx_seq, n_seq * 16))) return rc;
+        if ((rc = ensure(ctx, ctx->mx_words, words.size() * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->mx_seq.p, seq.data(), n_seq * 16, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->mx_words.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+        P.mx_seq = static_cast<const uint4 *>(ctx->mx_seq.p), P.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
+        P.mx_tbase = same ? 0u : n_q;
+        P.max_score = max_score, P.dx = dx, P.doe = doe, P.de = de, P.census = 0u, P.wide_exact = 0u, P.work = nullptr;
+        const uint32_t seq_words = (L + 15) / 16 + 1;
+        P.lds_seq_words = seq_words, P.sub_lds_words = wide_row_hw(L);
+        const size_t lds_g = (size_t)score_lds_words(seq_words) * 4;
+        const size_t lds_w = (size_t)wide_lds_words(seq_words, L) * 4, lds_n = (size_t)wide_lds_words_narrow(seq_words) * 4;
+        const int    waves = lds_w > 12 * 1024 ? 4 : 1;  // (as the full path: rings above 12 KB are shared by four waves)
+        const bool   two_phase = !glob && P.adaptive != 0u;
+        // ---- tiles: C targets x R queries, at most `tile` cells (columns split as well: 1 x 1e8 is 24 tiles)
+        uint64_t tile = glob ? MX_TILE_GLOBAL : std::min<uint64_t>(1ull << 18, MX_CKPT_BYTES / (WIDE_CKPT_WORDS * 4ull));
+        if (ctx->opt_matrix_tile_cells > 0) tile = std::min<uint64_t>((uint64_t)ctx->opt_matrix_tile_cells, 1ull << 24);
+        const uint64_t C = std::min(n_t, tile), R = std::min(n_q, tile / C);
+        tile = R * C;
+        if (two_phase && (rc = ensure(ctx, ctx->wide_ckpt, (size_t)tile * WIDE_CKPT_WORDS * 4))) return rc;
+        P.wide_ckpt = static_cast<uint32_t *>(ctx->wide_ckpt.p), P.wide_ckpt_on = two_phase ? 1u : 0u;
+        if ((rc = ensure(ctx, ctx->mx_out, (size_t)tile * 16))) return rc;
+        if (ctx->mx_pin_bytes < tile * 16) {
+            if (ctx->mx_pin) HIP_TRY(hipHostFree(ctx->mx_pin));
+            ctx->mx_pin = nullptr, ctx->mx_pin_bytes = 0;
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->mx_pin), tile * 16, hipHostMallocDefault));
+            ctx->mx_pin_bytes = tile * 16;
+        }
+        for (hipEvent_t &e : ctx->mx_ev)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        uint2 *const dout = static_cast<uint2 *>(ctx->mx_out.p);
+        struct Tile {
+            uint64_t r0, c0, rr, cc;
+        };
+        // tile t's results (in buffer b) into the caller's arrays; handed-back cells into fb
+        const auto scatter = [&](const Tile &t, int b) {
+            const uint2 *const h = ctx->mx_pin + (uint64_t)b * tile;
+            for (uint64_t r = 0; r < t.rr; r++)
+                for (uint64_t j = 0; j < t.cc; j++) {
+                    const uint2 v = h[r * t.cc + j];
+                    if (v.x >= ST_REDO_BYTES) fb.push_back((t.r0 + r) * n_t + t.c0 + j);
+                    else put(t.r0 + r, t.c0 + j, v.x, v.y);
+                }
+        };
+        HIP_TRY(hipEventRecord(ctx->ev0, st));
+        Tile     prev{};
+        uint64_t c = 0;
+        for (uint64_t r0 = 0; r0 < n_q; r0 += R)
+            for (uint64_t c0 = 0; c0 < n_t; c0 += C, c++) {
+                const Tile t{r0, c0, std::min(R, n_q - r0), std::min(C, n_t - c0)};
+                const int  b = (int)(c & 1u);
+                if (c >= 2) HIP_TRY(hipStreamWaitEvent(st, ctx->mx_ev[2 + b], 0));  // (buffer b's previous tile has left the device)
+                const uint32_t cn = (uint32_t)(t.rr * t.cc);
+                P.score_out = dout + (uint64_t)b * tile, P.chunk_first = 0u, P.chunk_n = cn;
+                P.mx_r0 = t.r0, P.mx_c0 = t.c0, P.mx_cols = (uint32_t)t.cc;
+                if (glob) {
+                    HIP_TRY(wfa_launch_score_matrix(P, cn, lds_g, st));
+                } else {
+                    HIP_TRY(wfa_launch_wide_score_matrix(shape, 0, waves, P, cn, lds_w, st));
+                    if (two_phase) {
+                        HIP_TRY(wfa_launch_wide_score_matrix(shape, 1, 1, P, cn, lds_n, st));
+                        tm.n_launches++;
+                    }
+                }
+                tm.n_launches++, tm.n_main_launches++;
+                HIP_TRY(hipEventRecord(ctx->mx_ev[b], st));
+                HIP_TRY(hipStreamWaitEvent(st_dn, ctx->mx_ev[b], 0));
+                HIP_TRY(hipMemcpyAsync(ctx->mx_pin + (uint64_t)b * tile, P.score_out, (size_t)cn * 8, hipMemcpyDeviceToHost, st_dn));
+                HIP_TRY(hipEventRecord(ctx->mx_ev[2 + b], st_dn));
+                if (c >= 1) {  // the previous tile, while this one runs
+                    HIP_TRY(hipEventSynchronize(ctx->mx_ev[2 + (b ^ 1)]));
+                    scatter(prev, b ^ 1);
+                }
+                prev = t;
+            }
+        HIP_TRY(hipEventRecord(ctx->ev1, st));
+        HIP_TRY(hipEventSynchronize(ctx->mx_ev[2 + (int)((c - 1) & 1u)]));
+        scatter(prev, (int)((c - 1) & 1u));
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        tm.kernel_ms = tm.main_kernel_ms = ms;
+        tm.main_kernel_kind = glob ? 21u : 22u;
+    }
+    // ---- the full path: what the kernels handed back (bytes outside ACGT, a band or a length they cannot hold) -- or every cell, for a
+    // penalty shape without an instance -- a batch of at most MX_FB_PAIRS cells at a time, only the score kept
+    const uint64_t n_fb = on_kernel ? (uint64_t)fb.size() : n_q * n_t;
+    {
+        std::vector<uint64_t> qo, to;
+        std::vector<uint32_t> ql, tl;
+        for (uint64_t a = 0; a < n_fb; a += MX_FB_PAIRS) {
+            const uint64_t n = std::min(MX_FB_PAIRS, n_fb - a);
+            qo.resize(n), to.resize(n), ql.resize(n), tl.resize(n);
+            for (uint64_t k = 0; k < n; k++) {
+                const uint64_t x = on_kernel ? fb[a + k] : a + k, i = x / n_t, j = x % n_t;
+                qo[k] = q_off[i], ql[k] = q_len[i], to[k] = t_off[j], tl[k] = t_len[j];
+            }
+            wfahip_results r;
+            if ((rc = align_batch_entry(ctx, p, seq_blob, blob_bytes, qo.data(), ql.data(), to.data(), tl.data(), n, &r))) return rc;
+            for (uint64_t k = 0; k < n; k++) {
+                const uint64_t x = on_kernel ? fb[a + k] : a + k;
+                const uint32_t st = (uint32_t)r.status[k], sc = r.score[k];
+                if (st == ST_OK && max_score != 0u && sc > max_score) put(x / n_t, x % n_t, ST_OVER_MAX, 0u);
+                else put(x / n_t, x % n_t, st, sc);
+            }
+            wfahip_results_free(&r);
+            const wfahip_timing &f = ctx->timing;
+            tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = std::max(tm.arena_bytes, f.arena_bytes);
+            if (!on_kernel) tm.main_kernel_ms += f.main_kernel_ms, tm.n_main_launches += f.n_main_launches, tm.main_kernel_kind = f.main_kernel_kind;
+        }
+    }
+    tm.n_retried_pairs = (uint32_t)std::min<uint64_t>(n_fb, UINT32_MAX);
+    tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    ctx->timing = tm;
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_score_matrix(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                                   const uint32_t *q_len, uint64_t n_q, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t, uint32_t max_score,
+                                   int32_t *status, uint32_t *score, uint64_t out_stride) {
+    WFAHIP_GUARD(score_matrix_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, n_q, t_off, t_len, n_t, max_score, status, score, out_stride))
+}
+
 // ---- pre-packed input (a quarter of the bytes cross PCIe)
 extern "C" int wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
                                          const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff,

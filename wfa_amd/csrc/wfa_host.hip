@@ -311,6 +311,9 @@ extern "C" void wfahip_destroy(wfahip_ctx *ctx) {
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->one_pin) (void)hipHostFree(ctx->one_pin);
     if (ctx->pack_pin) (void)hipHostFree(ctx->pack_pin);
+    if (ctx->mx_pin) (void)hipHostFree(ctx->mx_pin);
+    for (hipEvent_t e : ctx->mx_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->stream_up) (void)hipStreamDestroy(ctx->stream_up);
     if (ctx->stream_dn) (void)hipStreamDestroy(ctx->stream_dn);
     for (hipEvent_t e : ctx->ev_up) (void)hipEventDestroy(e);
@@ -319,7 +322,8 @@ extern "C" void wfahip_destroy(wfahip_ctx *ctx) {
         if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]);
     }
     for (DevBuf *b : {&ctx->arena, &ctx->fin, &ctx->team_ctl, &ctx->arena2, &ctx->meta2, &ctx->doneq, &ctx->ctrl, &ctx->redo, &ctx->work, &ctx->meta, &ctx->in_blob, &ctx->in_qoff, &ctx->in_qlen,
-                      &ctx->in_toff, &ctx->in_tlen, &ctx->out_rec, &ctx->out_ops, &ctx->in_packed, &ctx->in_small, &ctx->prepack, &ctx->one_ctl, &ctx->page_ctl, &ctx->xbuf, &ctx->wide_ckpt, &ctx->score_out})
+                      &ctx->in_toff, &ctx->in_tlen, &ctx->out_rec, &ctx->out_ops, &ctx->in_packed, &ctx->in_small, &ctx->prepack, &ctx->one_ctl, &ctx->page_ctl, &ctx->xbuf, &ctx->wide_ckpt, &ctx->score_out,
+                      &ctx->mx_seq, &ctx->mx_words, &ctx->mx_out})
         release(*b);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -451,6 +455,8 @@ static int set_option_impl(wfahip_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_wide = value;
     else if (k == "wide_min_pairs")
         ctx->opt_wide_min_pairs = value;
+    else if (k == "matrix_tile_cells")
+        ctx->opt_matrix_tile_cells = value > 0 ? value : 0;
     else if (k == "wide_max_len")
         ctx->opt_wide_max_len = value;
     else if (k == "wide_exact")

@@ -1,0 +1,33 @@
+// wfa_matrix.hpp -- the prologue the score kernels run in their matrix instances (wfahip_score_matrix: every query against every
+// target).  The host packs each of the n_q + n_t sequences ONCE into a table of 2-bit words and flags it once; a workgroup
+// finds its cell in a rectangular tile, copies the two sequences' packed words into LDS (no byte loads, no packing per cell)
+// and runs the row loop of the kernel it is an instance of, unchanged.
+#pragma once
+#include "wfa_common.hpp"
+
+namespace wfa {
+
+// flags of a sequence of the table (KParams::mx_seq[i].w); a cell takes the status of its two sequences' flags, OR-ed, in the
+// order the kernels test a pair: empty, too long, longer than the kernels take, a byte outside ACGT
+enum : uint32_t { MXF_EMPTY = 1u, MXF_TOO_LONG = 2u, MXF_LONG = 4u, MXF_BYTES = 8u };
+
+__host__ __device__ inline uint32_t mx_status(uint32_t f) {
+    return (f & MXF_EMPTY) ? ST_EMPTY : (f & MXF_TOO_LONG) ? ST_TOO_LONG : (f & MXF_LONG) ? ST_REDO_LDS : (f & MXF_BYTES) ? ST_REDO_BYTES : ST_PENDING;
+}
+
+// the table entries of cell idx of the tile (wave-uniform: one scalar division per workgroup)
+__device__ inline void mx_cell(const KParams &P, uint32_t idx, uint4 &qd, uint4 &td) {
+    const uint32_t r = idx / P.mx_cols, c = idx - r * P.mx_cols;
+    const uint4    a = P.mx_seq[P.mx_r0 + r], b = P.mx_seq[P.mx_tbase + P.mx_c0 + c];
+    const auto     rfl = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    qd = make_uint4(rfl(a.x), rfl(a.y), rfl(a.z), rfl(a.w)), td = make_uint4(rfl(b.x), rfl(b.y), rfl(b.z), rfl(b.w));
+}
+// words 0 .. (len + 15) / 16 of a packed sequence (the last one the zero pad word) into LDS: stage_pack's layout
+template <int G>
+__device__ inline void mx_stage(const uint32_t *words, const uint4 &d, uint32_t *dst, int tid) {
+    const uint32_t *const src = words + ((uint64_t)d.y << 32 | d.x);
+    const uint32_t        nw  = (d.z + 15u) >> 4;
+    for (uint32_t j = (uint32_t)tid; j <= nw; j += G) dst[j] = src[j];
+}
+
+}  // namespace wfa

@@ -1,6 +1,7 @@
 // wfa_score.hip -- translation unit of the score-only kernels behind wfahip_score_batch: wfa_score_kernel (global pairs, any
 // penalty shape score_shape_ok() takes) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
-// wfa_fwd_shape.inc).  The router is wfa_entry.hip (score_batch_impl).
+// wfa_fwd_shape.inc), and their matrix instances behind wfahip_score_matrix.  The routers are wfa_entry.hip (score_batch_impl,
+// score_matrix_impl).
 #define WFA_NO_AUX_KERNELS 1
 #define WFA_SCORE_UNIT 1
 #include "wfa_wide.hpp"
@@ -8,18 +9,21 @@
 
 namespace wfa {
 
-hipError_t wfa_launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+// (MATRIX: the instances of wfahip_score_matrix -- a cell of the score matrix per workgroup, wfa_matrix.hpp)
+template <bool MATRIX>
+static hipError_t launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     if (lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wfa_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wfa_score_kernel<MATRIX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(wfa_score_kernel, dim3(grid), dim3(64), lds_bytes, st, P);
+    hipLaunchKernelGGL(wfa_score_kernel<MATRIX>, dim3(grid), dim3(64), lds_bytes, st, P);
     return hipGetLastError();
 }
 
 // wfa_wide_kernel<.., SCORE = true> of penalty shape `shape` (wfa_fwd.hpp: fwd_shape()): phase 0 with `waves` waves per pair (1 or 4),
 // phase 1 with one -- as wfa_launch_wide (wfa_host.hip) launches the full-path instances
-hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+template <bool MATRIX>
+static hipError_t launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     const auto go = [&](auto kern, int nw) -> hipError_t {
         if (lds_bytes > 64 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -29,9 +33,9 @@ hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams 
         return hipGetLastError();
     };
 #define WFA_WIDE_SCORE_SHAPE(I, DX_, DOE_)                                                                      \
-    case 3 * I: return go(wfa_wide_kernel<DX_, DOE_, 0, 1, true>, 1);                                           \
-    case 3 * I + 1: return go(wfa_wide_kernel<DX_, DOE_, 0, 4, true>, 4);                                       \
-    case 3 * I + 2: return go(wfa_wide_kernel<DX_, DOE_, 1, 1, true>, 1);
+    case 3 * I: return go(wfa_wide_kernel<DX_, DOE_, 0, 1, true, MATRIX>, 1);                                   \
+    case 3 * I + 1: return go(wfa_wide_kernel<DX_, DOE_, 0, 4, true, MATRIX>, 4);                               \
+    case 3 * I + 2: return go(wfa_wide_kernel<DX_, DOE_, 1, 1, true, MATRIX>, 1);
     switch (shape * 3 + (phase ? 2 : (waves > 1 ? 1 : 0))) {
         WFA_WIDE_SCORE_SHAPE(0, 2, 4)
         WFA_WIDE_SCORE_SHAPE(1, 1, 3)
@@ -42,6 +46,15 @@ hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams 
     }
 #undef WFA_WIDE_SCORE_SHAPE
     return hipErrorInvalidValue;
+}
+
+hipError_t wfa_launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) { return launch_score<false>(P, grid, lds_bytes, st); }
+hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    return launch_wide_score<false>(shape, phase, waves, P, grid, lds_bytes, st);
+}
+hipError_t wfa_launch_score_matrix(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) { return launch_score<true>(P, grid, lds_bytes, st); }
+hipError_t wfa_launch_wide_score_matrix(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    return launch_wide_score<true>(shape, phase, waves, P, grid, lds_bytes, st);
 }
 
 }  // namespace wfa

@@ -16,8 +16,11 @@
 //   * one {status, score} per pair goes out, nothing else.
 // What it cannot hold -- a band wider than the ring (ST_REDO_BAND), a byte outside ACGT (ST_REDO_BYTES), a read longer than
 // SCORE_MAX_LEN (ST_REDO_LDS) -- is handed back to the host, which aligns those pairs on the full path.
+// MATRIX (wfahip_score_matrix): the workgroup's pair is a cell of a tile of the score matrix and its sequences come packed from the
+// call's sequence table (wfa_matrix.hpp); the row loop is the same.
 #pragma once
 #include "wfa_device.hpp"
+#include "wfa_matrix.hpp"
 
 namespace wfa {
 
@@ -35,6 +38,7 @@ inline bool score_shape_ok(uint32_t dx, uint32_t doe, uint32_t de) {
 }
 
 #ifdef WFA_SCORE_UNIT  // (the kernel lives in wfa_score.hip only; the host units take the constants)
+template <bool MATRIX = false>
 __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int       lane = (int)threadIdx.x;
@@ -56,11 +60,21 @@ __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
 
     const uint32_t idx = blockIdx.x;
     if (idx >= P.chunk_n) return;
-    const uint32_t pair = P.chunk_first + idx;
+    const uint32_t pair = MATRIX ? idx : P.chunk_first + idx;  // (MATRIX: the cell's slot of the tile's output)
     const auto     emit = [&](uint32_t st, uint32_t sc) {
         if (lane == 0) P.score_out[pair] = make_uint2(st, sc);
     };
-    const uint32_t nq = rfl(P.q_len[pair]), mt = rfl(P.t_len[pair]);
+    uint32_t nq, mt;
+    if constexpr (MATRIX) {
+        uint4 qd, td;
+        mx_cell(P, idx, qd, td);
+        nq = qd.z, mt = td.z;
+        const uint32_t st = mx_status(qd.w | td.w);  // (the table's flags: the tests below, made once per sequence)
+        if (st != ST_PENDING) return emit(st, 0u);
+        mx_stage<64>(P.mx_words, qd, lq, lane);
+        mx_stage<64>(P.mx_words, td, lt, lane);
+    } else {
+    nq = rfl(P.q_len[pair]), mt = rfl(P.t_len[pair]);
     if (nq == 0u || mt == 0u) return emit(ST_EMPTY, 0u);                         // wfa.go:204-206
     if (nq > 0x1FFFFFFFu || mt > 0x1FFFFFFFu) return emit(ST_TOO_LONG, 0u);      // wfa.go:207-209
     const uint32_t ml = nq > mt ? nq : mt;
@@ -69,6 +83,7 @@ __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
         bool bad = stage_pack<64>(P.blob, P.q_off[pair], nq, lq, lane);
         bad |= stage_pack<64>(P.blob, P.t_off[pair], mt, lt, lane);
         if (__ballot(bad) != 0ull) return emit(ST_REDO_BYTES, 0u);  // a byte outside ACGT: the byte-compare path takes the pair
+    }
     }
     const int n = (int)nq, m = (int)mt, Ak = m - n;
     SeqView<0> sv;

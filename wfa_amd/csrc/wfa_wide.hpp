@@ -32,6 +32,7 @@
 #pragma once
 #include "wfa_device.hpp"
 #include "wfa_pk16.hpp"  // wide_next2() and the packed helpers
+#include "wfa_matrix.hpp"  // the matrix instances' prologue
 
 namespace wfa {
 
@@ -71,10 +72,13 @@ __host__ __device__ inline uint32_t wide_lds_words_narrow(uint32_t seq_words) { 
 // SCORE (wfahip_score_batch): the score only -- no arena rows, no directory, no census; a semi-global pair stops at the first
 // row whose end-cell search finds a hit (the lowest score with one, wfa.go:270-375: a row's M is final after its extend and
 // reduce), and one {status, score} per pair goes to P.score_out
-template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1, bool SCORE = false>
+// MATRIX (SCORE only; wfahip_score_matrix): the workgroup's pair is cell idx of a tile of the score matrix, its sequences come packed
+// from the call's sequence table (wfa_matrix.hpp), and its {status, score} goes to P.score_out[idx]; the row loop is the same
+template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1, bool SCORE = false, bool MATRIX = false>
 __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(const KParams P) {
     static_assert(DX >= 1 && DOE >= 1 && DX <= 4 && DOE <= 4, "ring depths of one to four score steps");
     static_assert(NW == 1 || (PHASE == 0 && (NW == 2 || NW == 4)), "the narrow phase is one wave");
+    static_assert(SCORE || !MATRIX, "the matrix instances are score instances");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int       tid  = (int)threadIdx.x;
     const int       lane = tid & 63;
@@ -129,9 +133,16 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
         } else {
             if (P.wide_ckpt_on != 0u && tid == 0) ck[0] = 0u;
         }
-        const uint32_t pair = rfl(P.work ? P.work[idx] : P.chunk_first + idx);
-        const uint32_t nq = rfl(P.q_len[pair]), mt = rfl(P.t_len[pair]);
-        uint32_t       status = ST_PENDING;
+        uint32_t pair, nq, mt, status = ST_PENDING;
+        if constexpr (MATRIX) {
+            uint4 qd, td;
+            mx_cell(P, idx, qd, td);
+            pair = idx, nq = qd.z, mt = td.z;
+            status = mx_status(qd.w | td.w);  // (the table's flags: the tests below, made once per sequence)
+            if (status == ST_PENDING) mx_stage<64 * NW>(P.mx_words, qd, lq, tid), mx_stage<64 * NW>(P.mx_words, td, lt, tid);
+        } else {
+        pair = rfl(P.work ? P.work[idx] : P.chunk_first + idx);
+        nq = rfl(P.q_len[pair]), mt = rfl(P.t_len[pair]);
         if (nq == 0 || mt == 0)
             status = ST_EMPTY;  // wfa.go:204-206
         else if (nq > 0x1FFFFFFFu || mt > 0x1FFFFFFFu)
@@ -145,6 +156,7 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
             if constexpr (NW > 1) anybad = __syncthreads_or(bad ? 1 : 0) != 0;
             else anybad = __ballot(bad) != 0ull;
             if (anybad) status = ST_REDO_BYTES;  // a byte outside ACGT: the byte-compare path takes the pair
+        }
         }
         if (status != ST_PENDING) {
             if (tid == 0) {
