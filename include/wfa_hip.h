@@ -127,7 +127,9 @@ typedef struct {
                                   17 = wfa_teamc_kernel (wide wavefronts: a team of workgroups per pair, one backtrace word per diagonal),
                                   19 = wfa_score_kernel (wfahip_score_batch, global pairs), 20 = wfa_wide_kernel<.., SCORE> (wfahip_score_batch,
                                   semi-global pairs), 21 = wfa_score_kernel<MATRIX> (wfahip_score_matrix, global alignment),
-                                  22 = wfa_wide_kernel<.., SCORE, MATRIX> (wfahip_score_matrix, semi-global alignment) */
+                                  22 = wfa_wide_kernel<.., SCORE, MATRIX> (wfahip_score_matrix, semi-global alignment),
+                                  23 = wfa_score_long_kernel (wfahip_score_batch, global pairs of reads beyond 2 047 bases: reported when it took more
+                                  pairs of the call than wfa_score_kernel), 24 = wfa_score_long_kernel<MATRIX> (wfahip_score_matrix, likewise by cells) */
     uint32_t ladder_start_level; /* arena level the long-pair ladder of this call started on (0 unless a learned hint applied) */
 } wfahip_timing;
 
@@ -167,12 +169,15 @@ void wfahip_results_free(wfahip_results *r);
  * WFAHIP_PAIR_OVER_MAX -- exactly: global pairs when no M[s][m - n] reached the end by s = max_score, semi-global pairs when no
  * row up to max_score held an end cell (wfa.go:270-375) and none terminated.  Whole-call errors are those of wfahip_align_batch.
  * Only the forward pass runs, with the last rows on chip: no wavefront arena is allocated, nothing is kept for a backtrace.
- * Global pairs of reads up to 2 047 bases with e / g == 1 and x / g, (o+e) / g up to 7 (g = gcd(x, o+e, e)) run on
- * wfa_score_kernel; semi-global pairs up to 2 047 bases of the shapes wfahip_align_pair lists run on the score instances of
- * wfa_wide_kernel; every other pair -- a shape without an instance, a byte outside ACGT, a longer read, a band wider than the
- * kernel's 248 diagonals -- is aligned by the full path of wfahip_align_batch and only its score kept.  wfahip_last_timing:
- * main_kernel_kind 19 (wfa_score_kernel) or 20 (wfa_wide_kernel, score instances), n_retried_pairs = pairs that took the
- * full path, arena_bytes = 0 unless some did.  Release out with wfahip_scores_free (the arrays are malloc'd). */
+ * Global pairs with e / g == 1 and x / g, (o+e) / g up to 7 (g = gcd(x, o+e, e)): reads up to 2 047 bases run on
+ * wfa_score_kernel; longer reads, up to WFAHIP_MAX_SEQ_LEN, run on wfa_score_long_kernel (32-bit offsets, the sequences read 2-bit
+ * packed from global memory through sliding windows) when the call holds at least 64 such pairs (DEBUG option "score_long_min") --
+ * fewer take the full path.  Semi-global pairs up to 2 047 bases of the shapes wfahip_align_pair lists run on the score instances of
+ * wfa_wide_kernel.  Every other pair -- a shape without an instance, a byte outside ACGT, a longer semi-global read, a band wider
+ * than the kernels' 248 diagonals -- is aligned by the full path of wfahip_align_batch and only its score kept.  wfahip_last_timing:
+ * main_kernel_kind 19 (wfa_score_kernel), 23 (wfa_score_long_kernel, when it took more pairs of the call than wfa_score_kernel) or
+ * 20 (wfa_wide_kernel, score instances), n_retried_pairs = pairs that took the full path, arena_bytes = 0 unless some did.  Release
+ * out with wfahip_scores_free (the arrays are malloc'd). */
 typedef struct {
     uint64_t  n;
     int32_t  *status; /* WFAHIP_PAIR_OK / _EMPTY / _TOO_LONG / _NO_MEMORY / _OVER_MAX */
@@ -197,11 +202,14 @@ void wfahip_scores_free(wfahip_scores *s);
  * Each of the n_q + n_t sequences is 2-bit packed and checked once, and uploaded once (a quarter of its bytes); the cells run in
  * rectangular tiles on the matrix instances of the score kernels, global alignments on wfa_score_kernel, semi-global ones on
  * wfa_wide_kernel, each cell staging its two sequences from that table.  A tile's results download while the next tile runs.
- * The cells the score kernels cannot take -- a sequence with a byte outside ACGT or longer than 2 047 bases, a band wider than
- * wfa_score_kernel's 248 diagonals, every cell of a penalty shape without an instance -- are aligned by the full path of
- * wfahip_align_batch in batches of bounded size, and only their score kept.  wfahip_last_timing: main_kernel_kind 21 (global) or
- * 22 (semi-global) unless every cell took the full path, n_retried_pairs = cells that took the full path (saturating at
- * UINT32_MAX), arena_bytes = 0 unless some did. */
+ * Global cells with a sequence longer than 2 047 bases run on wfa_score_long_kernel<MATRIX>, a second launch over the same tile
+ * that reads the table's words through sliding windows, when the matrix holds at least 64 such cells (DEBUG option
+ * "score_long_min"); fewer take the full path.
+ * The cells the score kernels cannot take -- a sequence with a byte outside ACGT, a semi-global sequence longer than 2 047 bases, a
+ * band wider than the kernels' 248 diagonals, every cell of a penalty shape without an instance -- are aligned by the full path of
+ * wfahip_align_batch in batches of bounded size, and only their score kept.  wfahip_last_timing: main_kernel_kind 21 (global; 24
+ * when wfa_score_long_kernel took more cells than wfa_score_kernel) or 22 (semi-global) unless every cell took the full path,
+ * n_retried_pairs = cells that took the full path (saturating at UINT32_MAX), arena_bytes = 0 unless some did. */
 int  wfahip_score_matrix(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
                          const uint64_t *q_off, const uint32_t *q_len, uint64_t n_q,
                          const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t,
@@ -322,6 +330,11 @@ int  wfahip_last_timing(const wfahip_ctx *ctx, wfahip_timing *out);
  *   "wide_waves"  0|1|4    waves per pair in its first launch: 0 = by the rings' size (four above 12 KB)          default 0
  *   "matrix_tile_cells"    wfahip_score_matrix: cells per tile (0 = automatic: 4 194 304 global, 262 144 semi-global; tests force
  *                          small tiles so that the tiles split rows and columns)                                default 0
+ *   "score_long_min"       wfahip_score_batch / wfahip_score_matrix: global pairs (cells) of reads beyond 2 047 bases run on
+ *                          wfa_score_long_kernel when a call holds at least this many of them; fewer take the full path (such a launch
+ *                          fills a sixteenth of the SIMDs, and the arena it saves is a few MB; tests set 1)                  default 64
+ *   "score_long_window_words"  packed words of each sequence such a pair keeps in LDS (16..4096, a multiple of 4; results do not
+ *                          depend on it: a cell outside the window reads global memory)                                 default 256
  *   "arena_bytes_per_slot", "slots", "threads_per_pair"   generic kernel (one workgroup per pair)
  *   "prepack"  0|1         the sequences of a chunk are 2-bit packed by a kernel of their own before the 16-lane forward
  *                          kernel, whose refill then is one round of loads (forward pass -2 %, packing kernel +4 %)   default 0
@@ -395,6 +408,15 @@ int  wfahip_debug_team_compact(wfahip_ctx *ctx, const wfahip_params *p, const ui
                                wfahip_row **rows, uint64_t *n_rows, uint32_t **words, uint64_t *n_words, wfahip_results *res);
 int  wfahip_debug_compact_arena(wfahip_ctx *ctx, uint64_t pair, uint32_t **words, uint64_t *n_words, uint32_t *fmt,
                                 uint32_t *meta4);
+
+/* Debug / test aid, host only (no device, no context): what wfahip_score_batch hands wfa_score_long_kernel for a batch.  The global
+ * pairs with a read beyond 2 047 bases (neither sequence empty or over WFAHIP_MAX_SEQ_LEN) are 2-bit packed, pair after pair in batch
+ * order, query then target, in wfahip_pack_pairs' layout: *words (*n_words of them).  *table lists the *n_listed of them without a
+ * byte outside ACGT, eight words each: {query word offset lo, hi, query length, pair index, target word offset lo, hi, target
+ * length, 0}.  Caller frees *words and *table with wfahip_free. */
+int  wfahip_debug_score_long_list(const uint8_t *seq_blob, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off,
+                                  const uint32_t *t_len, uint64_t n_pairs, uint32_t **words, uint64_t *n_words, uint32_t **table,
+                                  uint64_t *n_listed);
 
 /* Synthetic input generator (host): the seeded dataset spec of DESIGN.md (mirrors what
  * WFA's generate_dataset, used by README.md:298-306, produces: random ACGT pattern of length

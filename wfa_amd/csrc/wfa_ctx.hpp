@@ -179,6 +179,9 @@ struct wfahip_ctx {
     size_t        mx_pin_bytes = 0;
     hipEvent_t    mx_ev[4]     = {};              // ... per buffer: its kernels are done, its download is done
     int64_t       opt_matrix_tile_cells    = 0;   // ... cells per tile (0 = automatic; tests force small tiles to cross tile edges)
+    int64_t       opt_score_long_min       = 64;  // wfahip_score_batch / _matrix: global pairs (cells) beyond wfa_score_kernel's 2 047 bases run on wfa_score_long_kernel when a call
+                                                  // holds at least this many of them (fewer: the full path -- such a launch fills a sixteenth of the SIMDs to save a few MB of arena)
+    int64_t       opt_score_long_window    = 256; // ... packed words of each sequence a pair keeps in LDS (wfa_score_long.hpp; tests: small windows, which move often)
     int64_t       opt_wide                 = 1;   // semi-global batches of reads up to 2 047 bases (penalties of one of the sub-wave shapes) start on wfa_wide_kernel (round 6: a workgroup per
                                                   // pair, the rows in 16-bit LDS rings of any width, two launches per chunk under wf-adaptive); 3: one launch per chunk, every pair
                                                   // runs to its end in the wide rings; 0: on the generic ladder

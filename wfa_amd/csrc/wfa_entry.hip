@@ -13,6 +13,7 @@
 #include "wfa_finalize.hpp"
 #include "wfa_wide.hpp"
 #include "wfa_score.hpp"
+#include "wfa_score_long.hpp"
 
 using namespace wfa;
 
@@ -827,7 +828,100 @@ extern "C" int wfahip_align_batch(wfahip_ctx *ctx, const wfahip_params *p, const
 namespace wfa {
 hipError_t wfa_launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 }  // namespace wfa
+
+// ---- the pairs of a score batch that wfa_score_long_kernel takes (wfa_score_long.hpp): global pairs with a read beyond wfa_score_kernel's
+// SCORE_MAX_LEN, neither empty nor too long.  They are 2-bit packed on host threads into ONE word buffer, in wfahip_pack_pairs' layout
+// (pair after pair, query then target, each word-aligned with its pad word), and listed for the kernel: two table entries per pair,
+// {word offset lo, hi, length, pair index} for the query and {.., .., length, 0} for the target.  A pair with a byte outside ACGT is
+// packed but not listed (`bytes`): it stays on the full path.
+namespace {
+struct ScoreLongPlan {
+    std::vector<uint64_t> ids;     // the long pairs, in batch order
+    std::vector<uint64_t> qw, tw;  // word offsets of their sequences
+    uint64_t              n_words = 0;
+};
+void score_long_plan(const uint32_t *q_len, const uint32_t *t_len, uint64_t n_pairs, ScoreLongPlan &pl) {
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (!(q_len[i] && t_len[i] && q_len[i] <= WFAHIP_MAX_SEQ_LEN && t_len[i] <= WFAHIP_MAX_SEQ_LEN)) continue;
+        if (std::max(q_len[i], t_len[i]) <= SCORE_MAX_LEN) continue;
+        pl.ids.push_back(i);
+        pl.qw.push_back(pl.n_words), pl.n_words += wfahip_packed_words(q_len[i]);
+        pl.tw.push_back(pl.n_words), pl.n_words += wfahip_packed_words(t_len[i]);
+    }
+}
+// words must hold pl.n_words words
+void score_long_pack(const uint8_t *seq_blob, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
+                     const ScoreLongPlan &pl, uint32_t *words, std::vector<uint4> &table, std::vector<uint64_t> &bytes) {
+    const uint64_t       n = pl.ids.size();
+    std::vector<uint8_t> bad(n, 0);
+    const auto           range = [&](uint64_t a, uint64_t b) {
+        for (uint64_t j = a; j < b; j++) {
+            const uint64_t i = pl.ids[j];
+            bool           bd = pack_seq_fast(seq_blob + q_off[i], q_len[i], words + pl.qw[j]);
+            bd |= pack_seq_fast(seq_blob + t_off[i], t_len[i], words + pl.tw[j]);
+            bad[j] = bd ? 1 : 0;
+        }
+    };
+    unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
+    if (const char *e = std::getenv("WFAHIP_PACK_THREADS")) n_thr = (unsigned)std::max(1, std::atoi(e));
+    const unsigned           nt = (unsigned)std::min<uint64_t>(std::min<uint64_t>(n_thr, pl.n_words / 65536 + 1), std::max<uint64_t>(n, 1));
+    std::vector<std::thread> th;
+    const uint64_t           per = (n + nt - 1) / nt;
+    for (unsigned t = 0; t < nt; t++) {
+        const uint64_t a = std::min<uint64_t>(n, (uint64_t)t * per), b = std::min<uint64_t>(n, a + per);
+        bool           inl = nt == 1;
+        if (!inl) {
+            try {
+                th.emplace_back(range, a, b);
+            } catch (...) {
+                inl = true;
+            }
+        }
+        if (inl) range(a, b);
+    }
+    for (auto &t : th) t.join();
+    table.clear(), bytes.clear();
+    for (uint64_t j = 0; j < n; j++) {
+        const uint64_t i = pl.ids[j];
+        if (bad[j]) {
+            bytes.push_back(i);
+            continue;
+        }
+        table.push_back(make_uint4((uint32_t)pl.qw[j], (uint32_t)(pl.qw[j] >> 32), q_len[i], (uint32_t)i));
+        table.push_back(make_uint4((uint32_t)pl.tw[j], (uint32_t)(pl.tw[j] >> 32), t_len[i], 0u));
+    }
+}
+}  // namespace
+
+// Debug / test aid, host only: the word buffer and the list above for a batch (include/wfa_hip.h)
+extern "C" int wfahip_debug_score_long_list(const uint8_t *seq_blob, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off,
+                                            const uint32_t *t_len, uint64_t n_pairs, uint32_t **words, uint64_t *n_words, uint32_t **table,
+                                            uint64_t *n_listed) {
+    if (!q_off || !q_len || !t_off || !t_len || !words || !n_words || !table || !n_listed || (!seq_blob && n_pairs)) return WFAHIP_ERR_BAD_ARG;
+    try {
+        ScoreLongPlan pl;
+        score_long_plan(q_len, t_len, n_pairs, pl);
+        std::vector<uint4>    tb;
+        std::vector<uint64_t> bytes;
+        uint32_t *const       w = static_cast<uint32_t *>(std::malloc((size_t)(pl.n_words + 1) * 4));
+        if (!w) return WFAHIP_ERR_OOM;
+        score_long_pack(seq_blob, q_off, q_len, t_off, t_len, pl, w, tb, bytes);
+        uint32_t *const t = static_cast<uint32_t *>(std::malloc(tb.size() * 16 + 16));
+        if (!t) {
+            std::free(w);
+            return WFAHIP_ERR_OOM;
+        }
+        if (!tb.empty()) std::memcpy(t, tb.data(), tb.size() * 16);
+        *words = w, *n_words = pl.n_words, *table = t, *n_listed = tb.size() / 2;
+        return WFAHIP_OK;
+    } catch (const std::bad_alloc &) {
+        return WFAHIP_ERR_OOM;
+    } catch (...) {
+        return WFAHIP_ERR_INTERNAL;
+    }
+}
 
 extern "C" void wfahip_scores_free(wfahip_scores *s) {
     if (!s) return;
@@ -867,19 +961,54 @@ static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
     const bool     glob  = P.global_alignment != 0u;
     const int      shape = fwd_shape(dx, doe, de);
     const bool     on_kernel = glob ? score_shape_ok(dx, doe, de) : shape >= 0;
+    // ---- global pairs beyond wfa_score_kernel's length: wfa_score_long_kernel takes them when the call holds at least "score_long_min"
+    // of them; they are packed here (host threads) into the context's page-locked word buffer and listed
+    ScoreLongPlan         lp;
+    std::vector<uint4>    ltab;    // two entries per listed pair
+    std::vector<uint64_t> lbytes;  // long pairs with a byte outside ACGT: the full path
+    bool                  use_long = false;
+    if (on_kernel && glob && n_pairs <= UINT32_MAX) {
+        score_long_plan(q_len, t_len, n_pairs, lp);
+        use_long = !lp.ids.empty() && (int64_t)lp.ids.size() >= ctx->opt_score_long_min;
+    }
+    if (use_long) {
+        const size_t need = (size_t)(lp.n_words + 4) * 4;
+        if (ctx->pack_pin_bytes < need) {
+            if (ctx->pack_pin) (void)hipHostFree(ctx->pack_pin);
+            ctx->pack_pin = nullptr, ctx->pack_pin_bytes = 0;
+            if (hipHostMalloc(reinterpret_cast<void **>(&ctx->pack_pin), need + need / 8, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                ctx->pack_pin = nullptr;
+                use_long = false;  // (no page-locked memory for the words: these pairs take the full path, as below the gate)
+            } else {
+                ctx->pack_pin_bytes = need + need / 8;
+            }
+        }
+    }
+    if (use_long) score_long_pack(seq_blob, q_off, q_len, t_off, t_len, lp, ctx->pack_pin, ltab, lbytes);
+    const uint64_t n_listed   = ltab.size() / 2;
+    const bool     skip_short = use_long && lp.ids.size() == n_pairs;  // every pair is long: nothing for wfa_score_kernel
     if (on_kernel) {
         hipStream_t st = ctx->stream;
-        if ((rc = ensure(ctx, ctx->in_blob, blob_bytes + 32))) return rc;
-        if ((rc = ensure(ctx, ctx->in_qoff, n_pairs * 8))) return rc;
-        if ((rc = ensure(ctx, ctx->in_toff, n_pairs * 8))) return rc;
-        if ((rc = ensure(ctx, ctx->in_qlen, n_pairs * 4))) return rc;
-        if ((rc = ensure(ctx, ctx->in_tlen, n_pairs * 4))) return rc;
         if ((rc = ensure(ctx, ctx->score_out, n_pairs * 8))) return rc;
-        if (blob_bytes) HIP_TRY(hipMemcpyAsync(ctx->in_blob.p, seq_blob, blob_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->in_qoff.p, q_off, n_pairs * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->in_toff.p, t_off, n_pairs * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+        if (!skip_short) {
+            if ((rc = ensure(ctx, ctx->in_blob, blob_bytes + 32))) return rc;
+            if ((rc = ensure(ctx, ctx->in_qoff, n_pairs * 8))) return rc;
+            if ((rc = ensure(ctx, ctx->in_toff, n_pairs * 8))) return rc;
+            if ((rc = ensure(ctx, ctx->in_qlen, n_pairs * 4))) return rc;
+            if ((rc = ensure(ctx, ctx->in_tlen, n_pairs * 4))) return rc;
+            if (blob_bytes) HIP_TRY(hipMemcpyAsync(ctx->in_blob.p, seq_blob, blob_bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_qoff.p, q_off, n_pairs * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_toff.p, t_off, n_pairs * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+        }
+        if (n_listed) {
+            if ((rc = ensure(ctx, ctx->mx_seq, ltab.size() * 16))) return rc;
+            if ((rc = ensure(ctx, ctx->mx_words, (size_t)(lp.n_words + 4) * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->mx_seq.p, ltab.data(), ltab.size() * 16, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->mx_words.p, ctx->pack_pin, (size_t)lp.n_words * 4, hipMemcpyHostToDevice, st));
+        }
         P.blob = static_cast<const uint8_t *>(ctx->in_blob.p), P.blob_bytes = blob_bytes;
         P.q_off = static_cast<const uint64_t *>(ctx->in_qoff.p), P.t_off = static_cast<const uint64_t *>(ctx->in_toff.p);
         P.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), P.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p);
@@ -900,7 +1029,7 @@ static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
         if (!ctx->ev0) HIP_TRY(hipEventCreate(&ctx->ev0));
         if (!ctx->ev1) HIP_TRY(hipEventCreate(&ctx->ev1));
         HIP_TRY(hipEventRecord(ctx->ev0, st));
-        for (uint64_t c0 = 0; c0 < n_pairs; c0 += chunk) {
+        for (uint64_t c0 = 0; c0 < n_pairs && !skip_short; c0 += chunk) {
             const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_pairs - c0);
             P.chunk_first = (uint32_t)c0, P.chunk_n = cn;
             if (glob) {
@@ -914,13 +1043,30 @@ static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
             }
             tm.n_launches++, tm.n_main_launches++;
         }
+        // the listed long pairs, behind wfa_score_kernel on the same stream: their slots (ST_REDO_LDS there) take the long kernel's result
+        const bool long_main = n_listed > n_pairs - lp.ids.size();  // it took more pairs of the call than the short kernel
+        if (n_listed) {
+            KParams PL = P;
+            PL.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
+            PL.lds_seq_words = score_long_window(ctx->opt_score_long_window);
+            const size_t lds_l = (size_t)score_long_lds_words(PL.lds_seq_words) * 4;
+            for (uint64_t c0 = 0; c0 < n_listed; c0 += chunk) {
+                const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_listed - c0);
+                PL.mx_seq = static_cast<const uint4 *>(ctx->mx_seq.p) + 2 * c0, PL.chunk_first = 0u, PL.chunk_n = cn;
+                HIP_TRY(wfa_launch_score_long(false, PL, cn, lds_l, st));
+                tm.n_launches++;
+                if (long_main) tm.n_main_launches++;
+            }
+        }
         HIP_TRY(hipEventRecord(ctx->ev1, st));
         HIP_TRY(hipMemcpyAsync(res.data(), ctx->score_out.p, n_pairs * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         tm.kernel_ms = tm.main_kernel_ms = ms;
-        tm.main_kernel_kind = glob ? 19u : 20u;
+        tm.main_kernel_kind = glob ? (long_main ? 23u : 19u) : 20u;
+        // (long pairs that were not listed: wfa_score_kernel said ST_REDO_LDS, or never saw them)
+        for (const uint64_t i : lbytes) res[i] = make_uint2(ST_REDO_BYTES, 0u);
     } else {
         for (uint64_t i = 0; i < n_pairs; i++) res[i] = make_uint2(ST_REDO_BAND, 0u);
     }
@@ -1023,19 +1169,42 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
         std::vector<uint4> seq(n_seq);
         uint64_t           pos = 0;
         uint32_t           L   = 1;
+        const auto flag_of = [&](uint64_t s) {
+            const uint32_t len = s < n_q ? q_len[s] : t_len[s - n_q];
+            return len == 0 ? (uint32_t)MXF_EMPTY : len > WFAHIP_MAX_SEQ_LEN ? (uint32_t)MXF_TOO_LONG : len > kmax ? (uint32_t)MXF_LONG : 0u;
+        };
+        // cells of the global matrix with a long sequence and nothing else against them (flags MXF_LONG only) run on wfa_score_long_kernel when
+        // the call holds at least "score_long_min" of them: the long sequences are then packed into the table too.  Counted from the flags of
+        // the two sides: {sequences without a flag, sequences flagged `want` only}
+        const auto count_side = [&](uint64_t a, uint64_t b, const auto &fl, uint64_t &plain, uint64_t &lng) {
+            plain = lng = 0;
+            for (uint64_t s = a; s < b; s++) {
+                const uint32_t f = fl(s);
+                plain += f == 0u, lng += f == MXF_LONG;
+            }
+        };
+        const auto long_cells = [&](const auto &fl) {
+            uint64_t pq, lq_, pt, lt_;
+            count_side(0, n_q, fl, pq, lq_);
+            if (same) pt = pq, lt_ = lq_;
+            else count_side(n_q, n_seq, fl, pt, lt_);
+            return lq_ * (pt + lt_) + pq * lt_;
+        };
+        bool use_long = glob && long_cells(flag_of) >= (uint64_t)ctx->opt_score_long_min;
         for (uint64_t s = 0; s < n_seq; s++) {
             const uint32_t len  = s < n_q ? q_len[s] : t_len[s - n_q];
-            const uint32_t flag = len == 0 ? MXF_EMPTY : len > WFAHIP_MAX_SEQ_LEN ? MXF_TOO_LONG : len > kmax ? MXF_LONG : 0u;
+            const uint32_t flag = flag_of(s);
             seq[s] = make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), len, flag);
-            if (flag == 0u) pos += wfahip_packed_words(len), L = std::max(L, len);
+            if (flag == 0u) L = std::max(L, len);
+            if (flag == 0u || (use_long && flag == MXF_LONG)) pos += wfahip_packed_words(len);
         }
         std::vector<uint32_t> words(pos + 4);
         {
             const auto range = [&](uint64_t a, uint64_t b) {
                 for (uint64_t s = a; s < b; s++) {
-                    if (seq[s].w != 0u) continue;
+                    if (!(seq[s].w == 0u || (use_long && seq[s].w == MXF_LONG))) continue;
                     const uint8_t *src = seq_blob + (s < n_q ? q_off[s] : t_off[s - n_q]);
-                    if (pack_seq_fast(src, seq[s].z, words.data() + ((uint64_t)seq[s].y << 32 | seq[s].x))) seq[s].w = MXF_BYTES;
+                    if (pack_seq_fast(src, seq[s].z, words.data() + ((uint64_t)seq[s].y << 32 | seq[s].x))) seq[s].w |= MXF_BYTES;
                 }
             };
             const unsigned nt = (unsigned)std::min<uint64_t>(std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2)), n_seq / 4096 + 1);
@@ -1055,6 +1224,17 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
             }
             for (auto &t : th) t.join();
         }
+        // (the count again, now that the bytes are known: cells with a byte outside ACGT stay on the full path and do not open the gate)
+        uint64_t n_long_cells = 0;
+        if (use_long) {
+            n_long_cells = long_cells([&](uint64_t s) { return seq[s].w; });
+            use_long     = n_long_cells >= (uint64_t)ctx->opt_score_long_min;
+        }
+        // sequences flagged MXF_LONG before each index: a tile has a cell for the long kernel when a row or a column of it is long, and none
+        // for wfa_score_kernel<MATRIX> when all its rows or all its columns are
+        std::vector<uint64_t> n_lng(use_long ? n_seq + 1 : 0, 0);
+        for (uint64_t s = 0; s < n_seq && use_long; s++) n_lng[s + 1] = n_lng[s] + ((seq[s].w & MXF_LONG) ? 1u : 0u);
+        const bool long_main = use_long && n_long_cells > n_q * n_t - n_long_cells;
         if ((rc = ensure(ctx, ctx->mx_seq, n_seq * 16))) return rc;
         if ((rc = ensure(ctx, ctx->mx_words, words.size() * 4))) return rc;
         HIP_TRY(hipMemcpyAsync(ctx->mx_seq.p, seq.data(), n_seq * 16, hipMemcpyHostToDevice, st));
@@ -1110,7 +1290,20 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
                 P.score_out = dout + (uint64_t)b * tile, P.chunk_first = 0u, P.chunk_n = cn;
                 P.mx_r0 = t.r0, P.mx_c0 = t.c0, P.mx_cols = (uint32_t)t.cc;
                 if (glob) {
-                    HIP_TRY(wfa_launch_score_matrix(P, cn, lds_g, st));
+                    // two launches over the tile: each kernel takes its own cells and leaves the other's slots alone
+                    bool some_long = false, all_long = false;
+                    if (use_long) {
+                        const uint64_t tb = same ? 0u : n_q;
+                        const uint64_t lr = n_lng[t.r0 + t.rr] - n_lng[t.r0], lc = n_lng[tb + t.c0 + t.cc] - n_lng[tb + t.c0];
+                        some_long = lr != 0 || lc != 0, all_long = lr == t.rr || lc == t.cc;
+                    }
+                    if (!all_long) HIP_TRY(wfa_launch_score_matrix(P, cn, lds_g, st));
+                    if (some_long) {
+                        KParams PL = P;
+                        PL.lds_seq_words = score_long_window(ctx->opt_score_long_window);
+                        HIP_TRY(wfa_launch_score_long(true, PL, cn, (size_t)score_long_lds_words(PL.lds_seq_words) * 4, st));
+                        if (!all_long) tm.n_launches++;
+                    }
                 } else {
                     HIP_TRY(wfa_launch_wide_score_matrix(shape, 0, waves, P, cn, lds_w, st));
                     if (two_phase) {
@@ -1136,7 +1329,7 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         tm.kernel_ms = tm.main_kernel_ms = ms;
-        tm.main_kernel_kind = glob ? 21u : 22u;
+        tm.main_kernel_kind = glob ? (long_main ? 24u : 21u) : 22u;
     }
     // ---- the full path: what the kernels handed back (bytes outside ACGT, a band or a length they cannot hold) -- or every cell, for a
     // penalty shape without an instance -- a batch of at most MX_FB_PAIRS cells at a time, only the score kept

@@ -457,6 +457,10 @@ static int set_option_impl(wfahip_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_wide_min_pairs = value;
     else if (k == "matrix_tile_cells")
         ctx->opt_matrix_tile_cells = value > 0 ? value : 0;
+    else if (k == "score_long_min")
+        ctx->opt_score_long_min = value > 0 ? value : 1;
+    else if (k == "score_long_window_words")
+        ctx->opt_score_long_window = value;
     else if (k == "wide_max_len")
         ctx->opt_wide_max_len = value;
     else if (k == "wide_exact")

@@ -1,11 +1,12 @@
 // wfa_score.hip -- translation unit of the score-only kernels behind wfahip_score_batch: wfa_score_kernel (global pairs, any
-// penalty shape score_shape_ok() takes) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
+// penalty shape score_shape_ok() takes; wfa_score_long_kernel for reads beyond its 2 047 bases) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
 // wfa_fwd_shape.inc), and their matrix instances behind wfahip_score_matrix.  The routers are wfa_entry.hip (score_batch_impl,
 // score_matrix_impl).
 #define WFA_NO_AUX_KERNELS 1
 #define WFA_SCORE_UNIT 1
 #include "wfa_wide.hpp"
 #include "wfa_score.hpp"
+#include "wfa_score_long.hpp"
 
 namespace wfa {
 
@@ -17,6 +18,16 @@ static hipError_t launch_score(const KParams &P, uint32_t grid, size_t lds_bytes
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(wfa_score_kernel<MATRIX>, dim3(grid), dim3(64), lds_bytes, st, P);
+    return hipGetLastError();
+}
+
+// wfa_score_long_kernel (wfa_score_long.hpp) over a list of `grid` long pairs -- matrix: over the `grid` cells of a tile, of which it
+// takes those with a long sequence.  Its LDS (score_long_lds_words: 14 KB at the default window, 44 KB at the largest) needs no opt-in
+hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    if (matrix)
+        hipLaunchKernelGGL(wfa_score_long_kernel<true>, dim3(grid), dim3(64), lds_bytes, st, P);
+    else
+        hipLaunchKernelGGL(wfa_score_long_kernel<false>, dim3(grid), dim3(64), lds_bytes, st, P);
     return hipGetLastError();
 }
 
