@@ -228,6 +228,30 @@ int  wfahip_align_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const vo
                                uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap,
                                uint64_t *ops_needed, void *stream);
 
+/* Score only on device-resident input: wfahip_score_batch for a batch that already lives in HBM -- the output of
+ * wfahip_generate_pairs_device, a torch pipeline, the candidates of an earlier GPU stage -- with the results left there for the next
+ * stage.  Conventions as wfahip_align_batch_device: every pointer is a device address on the context's GPU and stays the caller's;
+ * d_q_off / d_t_off are u64, d_q_len / d_t_len u32; max_len = an upper bound of every length (0 = the library finds it, on the
+ * device); stream = hipStream_t to launch on (NULL = the context's own).  Synchronous: returns when the results are complete.
+ * d_status (int32) and d_score (uint32) receive n_pairs elements each and nothing beyond them; the inputs are never written.
+ * For every pair, d_status[i] and d_score[i] equal what wfahip_score_batch returns for the same bytes, params and max_score
+ * (WFAHIP_PAIR_OK / _EMPTY / _TOO_LONG / _NO_MEMORY / _OVER_MAX, score 0 unless OK), and the same kernels do the work.
+ * Whole-call errors: WFAHIP_ERR_BAD_ARG for a null ctx or p, or with n_pairs > 0 a null offset, length or output pointer (or a null
+ * blob with blob_bytes > 0) -- checked before the device is touched; then the params as wfahip_align_batch checks them; n_pairs == 0
+ * returns WFAHIP_OK and touches nothing.  The offsets cannot be seen from the host: wfa_score_plan_kernel checks, from the offset and
+ * length arrays alone, that every non-empty pair within WFAHIP_MAX_SEQ_LEN lies inside [0, blob_bytes), and a batch that fails
+ * returns WFAHIP_ERR_BAD_ARG with the outputs untouched BEFORE any kernel that reads a sequence byte is launched.
+ * What the host entry does with the sequences in its hands happens on the device (wfa_score_dev.hpp): the long global pairs are
+ * listed by a scan in batch order and 2-bit packed from the caller's blob by wfa_score_pack_kernel; the pairs the score kernels hand
+ * back are gathered in pair order by wfa_score_redo_kernel (their offsets keep pointing into the caller's blob) and aligned by the
+ * full path of wfahip_align_batch_device into buffers of the context; wfa_score_finish_kernel writes d_status / d_score.  Apart from
+ * the kernel arguments, three fetches of 64 bytes of counters per call cross PCIe, plus what the full path itself fetches when
+ * pairs take it.  wfahip_last_timing as after wfahip_score_batch (main_kernel_kind 19 / 23 / 20, n_retried_pairs, arena_bytes). */
+int  wfahip_score_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_seq_blob, uint64_t blob_bytes,
+                               const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len,
+                               uint64_t n_pairs, uint32_t max_len, uint32_t max_score, void *d_status, void *d_score,
+                               void *stream);
+
 /* Pre-packed input: the sequences arrive 2-bit packed, 16 bases per uint32 (base i of a
  * sequence in bits 2(i%16).. of word i/16, code = (ascii >> 1) & 3: A 0, C 1, T 2, G 3), every sequence starting at a
  * word boundary and followed by one pad word; pair i is packed[q_woff[i] ..] (q_len[i] bases) vs packed[t_woff[i] ..].
@@ -417,6 +441,12 @@ int  wfahip_debug_compact_arena(wfahip_ctx *ctx, uint64_t pair, uint32_t **words
 int  wfahip_debug_score_long_list(const uint8_t *seq_blob, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off,
                                   const uint32_t *t_len, uint64_t n_pairs, uint32_t **words, uint64_t *n_words, uint32_t **table,
                                   uint64_t *n_listed);
+
+/* Debug / test aid: the same buffer and table as the LAST wfahip_score_batch_device call on ctx built them on the device
+ * (wfa_score_plan_kernel, wfa_score_pack_kernel, wfa_score_list_kernel), copied to the host: word for word what
+ * wfahip_debug_score_long_list returns for the same batch.  *n_words == 0 (and NULL arrays) when that call ran no long pairs on
+ * wfa_score_long_kernel; valid until the next score call on ctx.  Caller frees *words and *table with wfahip_free. */
+int  wfahip_debug_score_device_list(wfahip_ctx *ctx, uint32_t **words, uint64_t *n_words, uint32_t **table, uint64_t *n_listed);
 
 /* Synthetic input generator (host): the seeded dataset spec of DESIGN.md (mirrors what
  * WFA's generate_dataset, used by README.md:298-306, produces: random ACGT pattern of length

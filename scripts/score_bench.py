@@ -9,7 +9,13 @@ wf-adaptive 10/50/1, seed 5; --pairs scales L5 down for a rehearsal.  --other-li
 ANOTHER build of the library (the parent commit's, built beforehand) on the same inputs, alternating with the two others in
 the same process, so that the new score path is read against the old one and against that one's own run-to-run spread.
 
+Device leg (--device, KERNELS.md 4j): the legs become `score` (wfahip_score_batch, host arrays), `score_device`
+(wfahip_score_batch_device on the same data resident in HBM, results left there) and `align_device`
+(wfahip_align_batch_device on the same buffers), alternating per step; the scores of all three are compared in every step,
+outside the timed region.
+
     python scripts/score_bench.py [--configs c3,g3] [--pairs 1000000] [--steps 5]
+    python scripts/score_bench.py --device --configs c3,g3,L5 [--other-lib parent/wfa_amd/lib/libwfahip.so]
     python scripts/score_bench.py --configs L5,l5 [--other-lib parent/wfa_amd/lib/libwfahip.so]
 """
 import argparse
@@ -68,11 +74,52 @@ class OtherLib:
         self.lib.wfahip_destroy(self.ctx)
 
 
+def device_legs(w, al, arrays, glob, length, err):
+    """The legs on device-resident input: the batch as torch tensors in HBM, scored by wfahip_score_batch_device and aligned by
+    wfahip_align_batch_device.  Each returns a function that fetches (status, score) -- called outside the timed region."""
+    import torch
+    from wfa_amd import _lib as L
+    dev = torch.device("cuda", 0)
+    blob, q_off, q_len, t_off, t_len = arrays
+    n = len(q_len)
+    d = [torch.from_numpy(a).to(dev) for a in (blob, q_off.view(np.int64), q_len.view(np.int32), t_off.view(np.int64), t_len.view(np.int32))]
+    max_len = int(max(q_len.max(), t_len.max()))
+    sum_len = int(q_len.astype(np.int64).sum() + t_len.astype(np.int64).sum())
+    ops_cap = int(sum_len * max(0.25, 3.0 * err)) + 8 * n + 1024  # (bench.py's sizing)
+    if not glob or length >= 20000:
+        ops_cap = sum_len + 2 * n + 1024
+    d_rec = torch.zeros((n, L.REC_WORDS), dtype=torch.int32, device=dev)
+    d_ops = torch.zeros(ops_cap, dtype=torch.int64, device=dev)
+    out = (torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+    torch.cuda.synchronize(dev)
+    prm, lib = al._params(), L.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def score_device():
+        al.score_tensors(*d, out=out)
+        return lambda: (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32))
+
+    def align_device():
+        needed = C.c_uint64()
+        L.check(lib.wfahip_align_batch_device(al._ctx, C.byref(prm), d[0].data_ptr(), blob.size, d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                                              d[4].data_ptr(), n, max_len, d_rec.data_ptr(), d_ops.data_ptr(), ops_cap, C.byref(needed), stream),
+                "wfahip_align_batch_device")
+
+        def fetch():
+            rec = d_rec[:, :2].cpu().numpy()
+            st = rec[:, L.REC_STATUS].copy()
+            return st, np.where(st == 0, rec[:, L.REC_SCORE].view(np.uint32), 0).astype(np.uint32)
+        return fetch
+
+    return [("score_device", score_device, al), ("align_device", align_device, al)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="c3,g3")
     ap.add_argument("--pairs", type=int, default=None, help="pairs of c3 / g3 (default 1e6); scales L5 down when given")
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--device", action="store_true", help="legs on device-resident input: score (host entry), score_device, align_device")
     ap.add_argument("--other-lib", default=None, help="libwfahip.so of another build: its wfahip_score_batch runs as a third leg")
     args = ap.parse_args()
     import torch
@@ -89,6 +136,8 @@ def main():
         al = w.New(w.DefaultPenalties, w.Options(GlobalAlignment=glob), device=0)
         assert al.AdaptiveReduction(w.DefaultAdaptiveOption) is None
         fns = [("align", lambda: al.align_arrays(*arrays), al), ("score", lambda: al.score_arrays(*arrays), al)]
+        if args.device:
+            fns = [("score", lambda: al.score_arrays(*arrays), al)] + device_legs(w, al, arrays, glob, length, err)
         other = None
         if args.other_lib:
             other = OtherLib(args.other_lib, w, glob)
@@ -104,12 +153,14 @@ def main():
                 dt = (time.perf_counter() - t0) * 1e3
                 t = who.last_timing()
                 legs[leg].append((dt, t.kernel_ms, t.main_kernel_kind, t.n_retried_pairs, t.arena_bytes))
-            ref = res["align"]
-            want = np.where(ref.status == 0, ref.score, 0)
+            if args.device:
+                ref_status, want = res["score"]
+            else:
+                ref_status, want = res["align"].status, np.where(res["align"].status == 0, res["align"].score, 0)
             for leg in legs:  # the scores are compared in every step
-                if leg != "align":
-                    st, sc = res[leg]
-                    assert np.array_equal(st, ref.status) and np.array_equal(sc, want), (name, leg)
+                if leg != ("score" if args.device else "align"):
+                    st, sc = res[leg]() if callable(res[leg]) else res[leg]
+                    assert np.array_equal(st, ref_status) and np.array_equal(sc, want), (name, leg)
         out = {"config": name, "pairs": pairs, "steps": args.steps}
         for leg, v in legs.items():
             wall = float(np.median([x[0] for x in v]))

@@ -27,7 +27,7 @@ EXPORTS = [
     "wfahip_multi_ctx", "wfahip_align_batch_multi", "wfahip_debug_compact_arena",
     "wfahip_generate_pairs_device", "wfahip_align_pair", "wfahip_last_error", "wfahip_debug_clock",
     "wfahip_debug_team_compact", "wfahip_score_batch", "wfahip_scores_free", "wfahip_score_matrix",
-    "wfahip_debug_score_long_list",
+    "wfahip_debug_score_long_list", "wfahip_score_batch_device", "wfahip_debug_score_device_list",
 ]
 
 
@@ -93,6 +93,11 @@ def lib():
         L.wfahip_debug_score_long_list.restype = C.c_int
         L.wfahip_debug_score_long_list.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(C.POINTER(u32)), C.POINTER(u64),
                                                    C.POINTER(C.POINTER(u32)), C.POINTER(u64)]
+        L.wfahip_score_batch_device.restype = C.c_int
+        L.wfahip_score_batch_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, u32, vp, vp, vp]
+        L.wfahip_debug_score_device_list.restype = C.c_int
+        L.wfahip_debug_score_device_list.argtypes = [vp, C.POINTER(C.POINTER(u32)), C.POINTER(u64), C.POINTER(C.POINTER(u32)),
+                                                     C.POINTER(u64)]
         L.wfahip_align_batch_device.restype = C.c_int
         L.wfahip_align_batch_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, vp, vp,
                                                 u64, C.POINTER(u64), vp]

@@ -186,6 +186,7 @@ class Aligner:
         self.ad: Optional[AdaptiveReductionOption] = None
         self._ctx = C.c_void_p()
         self._one = None  # Align's reusable record / ops buffers
+        self._device = device if device >= 0 else None  # (None: the HIP runtime's current device when the context was created)
         L.check(L.lib().wfahip_create(device, C.byref(self._ctx)), "wfahip_create")
 
     # -- reference API ---------------------------------------------------------------------------
@@ -319,6 +320,74 @@ class Aligner:
         if st[0] != L.PAIR_OK:
             raise WfaError("pair could not be aligned (out of device memory)")
         return int(sc[0])
+
+    # -- new: score only on device-resident input (include/wfa_hip.h: wfahip_score_batch_device) ------
+    def score_tensors(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, out=None, stream=None):
+        """score_arrays for a batch that lives on the aligner's GPU: torch tensors in (blob uint8, q_off int64, q_len int32,
+        t_off int64, t_len int32 -- what generate_pairs_device returns), a pair of int32 tensors (status, score) on the same
+        device out.  `score` holds the C-ABI's uint32 bit for bit (torch has no unsigned 32-bit arithmetic: a score of 2^31 or
+        more reads negative; view it through numpy as uint32 if that can happen).  status and score equal what score_arrays
+        returns for the same bytes and max_score.  Nothing proportional to the batch crosses PCIe, and the inputs are never
+        written.  out: an optional pair of contiguous int32 tensors of at least n elements each on that device; elements
+        beyond n keep their contents.  stream: a torch.cuda.Stream, None = torch's current stream; the call returns when the
+        results are there.  Raises ValueError -- before the library is called -- for anything that is not a contiguous
+        tensor of the right dtype on the aligner's device, or for offset / length tensors of differing lengths.
+        (The buffers are torch's: torch.cuda must have been initialised before the first aligner of the process was created
+        -- torch ships its own HIP runtime, and it does not find the GPUs once the library's runtime has come up first.)"""
+        import torch
+        ins = (("blob", blob, torch.uint8), ("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32),
+               ("t_off", t_off, torch.int64), ("t_len", t_len, torch.int32))
+        dev = None
+
+        def want(name, t, dtype):
+            nonlocal dev
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor on the aligner's device, not {type(t).__name__}")
+            if not t.is_cuda:
+                raise ValueError(f"{name} is on the host: score_tensors takes tensors on the aligner's device (score_arrays takes host arrays)")
+            if self._device is not None and t.device.index != self._device:
+                raise ValueError(f"{name} is on {t.device}, the aligner on device {self._device}")
+            if dev is None:
+                dev = t.device
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, blob on {dev}")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+            if t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"{name} must be one-dimensional and contiguous")
+
+        for name, t, dtype in ins:
+            want(name, t, dtype)
+        n = int(q_len.numel())
+        if q_off.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors differ in length")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        if out is None:
+            status = torch.zeros(n, dtype=torch.int32, device=dev)
+            score = torch.zeros(n, dtype=torch.int32, device=dev)
+        else:
+            try:
+                status, score = out
+            except (TypeError, ValueError):
+                raise ValueError("out must be a pair (status, score) of tensors") from None
+            want("out status", status, torch.int32), want("out score", score, torch.int32)
+            if status.numel() < n or score.numel() < n:
+                raise ValueError(f"out tensors must hold at least {n} elements")
+        if n == 0:
+            return status, score
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        elif not isinstance(stream, torch.cuda.Stream):
+            raise ValueError("stream must be a torch.cuda.Stream")
+        if out is None:
+            stream.wait_stream(torch.cuda.current_stream(dev))  # (the fills above ran on torch's current stream)
+        prm = self._params()
+        rc = L.lib().wfahip_score_batch_device(self._ctx, C.byref(prm), blob.data_ptr(), blob.numel(), q_off.data_ptr(), q_len.data_ptr(),
+                                               t_off.data_ptr(), t_len.data_ptr(), n, 0, int(max_score), status.data_ptr(),
+                                               score.data_ptr(), stream.cuda_stream)
+        L.check(rc, "wfahip_score_batch_device" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return status, score
 
     # -- new: score matrix (include/wfa_hip.h: wfahip_score_matrix) ------------------------------------
     def score_matrix_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, out=None):

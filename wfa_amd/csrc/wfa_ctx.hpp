@@ -174,6 +174,8 @@ struct wfahip_ctx {
     DevBuf        score_out;                      // wfahip_score_batch: {status, score} per pair
     DevBuf        wide_ckpt;                      // wfa_wide_kernel: what its first launch hands its second, per pair of the chunk
     DevBuf        mx_seq, mx_words;               // wfahip_score_matrix: the call's sequence table (wfa_matrix.hpp)
+    DevBuf        sd_ctl, sd_blk, sd_list, sd_redo;  // wfahip_score_batch_device (wfa_score_dev.hpp): control words, tile sums, the long pairs, the pairs of the full path
+    uint64_t      sd_n_words = 0, sd_n_listed = 0;   // ... what its last call left in mx_words / mx_seq (wfahip_debug_score_device_list)
     DevBuf        mx_out;                         // ... {status, score} of two tiles (double-buffered: tile c downloads while tile c + 1 runs)
     uint2        *mx_pin       = nullptr;         // ... their page-locked host copies
     size_t        mx_pin_bytes = 0;

@@ -14,6 +14,7 @@
 #include "wfa_wide.hpp"
 #include "wfa_score.hpp"
 #include "wfa_score_long.hpp"
+#include "wfa_score_dev.hpp"
 
 using namespace wfa;
 
@@ -829,6 +830,7 @@ namespace wfa {
 hipError_t wfa_launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st);
 }  // namespace wfa
 
 // ---- the pairs of a score batch that wfa_score_long_kernel takes (wfa_score_long.hpp): global pairs with a read beyond wfa_score_kernel's
@@ -929,6 +931,63 @@ extern "C" void wfahip_scores_free(wfahip_scores *s) {
     s->status = nullptr, s->score = nullptr, s->n = 0;
 }
 
+// The launch section of a score batch, shared by wfahip_score_batch and wfahip_score_batch_device: P names the batch (device
+// pointers), score_out, the penalties and max_score.  LDS sizing from max_len, chunks of 2^24 (global) / 2^18 (semi-global: the wide
+// kernel's checkpoints take WIDE_CKPT_WORDS words per pair of a chunk) pairs, the wide kernel's two phases under wf-adaptive, and
+// the n_listed pairs of ctx->mx_seq / mx_words on wfa_score_long_kernel behind the short launch.  Records ctx->ev0 before the
+// first launch and ctx->ev1 behind the last; synchronises nothing.  n_long: the long pairs of the batch (listed or not).
+static int score_launch(wfahip_ctx *ctx, KParams &P, uint64_t n_pairs, uint32_t max_len, int shape, bool skip_short, uint64_t n_listed,
+                        uint64_t n_long, hipStream_t st, wfahip_timing &tm, bool &long_main) {
+    int            rc;
+    const bool     glob = P.global_alignment != 0u;
+    const uint32_t L = std::min<uint32_t>(max_len, glob ? SCORE_MAX_LEN : WIDE_MAX_LEN);  // (longer pairs come back ST_REDO_LDS)
+    const uint32_t seq_words = (L + 15) / 16 + 1;
+    P.lds_seq_words = seq_words;
+    // chunks: the wide kernel's checkpoints take WIDE_CKPT_WORDS words per pair of a chunk
+    const uint64_t chunk = glob ? (1ull << 24) : (1ull << 18);
+    const bool     two_phase = !glob && P.adaptive != 0u;
+    if (two_phase && (rc = ensure(ctx, ctx->wide_ckpt, (size_t)std::min<uint64_t>(chunk, n_pairs) * WIDE_CKPT_WORDS * 4))) return rc;
+    P.wide_ckpt = static_cast<uint32_t *>(ctx->wide_ckpt.p), P.wide_ckpt_on = two_phase ? 1u : 0u;
+    const size_t lds_g = (size_t)score_lds_words(seq_words) * 4;
+    const size_t lds_w = (size_t)wide_lds_words(seq_words, L) * 4, lds_n = (size_t)wide_lds_words_narrow(seq_words) * 4;
+    const int    waves = lds_w > 12 * 1024 ? 4 : 1;  // (as the full path: rings above 12 KB are shared by four waves)
+    P.sub_lds_words = wide_row_hw(L);
+    if (!ctx->ev0) HIP_TRY(hipEventCreate(&ctx->ev0));
+    if (!ctx->ev1) HIP_TRY(hipEventCreate(&ctx->ev1));
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    for (uint64_t c0 = 0; c0 < n_pairs && !skip_short; c0 += chunk) {
+        const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_pairs - c0);
+        P.chunk_first = (uint32_t)c0, P.chunk_n = cn;
+        if (glob) {
+            HIP_TRY(wfa_launch_score(P, cn, lds_g, st));
+        } else {
+            HIP_TRY(wfa_launch_wide_score(shape, 0, waves, P, cn, lds_w, st));
+            if (two_phase) {
+                HIP_TRY(wfa_launch_wide_score(shape, 1, 1, P, cn, lds_n, st));
+                tm.n_launches++;
+            }
+        }
+        tm.n_launches++, tm.n_main_launches++;
+    }
+    // the listed long pairs, behind wfa_score_kernel on the same stream: their slots (ST_REDO_LDS there) take the long kernel's result
+    long_main = n_listed > n_pairs - n_long;  // it took more pairs of the call than the short kernel
+    if (n_listed) {
+        KParams PL = P;
+        PL.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
+        PL.lds_seq_words = score_long_window(ctx->opt_score_long_window);
+        const size_t lds_l = (size_t)score_long_lds_words(PL.lds_seq_words) * 4;
+        for (uint64_t c0 = 0; c0 < n_listed; c0 += chunk) {
+            const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_listed - c0);
+            PL.mx_seq = static_cast<const uint4 *>(ctx->mx_seq.p) + 2 * c0, PL.chunk_first = 0u, PL.chunk_n = cn;
+            HIP_TRY(wfa_launch_score_long(false, PL, cn, lds_l, st));
+            tm.n_launches++;
+            if (long_main) tm.n_main_launches++;
+        }
+    }
+    HIP_TRY(hipEventRecord(ctx->ev1, st));
+    return WFAHIP_OK;
+}
+
 static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
                             const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
                             wfahip_scores *out) {
@@ -1014,51 +1073,8 @@ static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
         P.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), P.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p);
         P.score_out = static_cast<uint2 *>(ctx->score_out.p), P.max_score = max_score;
         P.dx = dx, P.doe = doe, P.de = de, P.census = 0u, P.wide_exact = 0u, P.work = nullptr;
-        const uint32_t L = std::min<uint32_t>(max_len, glob ? SCORE_MAX_LEN : WIDE_MAX_LEN);  // (longer pairs come back ST_REDO_LDS)
-        const uint32_t seq_words = (L + 15) / 16 + 1;
-        P.lds_seq_words = seq_words;
-        // chunks: the wide kernel's checkpoints take WIDE_CKPT_WORDS words per pair of a chunk
-        const uint64_t chunk = glob ? (1ull << 24) : (1ull << 18);
-        const bool     two_phase = !glob && P.adaptive != 0u;
-        if (two_phase && (rc = ensure(ctx, ctx->wide_ckpt, (size_t)std::min<uint64_t>(chunk, n_pairs) * WIDE_CKPT_WORDS * 4))) return rc;
-        P.wide_ckpt = static_cast<uint32_t *>(ctx->wide_ckpt.p), P.wide_ckpt_on = two_phase ? 1u : 0u;
-        const size_t lds_g = (size_t)score_lds_words(seq_words) * 4;
-        const size_t lds_w = (size_t)wide_lds_words(seq_words, L) * 4, lds_n = (size_t)wide_lds_words_narrow(seq_words) * 4;
-        const int    waves = lds_w > 12 * 1024 ? 4 : 1;  // (as the full path: rings above 12 KB are shared by four waves)
-        P.sub_lds_words = wide_row_hw(L);
-        if (!ctx->ev0) HIP_TRY(hipEventCreate(&ctx->ev0));
-        if (!ctx->ev1) HIP_TRY(hipEventCreate(&ctx->ev1));
-        HIP_TRY(hipEventRecord(ctx->ev0, st));
-        for (uint64_t c0 = 0; c0 < n_pairs && !skip_short; c0 += chunk) {
-            const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_pairs - c0);
-            P.chunk_first = (uint32_t)c0, P.chunk_n = cn;
-            if (glob) {
-                HIP_TRY(wfa_launch_score(P, cn, lds_g, st));
-            } else {
-                HIP_TRY(wfa_launch_wide_score(shape, 0, waves, P, cn, lds_w, st));
-                if (two_phase) {
-                    HIP_TRY(wfa_launch_wide_score(shape, 1, 1, P, cn, lds_n, st));
-                    tm.n_launches++;
-                }
-            }
-            tm.n_launches++, tm.n_main_launches++;
-        }
-        // the listed long pairs, behind wfa_score_kernel on the same stream: their slots (ST_REDO_LDS there) take the long kernel's result
-        const bool long_main = n_listed > n_pairs - lp.ids.size();  // it took more pairs of the call than the short kernel
-        if (n_listed) {
-            KParams PL = P;
-            PL.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
-            PL.lds_seq_words = score_long_window(ctx->opt_score_long_window);
-            const size_t lds_l = (size_t)score_long_lds_words(PL.lds_seq_words) * 4;
-            for (uint64_t c0 = 0; c0 < n_listed; c0 += chunk) {
-                const uint32_t cn = (uint32_t)std::min<uint64_t>(chunk, n_listed - c0);
-                PL.mx_seq = static_cast<const uint4 *>(ctx->mx_seq.p) + 2 * c0, PL.chunk_first = 0u, PL.chunk_n = cn;
-                HIP_TRY(wfa_launch_score_long(false, PL, cn, lds_l, st));
-                tm.n_launches++;
-                if (long_main) tm.n_main_launches++;
-            }
-        }
-        HIP_TRY(hipEventRecord(ctx->ev1, st));
+        bool long_main = false;
+        if ((rc = score_launch(ctx, P, n_pairs, max_len, shape, skip_short, n_listed, lp.ids.size(), st, tm, long_main))) return rc;
         HIP_TRY(hipMemcpyAsync(res.data(), ctx->score_out.p, n_pairs * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         float ms = 0;
@@ -1107,6 +1123,194 @@ extern "C" int wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const
                                   const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
                                   wfahip_scores *out) {
     WFAHIP_GUARD(score_batch_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, max_score, out))
+}
+
+// ---- score only on device-resident input (wfahip_score_batch_device): score_batch_impl with everything it does on the host done by
+// the kernels of wfa_score_dev.hpp.  The host sees three blocks of SDC_WORDS counters -- after the plan (bounds flag, longest
+// length, long pairs, their words), after the list (listed pairs) when long pairs run, after the redo count (pairs of the full path,
+// their bases, their longest length) -- and nothing else of the batch.
+namespace {
+constexpr uint64_t SD_FB_PAIRS = 1ull << 20;  // pairs per call of the full path: 64 MB of records
+}
+
+static int score_batch_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_blob, uint64_t blob_bytes, const void *d_q_off,
+                                   const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n_pairs, uint32_t max_len,
+                                   uint32_t max_score, void *d_status, void *d_score, hipStream_t st) {
+    if (!ctx || !p) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs && (!d_q_off || !d_q_len || !d_t_off || !d_t_len || !d_status || !d_score || (!d_blob && blob_bytes))) return WFAHIP_ERR_BAD_ARG;
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_pairs == 0) return WFAHIP_OK;
+    if (n_pairs > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit: pair indices are 32-bit on the device)
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    const auto    t_start = std::chrono::steady_clock::now();
+    wfahip_timing tm{};
+    ctx->sd_n_words = ctx->sd_n_listed = 0;
+
+    KParams P{};
+    P.x = p->mismatch, P.o = p->gap_open, P.e = p->gap_ext, P.oe = p->gap_open + p->gap_ext;
+    P.g = gcd_u32(gcd_u32(P.x, P.oe), P.e);
+    P.global_alignment = p->global_alignment ? 1u : 0u, P.adaptive = p->adaptive ? 1u : 0u;
+    P.min_wf_len = p->min_wf_len, P.max_dist_diff = p->max_dist_diff;
+    const uint32_t dx = P.x / P.g, doe = P.oe / P.g, de = P.e / P.g;
+    const bool     glob  = P.global_alignment != 0u;
+    const int      shape = fwd_shape(dx, doe, de);
+    const bool     on_kernel = glob ? score_shape_ok(dx, doe, de) : shape >= 0;
+
+    const uint64_t n_tiles = (n_pairs + SD_TILE - 1) / SD_TILE;
+    if ((rc = ensure(ctx, ctx->sd_ctl, SDC_WORDS * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->sd_blk, n_tiles * sizeof(SDSum)))) return rc;
+    SDParams S{};
+    S.blob = static_cast<const uint8_t *>(d_blob), S.blob_bytes = blob_bytes;
+    S.q_off = static_cast<const uint64_t *>(d_q_off), S.t_off = static_cast<const uint64_t *>(d_t_off);
+    S.q_len = static_cast<const uint32_t *>(d_q_len), S.t_len = static_cast<const uint32_t *>(d_t_len);
+    S.ctl = static_cast<unsigned long long *>(ctx->sd_ctl.p), S.blk = static_cast<SDSum *>(ctx->sd_blk.p);
+    S.d_status = static_cast<int32_t *>(d_status), S.d_score = static_cast<uint32_t *>(d_score), S.max_score = max_score;
+    // a selection's count launch over `items` items and the scan of its tile sums into control words c_cnt / c_wt
+    const auto count_and_scan = [&](int k, uint64_t items, uint32_t c_cnt, uint32_t c_wt) -> int {
+        const uint64_t tiles = (items + SD_TILE - 1) / SD_TILE;
+        SDParams       T = S;
+        T.n = items;
+        HIP_TRY(wfa_launch_score_dev(k, T, (uint32_t)tiles, st));
+        T.n = tiles, T.c_cnt = c_cnt, T.c_wt = c_wt;
+        HIP_TRY(wfa_launch_score_dev(SDK_SCAN, T, 1, st));
+        return WFAHIP_OK;
+    };
+    const auto launch = [&](int k, uint64_t items, uint64_t per_group) -> int {
+        SDParams T = S;
+        T.n = items;
+        HIP_TRY(wfa_launch_score_dev(k, T, (uint32_t)((items + per_group - 1) / per_group), st));
+        return WFAHIP_OK;
+    };
+    uint64_t   hc[SDC_WORDS];
+    const auto fetch_ctl = [&]() -> int {  // (through the context's pinned block: a pageable copy of 64 bytes costs 0.3 ms)
+        HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, S.ctl, SDC_WORDS * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(hc, ctx->hpin + HPIN_CTRL, SDC_WORDS * 8);
+        return WFAHIP_OK;
+    };
+    static_assert(SDC_WORDS * 8 <= HPIN_REDO * 4, "the control words fit the head of the pinned block");
+
+    // ---- plan: bounds, the longest length, the long pairs.  No kernel that reads a sequence byte runs before its verdict is in
+    HIP_TRY(hipMemsetAsync(S.ctl, 0, SDC_WORDS * 8, st));
+    S.want_long = (on_kernel && glob) ? 1u : 0u;
+    if ((rc = count_and_scan(SDK_PLAN_COUNT, n_pairs, SDC_N_LONG, SDC_N_WORDS))) return rc;
+    if ((rc = fetch_ctl())) return rc;
+    if (hc[SDC_BOUNDS] != 0) return WFAHIP_ERR_BAD_ARG;
+    if (max_len == 0) max_len = (uint32_t)std::max<uint64_t>(1, hc[SDC_MAX_LEN]);
+    const uint64_t n_long = hc[SDC_N_LONG], n_words = hc[SDC_N_WORDS];
+    const bool     use_long = n_long != 0 && (int64_t)n_long >= ctx->opt_score_long_min;
+    uint64_t       n_listed = 0;
+    if (on_kernel && (rc = ensure(ctx, ctx->score_out, n_pairs * 8))) return rc;
+    S.score_out = static_cast<uint2 *>(ctx->score_out.p);
+    if (use_long) {
+        // ---- the long pairs: listed (plan, write launch), packed from the caller's blob, and those without a byte outside ACGT tabled
+        if ((rc = ensure(ctx, ctx->sd_list, n_long * 24))) return rc;
+        if ((rc = ensure(ctx, ctx->mx_seq, n_long * 32))) return rc;
+        if ((rc = ensure(ctx, ctx->mx_words, (size_t)(n_words + 4) * 4))) return rc;
+        S.l_qw = static_cast<uint64_t *>(ctx->sd_list.p), S.l_tw = S.l_qw + n_long;
+        S.l_id = reinterpret_cast<uint32_t *>(S.l_tw + n_long), S.l_bad = S.l_id + n_long;
+        S.words = static_cast<uint32_t *>(ctx->mx_words.p), S.table = static_cast<uint4 *>(ctx->mx_seq.p);
+        if ((rc = launch(SDK_PLAN_WRITE, n_pairs, SD_TILE))) return rc;
+        {
+            SDParams T = S;
+            T.n = n_long;
+            HIP_TRY(wfa_launch_score_dev(SDK_PACK, T, (uint32_t)std::min<uint64_t>(2 * n_long, 1u << 20), st));
+        }
+        if ((rc = count_and_scan(SDK_LIST_COUNT, n_long, SDC_N_LISTED, SDC_N_REDO))) return rc;  // (no weights: the second total is 0)
+        if ((rc = launch(SDK_LIST_WRITE, n_long, SD_TILE))) return rc;
+        if ((rc = fetch_ctl())) return rc;
+        n_listed = hc[SDC_N_LISTED];
+        ctx->sd_n_words = n_words, ctx->sd_n_listed = n_listed;
+    }
+    // ---- the score kernels, as wfahip_score_batch launches them
+    if (on_kernel) {
+        const bool skip_short = use_long && n_long == n_pairs;
+        P.blob = S.blob, P.blob_bytes = blob_bytes, P.q_off = S.q_off, P.t_off = S.t_off, P.q_len = S.q_len, P.t_len = S.t_len;
+        P.score_out = S.score_out, P.max_score = max_score;
+        P.dx = dx, P.doe = doe, P.de = de, P.census = 0u, P.wide_exact = 0u, P.work = nullptr;
+        bool long_main = false;
+        if ((rc = score_launch(ctx, P, n_pairs, max_len, shape, skip_short, n_listed, use_long ? n_long : 0, st, tm, long_main))) return rc;
+        tm.main_kernel_kind = glob ? (long_main ? 23u : 19u) : 20u;
+    }
+    // ---- what they handed back (every pair, for a shape without an instance): counted, then gathered in pair order
+    S.all = on_kernel ? 0u : 1u;
+    if ((rc = count_and_scan(SDK_REDO_COUNT, n_pairs, SDC_N_REDO, SDC_REDO_SUM))) return rc;
+    if (on_kernel && (rc = launch(SDK_FINISH, n_pairs, SD_BLOCK))) return rc;
+    if ((rc = fetch_ctl())) return rc;
+    if (on_kernel) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        tm.kernel_ms = tm.main_kernel_ms = ms;
+    }
+    const uint64_t n_redo = hc[SDC_N_REDO], sum_len = hc[SDC_REDO_SUM];
+    const uint32_t fb_max = (uint32_t)std::max<uint64_t>(1, hc[SDC_REDO_MAX]);
+    if (n_redo) {
+        if ((rc = ensure(ctx, ctx->sd_redo, n_redo * 28))) return rc;
+        S.r_qoff = static_cast<uint64_t *>(ctx->sd_redo.p), S.r_toff = S.r_qoff + n_redo;
+        S.r_id = reinterpret_cast<uint32_t *>(S.r_toff + n_redo), S.r_qlen = S.r_id + n_redo, S.r_tlen = S.r_qlen + n_redo;
+        if ((rc = launch(SDK_REDO_WRITE, n_pairs, SD_TILE))) return rc;
+        for (uint64_t a = 0; a < n_redo; a += SD_FB_PAIRS) {
+            const uint64_t nb = std::min(SD_FB_PAIRS, n_redo - a);
+            if ((rc = ensure(ctx, ctx->out_rec, nb * REC_WORDS * 4))) return rc;
+            // CIGAR ops are merged runs: the host entry's first guess, (n+m)/4 + 8 per pair, run again once with what was needed
+            uint64_t ops_cap = std::min<uint64_t>(sum_len, 2ull * fb_max * nb) / 4 + 8 * nb + 1024;
+            for (int attempt = 0;; attempt++) {
+                if ((rc = ensure(ctx, ctx->out_ops, ops_cap * 8))) return rc;
+                uint64_t needed = 0;
+                rc = align_device(ctx, p, d_blob, blob_bytes, S.r_qoff + a, S.r_qlen + a, S.r_toff + a, S.r_tlen + a, nb, fb_max, ctx->out_rec.p,
+                                  ctx->out_ops.p, ops_cap, &needed, st, false);
+                if (rc == WFAHIP_ERR_OOM && needed > ops_cap && attempt == 0) {
+                    ops_cap = needed;
+                    continue;
+                }
+                break;
+            }
+            if (rc) return rc;
+            const wfahip_timing &f = ctx->timing;
+            tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = std::max(tm.arena_bytes, f.arena_bytes);
+            if (!on_kernel && a == 0) tm.main_kernel_ms = f.main_kernel_ms, tm.n_main_launches = f.n_main_launches, tm.main_kernel_kind = f.main_kernel_kind;
+            SDParams T = S;
+            T.n = nb, T.first = a, T.rec = static_cast<const uint32_t *>(ctx->out_rec.p);
+            HIP_TRY(wfa_launch_score_dev(SDK_FINISH, T, (uint32_t)((nb + SD_BLOCK - 1) / SD_BLOCK), st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    tm.n_retried_pairs = (uint32_t)std::min<uint64_t>(n_redo, UINT32_MAX);
+    tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    ctx->timing = tm;
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_score_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_seq_blob, uint64_t blob_bytes,
+                                         const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len,
+                                         uint64_t n_pairs, uint32_t max_len, uint32_t max_score, void *d_status, void *d_score, void *stream) {
+    WFAHIP_GUARD(score_batch_device_impl(ctx, p, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs, max_len, max_score, d_status,
+                                         d_score, static_cast<hipStream_t>(stream)))
+}
+
+// Debug / test aid: the packed words and the table the last wfahip_score_batch_device call on ctx handed wfa_score_long_kernel
+// (include/wfa_hip.h), copied to the host
+extern "C" int wfahip_debug_score_device_list(wfahip_ctx *ctx, uint32_t **words, uint64_t *n_words, uint32_t **table, uint64_t *n_listed) {
+    if (!ctx || !words || !n_words || !table || !n_listed) return WFAHIP_ERR_BAD_ARG;
+    *words = *table = nullptr, *n_words = *n_listed = 0;
+    const uint64_t nw = ctx->sd_n_words, nl = ctx->sd_n_listed;
+    if (nw == 0) return WFAHIP_OK;
+    if (ctx->mx_words.bytes < nw * 4 || ctx->mx_seq.bytes < nl * 32) return WFAHIP_ERR_INTERNAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    uint32_t *const w = static_cast<uint32_t *>(std::malloc((size_t)nw * 4 + 4)), *const t = static_cast<uint32_t *>(std::malloc((size_t)nl * 32 + 16));
+    if (!w || !t) {
+        std::free(w), std::free(t);
+        return WFAHIP_ERR_OOM;
+    }
+    if (hipMemcpy(w, ctx->mx_words.p, (size_t)nw * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        (nl && hipMemcpy(t, ctx->mx_seq.p, (size_t)nl * 32, hipMemcpyDeviceToHost) != hipSuccess)) {
+        std::free(w), std::free(t);
+        return WFAHIP_ERR_HIP;
+    }
+    *words = w, *n_words = nw, *table = t, *n_listed = nl;
+    return WFAHIP_OK;
 }
 
 // ---- score matrix (wfahip_score_matrix): every query against every target, score only.  The n_q + n_t sequences are packed and

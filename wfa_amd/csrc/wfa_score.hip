@@ -1,12 +1,13 @@
 // wfa_score.hip -- translation unit of the score-only kernels behind wfahip_score_batch: wfa_score_kernel (global pairs, any
 // penalty shape score_shape_ok() takes; wfa_score_long_kernel for reads beyond its 2 047 bases) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
-// wfa_fwd_shape.inc), and their matrix instances behind wfahip_score_matrix.  The routers are wfa_entry.hip (score_batch_impl,
-// score_matrix_impl).
+// wfa_fwd_shape.inc), and their matrix instances behind wfahip_score_matrix; and the routing kernels of wfahip_score_batch_device
+// (wfa_score_dev.hpp).  The routers are wfa_entry.hip (score_batch_impl, score_batch_device_impl, score_matrix_impl).
 #define WFA_NO_AUX_KERNELS 1
 #define WFA_SCORE_UNIT 1
 #include "wfa_wide.hpp"
 #include "wfa_score.hpp"
 #include "wfa_score_long.hpp"
+#include "wfa_score_dev.hpp"
 
 namespace wfa {
 
@@ -66,6 +67,24 @@ hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams 
 hipError_t wfa_launch_score_matrix(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) { return launch_score<true>(P, grid, lds_bytes, st); }
 hipError_t wfa_launch_wide_score_matrix(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     return launch_wide_score<true>(shape, phase, waves, P, grid, lds_bytes, st);
+}
+
+// the routing kernels of wfahip_score_batch_device (wfa_score_dev.hpp): kernel `k` (SDK_*) over `grid` workgroups of SD_BLOCK threads
+hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st) {
+    const dim3 g(grid), b(SD_BLOCK);
+    switch (k) {
+    case SDK_PLAN_COUNT: hipLaunchKernelGGL(wfa_score_plan_kernel<false>, g, b, 0, st, S); break;
+    case SDK_PLAN_WRITE: hipLaunchKernelGGL(wfa_score_plan_kernel<true>, g, b, 0, st, S); break;
+    case SDK_SCAN: hipLaunchKernelGGL(wfa_score_scan_kernel, dim3(1), b, 0, st, S); break;
+    case SDK_PACK: hipLaunchKernelGGL(wfa_score_pack_kernel, g, b, 0, st, S); break;
+    case SDK_LIST_COUNT: hipLaunchKernelGGL(wfa_score_list_kernel<false>, g, b, 0, st, S); break;
+    case SDK_LIST_WRITE: hipLaunchKernelGGL(wfa_score_list_kernel<true>, g, b, 0, st, S); break;
+    case SDK_REDO_COUNT: hipLaunchKernelGGL(wfa_score_redo_kernel<false>, g, b, 0, st, S); break;
+    case SDK_REDO_WRITE: hipLaunchKernelGGL(wfa_score_redo_kernel<true>, g, b, 0, st, S); break;
+    case SDK_FINISH: hipLaunchKernelGGL(wfa_score_finish_kernel, g, b, 0, st, S); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 }  // namespace wfa
