@@ -92,6 +92,16 @@ def test_matrix_kernels_do_the_work(glob, adaptive):
     assert t.main_kernel_kind == (21 if glob else 22) and t.n_retried_pairs == 0 and t.arena_bytes == 0
     wst, wsc = _want_batch(al, seqs[:17], seqs[17:])
     assert np.array_equal(st, wst) and np.array_equal(sc, wsc)
+    if adaptive is not None:
+        # launch accounting: 8 x 8 sequences of 1 kbp in tiles of 16 cells are four tiles -- a launch each on wfa_score_kernel, two on
+        # the wide kernel under wf-adaptive (its two phases count as one main launch)
+        kbp = _families(16, 1, 16, 1000, 0.05)
+        al.set_option("matrix_tile_cells", 16)
+        al.ScoreMatrix(kbp[:8], kbp[8:])
+        t = al.last_timing()
+        print("launches", glob, "retried", t.n_retried_pairs, (t.main_kernel_kind, t.n_launches, t.n_main_launches))
+        assert t.n_retried_pairs == 0
+        assert (t.main_kernel_kind, t.n_launches, t.n_main_launches) == ((21, 4, 4) if glob else (22, 8, 4))
 
 
 @pytest.mark.parametrize("glob", [True, False])

@@ -148,3 +148,26 @@ def test_score_kernels_do_the_work():
         al.score_arrays(*short)
         t = al.last_timing()
         assert (t.main_kernel_kind, t.n_retried_pairs, t.arena_bytes) == (kind, 0, 0)
+    # launch accounting, (main_kernel_kind, n_launches, n_main_launches) of a call none of whose pairs is handed back: one launch per
+    # chunk (wfa_score_kernel, or the wide kernel without wf-adaptive), two under wf-adaptive on the wide kernel (its two phases
+    # count as one main launch), one more for the listed long pairs -- the main one where they are most of the call
+    import torch
+    kbp = wfa_amd.generate_pairs(seed=21, n_pairs=64, length=1000, error_rate=0.05)
+    lng = wfa_amd.generate_pairs(seed=22, n_pairs=64, length=2100, error_rate=0.05)
+    shift = np.uint64(kbp[0].size)  # the long pairs' blob behind the short pairs'
+    both = (np.concatenate([kbp[0], lng[0]]), np.concatenate([kbp[1], lng[1] + shift]), np.concatenate([kbp[2], lng[2]]),
+            np.concatenate([kbp[3], lng[3] + shift]), np.concatenate([kbp[4], lng[4]]))
+    dev = [torch.from_numpy(a).to("cuda:0") for a in (np.concatenate([kbp[0], np.zeros(64, np.uint8)]), kbp[1].view(np.int64),
+                                                       kbp[2].view(np.int32), kbp[3].view(np.int64), kbp[4].view(np.int32))]
+    for glob, adaptive, arrays, want in ((True, (10, 50, 1), kbp, (19, 1, 1)), (False, (10, 50, 1), kbp, (20, 2, 1)), (False, None, kbp, (20, 1, 1)),
+                                         (True, (10, 50, 1), both, (19, 2, 1)), (True, (10, 50, 1), lng, (23, 1, 1)),
+                                         (True, (10, 50, 1), dev, (19, 1, 1)), (False, (10, 50, 1), dev, (20, 2, 1))):
+        al = _aligner(glob, adaptive)
+        if arrays is dev:
+            al.score_tensors(*dev)
+        else:
+            al.score_arrays(*arrays)
+        t = al.last_timing()
+        print("launches", glob, adaptive, len(arrays[2]), "retried", t.n_retried_pairs, (t.main_kernel_kind, t.n_launches, t.n_main_launches))
+        assert t.n_retried_pairs == 0
+        assert (t.main_kernel_kind, t.n_launches, t.n_main_launches) == want

@@ -4,6 +4,8 @@
 //                  long-pair ladder behind it (align_device)
 //   wfa_entry.hip  the host entries: wfahip_align_batch (sliced upload / alignment / download), packed input,
 //                  wfahip_align_pair, submit / collect, the results cache
+//   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_device, wfahip_score_matrix -- a
+//                  router each over the launch section, the geometry and the full-path fallback they share
 //   wfa_debug.hip  parity and measurement aids: wavefront dumps, the compact arenas, the device-side generator, the clock probe
 #pragma once
 #include "../../include/wfa_hip.h"
@@ -277,6 +279,31 @@ inline uint32_t gcd_u32(uint32_t a, uint32_t b) {
     return a;
 }
 
+// the penalties and the alignment mode of a call, as every forward kernel reads them (P.g: what the three penalties share)
+inline void set_penalties(wfa::KParams &P, const wfahip_params *p) {
+    P.x = p->mismatch, P.o = p->gap_open, P.e = p->gap_ext, P.oe = p->gap_open + p->gap_ext;
+    P.g = gcd_u32(gcd_u32(P.x, P.oe), P.e);
+    P.global_alignment = p->global_alignment ? 1u : 0u, P.adaptive = p->adaptive ? 1u : 0u;
+    P.min_wf_len = p->min_wf_len, P.max_dist_diff = p->max_dist_diff;
+}
+
+// A page-locked host buffer of a context (ptr, `have` bytes) grown to `need` bytes plus `slack`, its contents dropped.  Where
+// no page-locked memory is to be had: the error, cleared from the runtime, and ptr == nullptr -- the caller decides what that means.
+template <class T>
+inline hipError_t grow_pinned(T *&ptr, size_t &have, size_t need, size_t slack) {
+    if (have >= need) return hipSuccess;
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr, have = 0;
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ptr), need + slack, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ptr = nullptr;
+        return e;
+    }
+    have = need + slack;
+    return hipSuccess;
+}
+
 inline int check_params(const wfahip_params *p) {
     if (!p) return WFAHIP_ERR_BAD_ARG;
     // Mismatch == 0: the reference's own loop does not terminate when the first bases differ (the seed is then a
@@ -293,6 +320,9 @@ constexpr size_t LDS_MAX_BYTES = 160 * 1024;
 void results_zero(wfahip_results *r);
 // records + ops of n pairs (as the kernels leave them) -> the malloc'd arrays of a wfahip_results
 int unpack_results(const std::vector<uint32_t> &rec, const std::vector<uint64_t> &ops, uint64_t n, wfahip_results *out, uint64_t *cells_total);
+// wfahip_align_batch behind its guard: the full path the score entries send the pairs their kernels hand back through
+int align_batch_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                      const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
 
 // ---- defined in wfa_host.hip
 // the device-resident core behind every entry (exception-safe: the host entry calls it while its upload / download threads are joinable)
@@ -302,3 +332,11 @@ int align_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_blob, ui
 // one workgroup of wfa_backtrace_kernel behind a lone-pair forward launch (wfahip_align_pair)
 hipError_t wfa_launch_backtrace_one(const wfa::KParams &P, hipStream_t st);
 
+// ---- defined in wfa_score.hip: the launches of the score-only kernels (matrix: the instances that take the cells of a tile)
+namespace wfa {
+struct SDParams;
+hipError_t wfa_launch_score(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_wide_score(bool matrix, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st);
+}  // namespace wfa

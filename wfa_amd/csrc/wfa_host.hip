@@ -613,10 +613,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
     P.ops_cursor = reinterpret_cast<unsigned long long *>(d_ctrl + 2);
     P.debug_info = debug_single ? d_ctrl + 4 : nullptr;
     P.redo_list  = static_cast<uint32_t *>(ctx->redo.p);
-    P.x = p->mismatch, P.o = p->gap_open, P.e = p->gap_ext, P.oe = p->gap_open + p->gap_ext;
-    P.g                = gcd_u32(gcd_u32(P.x, P.oe), P.e);
-    P.global_alignment = p->global_alignment ? 1 : 0;
-    P.adaptive = p->adaptive ? 1 : 0, P.min_wf_len = p->min_wf_len, P.max_dist_diff = p->max_dist_diff;
+    set_penalties(P, p);
     P.census = ctx->opt_census ? 1u : 0u;
     P.rec = static_cast<uint32_t *>(d_rec);
     P.ops = static_cast<uint64_t *>(d_ops), P.ops_cap = ops_cap;

@@ -1,7 +1,8 @@
 // wfa_score.hip -- translation unit of the score-only kernels behind wfahip_score_batch: wfa_score_kernel (global pairs, any
 // penalty shape score_shape_ok() takes; wfa_score_long_kernel for reads beyond its 2 047 bases) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
 // wfa_fwd_shape.inc), and their matrix instances behind wfahip_score_matrix; and the routing kernels of wfahip_score_batch_device
-// (wfa_score_dev.hpp).  The routers are wfa_entry.hip (score_batch_impl, score_batch_device_impl, score_matrix_impl).
+// (wfa_score_dev.hpp).  The routers are wfa_score_entry.hip (score_batch_impl, score_batch_device_impl, score_matrix_impl); the
+// launches below are declared for them in wfa_ctx.hpp.
 #define WFA_NO_AUX_KERNELS 1
 #define WFA_SCORE_UNIT 1
 #include "wfa_wide.hpp"
@@ -60,13 +61,17 @@ static hipError_t launch_wide_score(int shape, int phase, int waves, const KPara
     return hipErrorInvalidValue;
 }
 
-hipError_t wfa_launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) { return launch_score<false>(P, grid, lds_bytes, st); }
-hipError_t wfa_launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
-    return launch_wide_score<false>(shape, phase, waves, P, grid, lds_bytes, st);
+// (instantiated in this order, so that the kernels keep their places in the code object: the batch instances, then the matrix ones)
+template hipError_t launch_score<false>(const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_wide_score<false>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_score<true>(const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_wide_score<true>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
+
+hipError_t wfa_launch_score(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    return !matrix ? launch_score<false>(P, grid, lds_bytes, st) : launch_score<true>(P, grid, lds_bytes, st);
 }
-hipError_t wfa_launch_score_matrix(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) { return launch_score<true>(P, grid, lds_bytes, st); }
-hipError_t wfa_launch_wide_score_matrix(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
-    return launch_wide_score<true>(shape, phase, waves, P, grid, lds_bytes, st);
+hipError_t wfa_launch_wide_score(bool matrix, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    return !matrix ? launch_wide_score<false>(shape, phase, waves, P, grid, lds_bytes, st) : launch_wide_score<true>(shape, phase, waves, P, grid, lds_bytes, st);
 }
 
 // the routing kernels of wfahip_score_batch_device (wfa_score_dev.hpp): kernel `k` (SDK_*) over `grid` workgroups of SD_BLOCK threads
