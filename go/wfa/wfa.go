@@ -74,7 +74,11 @@ const (
 	pairOK        = uint32(C.WFAHIP_PAIR_OK)
 	pairEmpty     = uint32(C.WFAHIP_PAIR_EMPTY)
 	pairTooLong   = uint32(C.WFAHIP_PAIR_TOO_LONG)
+	pairOverMax   = uint32(C.WFAHIP_PAIR_OVER_MAX)
 )
+
+// ErrOverMaxScore is the error of a pair whose score exceeds the bound given to AlignBatchBounded.
+var ErrOverMaxScore error = fmt.Errorf("wfa: alignment score exceeds max_score")
 
 var ErrSeqTooLong error = fmt.Errorf("wfa: sequences longer than %d are not supported", MaxSeqLen)
 
@@ -218,6 +222,13 @@ func (algn *Aligner) AlignPointers(q, t *[]byte) (*AlignmentResult, error) {
 // Sequences are copied into one flat blob: C never sees Go pointers inside Go memory (cgo pointer rules) and
 // keeps nothing after the call returns.
 func (algn *Aligner) AlignBatch(qs, ts [][]byte) ([]*AlignmentResult, []error) {
+	return algn.AlignBatchBounded(qs, ts, 0)
+}
+
+// AlignBatchBounded is AlignBatch under a score bound (wfahip_align_batch_bounded): a pair whose score exceeds maxScore
+// stops early, has no result and ErrOverMaxScore; the pairs within the bound come back as from AlignBatch.  maxScore == 0:
+// no bound.  One GPU: an Aligner over several GPUs reports an error for every pair.
+func (algn *Aligner) AlignBatchBounded(qs, ts [][]byte, maxScore uint32) ([]*AlignmentResult, []error) {
 	n := len(qs)
 	results := make([]*AlignmentResult, n)
 	errs := make([]error, n)
@@ -243,7 +254,12 @@ func (algn *Aligner) AlignBatch(qs, ts [][]byte) ([]*AlignmentResult, []error) {
 	p := algn.params()
 	var out C.wfahip_results
 	var rc C.int
-	if algn.multi != nil { // a context set over several GPUs: contiguous shards, one host thread per GPU inside the library
+	if algn.multi != nil && maxScore != 0 {
+		rc = C.int(C.WFAHIP_ERR_UNSUPPORTED)
+	} else if maxScore != 0 {
+		rc = C.wfahip_align_batch_bounded(algn.ctx, &p, (*C.uint8_t)(unsafe.Pointer(&blob[0])), C.uint64_t(len(blob)),
+			&qOff[0], &qLen[0], &tOff[0], &tLen[0], C.uint64_t(n), C.uint32_t(maxScore), &out)
+	} else if algn.multi != nil { // a context set over several GPUs: contiguous shards, one host thread per GPU inside the library
 		rc = C.wfahip_align_batch_multi(algn.multi, &p, (*C.uint8_t)(unsafe.Pointer(&blob[0])), C.uint64_t(len(blob)),
 			&qOff[0], &qLen[0], &tOff[0], &tLen[0], C.uint64_t(n), &out)
 	} else {
@@ -296,6 +312,8 @@ func (algn *Aligner) unpack(rc C.int, out *C.wfahip_results, n int) ([]*Alignmen
 			errs[i] = ErrEmptySeq
 		case pairTooLong:
 			errs[i] = ErrSeqTooLong
+		case pairOverMax:
+			errs[i] = ErrOverMaxScore
 		default:
 			errs[i] = fmt.Errorf("wfa: out of device memory for this pair")
 		}

@@ -62,7 +62,7 @@ enum {
     WFAHIP_PAIR_EMPTY     = 1, /* ErrEmptySeq,   wfa.go:204-206 */
     WFAHIP_PAIR_TOO_LONG  = 2, /* ErrSeqTooLong, wfa.go:207-209 */
     WFAHIP_PAIR_NO_MEMORY = 4, /* wavefront arena could not be grown enough for this pair */
-    WFAHIP_PAIR_OVER_MAX  = 8  /* wfahip_score_batch only: the pair's score exceeds max_score */
+    WFAHIP_PAIR_OVER_MAX  = 8  /* the entries that take a max_score (score entries, wfahip_align_batch_bounded): the pair's score exceeds it */
 };
 
 /* wfa.go:190 MaxSeqLen */
@@ -227,6 +227,34 @@ int  wfahip_align_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const vo
                                const void *d_t_off, const void *d_t_len, uint64_t n_pairs,
                                uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap,
                                uint64_t *ops_needed, void *stream);
+
+/* Full alignment under a score bound: CIGARs for the pairs that pass a threshold, an early stop for the others.  Arguments,
+ * ownership and whole-call errors are those of wfahip_align_batch / wfahip_align_batch_device.
+ *   max_score == 0    no bound: the result equals the unbounded entry's in every field.
+ *   score <= max_score  a pair the unbounded entry reports as WFAHIP_PAIR_OK with such a score comes back identical, every field
+ *                     and every CIGAR op.
+ *   score > max_score   status WFAHIP_PAIR_OVER_MAX, every other field 0, ops_len and ops_off 0 (device: the record is {8, 0, .., 0}).
+ * WFAHIP_PAIR_EMPTY and _TOO_LONG are unchanged.  A pair the unbounded entry reports as WFAHIP_PAIR_NO_MEMORY may come back
+ * WFAHIP_PAIR_OVER_MAX (it stops earlier), never the reverse.  For every pair, status and score equal what
+ * wfahip_score_batch(.., max_score) returns -- the exact definition of "over" given there -- global or semi-global, wf-adaptive
+ * on or off, any penalties, any bytes.
+ * Where the bound STOPS a pair: the sub-wave forward kernels with row-indexed arenas (main_kernel_kind 3..6, 8..15) get arena
+ * slots of max_score / g + 1 rows (g = gcd of the penalties) instead of rows for half the read length -- a pair that runs out
+ * of them is over and final, it visits no retry rung and grows no arena; and wfa_generic_kernel ends a global pair when its
+ * score step passes the bound.  Where it only FILTERS, after the alignment is done: semi-global pairs, the team kernels, the
+ * two first-generation sub-wave kernels (kinds 1, 2).
+ * Host entry: out->ops is dense in pair order, as from wfahip_align_batch.  Device entry: d_ops may hold unreferenced ops of
+ * pairs that were filtered after their backtrace, and *ops_needed counts them.  wfahip_last_timing as after the unbounded
+ * entries; pairs finalised as over by a pass do not count in n_retried_pairs. */
+int  wfahip_align_batch_bounded(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob,
+                                uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                                const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs,
+                                uint32_t max_score, wfahip_results *out);
+int  wfahip_align_batch_bounded_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_seq_blob,
+                                       uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
+                                       const void *d_t_off, const void *d_t_len, uint64_t n_pairs,
+                                       uint32_t max_len, uint32_t max_score, void *d_rec, void *d_ops, uint64_t ops_cap,
+                                       uint64_t *ops_needed, void *stream);
 
 /* Score only on device-resident input: wfahip_score_batch for a batch that already lives in HBM -- the output of
  * wfahip_generate_pairs_device, a torch pipeline, the candidates of an earlier GPU stage -- with the results left there for the next

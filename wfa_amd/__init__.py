@@ -5,7 +5,7 @@ lib/ (the built libwfahip.so) and aligner.py (host-side mirror of the reference'
 """
 from .aligner import (  # noqa: F401
     AdaptiveReductionOption, Aligner, AlignmentResult, MultiAligner, pack_pairs, generate_pairs_device, BatchResult, DefaultAdaptiveOption, DefaultOptions,
-    DefaultPenalties, ErrEmptySeq, ErrSeqTooLong, MaskLower32, MaxSeqLen, New, Op, OpD, OpH, OpI, OpM, OpX,
+    DefaultPenalties, ErrEmptySeq, ErrOverMaxScore, ErrSeqTooLong, MaskLower32, MaxSeqLen, New, Op, OpD, OpH, OpI, OpM, OpX,
     Options, Penalties, RecycleAligner, RecycleAlignmentResult, RecycleAlignmentText, WfaError, generate_pairs,
     make_blob, plot_component, trimOps,
 )

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libwfahip.so")
 # whole-call codes / per-pair status (include/wfa_hip.h)
 OK, ERR_NO_DEVICE, ERR_BAD_ARG, ERR_OOM, ERR_HIP, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 PAIR_OK, PAIR_EMPTY, PAIR_TOO_LONG, PAIR_NO_MEMORY = 0, 1, 2, 4
-PAIR_OVER_MAX = 8  # wfahip_score_batch: the pair's score exceeds max_score
+PAIR_OVER_MAX = 8  # the entries that take a max_score: the pair's score exceeds it
 MAX_SEQ_LEN = (1 << 29) - 1
 REC_WORDS = 16
 (REC_STATUS, REC_SCORE, REC_TBEGIN, REC_TEND, REC_QBEGIN, REC_QEND, REC_ALIGN_LEN, REC_MATCHES, REC_GAPS,
@@ -28,6 +28,7 @@ EXPORTS = [
     "wfahip_generate_pairs_device", "wfahip_align_pair", "wfahip_last_error", "wfahip_debug_clock",
     "wfahip_debug_team_compact", "wfahip_score_batch", "wfahip_scores_free", "wfahip_score_matrix",
     "wfahip_debug_score_long_list", "wfahip_score_batch_device", "wfahip_debug_score_device_list",
+    "wfahip_align_batch_bounded", "wfahip_align_batch_bounded_device",
 ]
 
 
@@ -101,6 +102,11 @@ def lib():
         L.wfahip_align_batch_device.restype = C.c_int
         L.wfahip_align_batch_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, vp, vp,
                                                 u64, C.POINTER(u64), vp]
+        L.wfahip_align_batch_bounded.restype = C.c_int
+        L.wfahip_align_batch_bounded.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, C.POINTER(Results)]
+        L.wfahip_align_batch_bounded_device.restype = C.c_int
+        L.wfahip_align_batch_bounded_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, u32, vp, vp,
+                                                        u64, C.POINTER(u64), vp]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

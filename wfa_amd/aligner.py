@@ -36,6 +36,7 @@ class WfaError(Exception):
 
 ErrEmptySeq = WfaError("wfa: invalid empty sequence")                                 # wfa.go:187
 ErrSeqTooLong = WfaError(f"wfa: sequences longer than {MaxSeqLen} are not supported")  # wfa.go:193
+ErrOverMaxScore = WfaError("wfa: alignment score exceeds max_score")                  # (no counterpart: AlignBatch(.., max_score))
 
 
 @dataclass
@@ -243,8 +244,12 @@ class Aligner:
             p.min_wf_len, p.max_dist_diff, p.cutoff_step = self.ad.MinWFLen, self.ad.MaxDistDiff, self.ad.CutoffStep
         return p
 
-    def align_arrays(self, blob, q_off, q_len, t_off, t_len) -> "BatchResult":
-        """Batch alignment over the C-ABI layout; returns struct-of-arrays results (numpy copies)."""
+    def align_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0) -> "BatchResult":
+        """Batch alignment over the C-ABI layout; returns struct-of-arrays results (numpy copies).  max_score > 0
+        (include/wfa_hip.h: wfahip_align_batch_bounded): a pair whose score exceeds it stops early, with status PAIR_OVER_MAX
+        (8) and every other field 0; the pairs within the bound come back as without one."""
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
         n = int(len(q_len))
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
@@ -254,8 +259,12 @@ class Aligner:
         res = L.Results()
         prm = self._params()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        L.check(L.lib().wfahip_align_batch(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len),
-                                           vp(t_off), vp(t_len), n, C.byref(res)), "wfahip_align_batch")
+        if int(max_score):
+            L.check(L.lib().wfahip_align_batch_bounded(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len),
+                                                       vp(t_off), vp(t_len), n, int(max_score), C.byref(res)), "wfahip_align_batch_bounded")
+        else:
+            L.check(L.lib().wfahip_align_batch(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len),
+                                               vp(t_off), vp(t_len), n, C.byref(res)), "wfahip_align_batch")
         return _take_results(res, n)
 
     def align_arrays_packed(self, packed, q_woff, q_len, t_woff, t_len) -> "BatchResult":
@@ -468,13 +477,14 @@ class Aligner:
         L.check(L.lib().wfahip_collect(self._ctx, C.byref(prm), C.byref(res)), "wfahip_collect")
         return _results_and_errors(_take_results(res, n))
 
-    def AlignBatch(self, qs: Sequence[bytes], ts: Sequence[bytes]):
-        """([]*AlignmentResult, []error): per-pair results and per-pair errors (None = ok)."""
+    def AlignBatch(self, qs: Sequence[bytes], ts: Sequence[bytes], max_score: int = 0):
+        """([]*AlignmentResult, []error): per-pair results and per-pair errors (None = ok).  max_score > 0: a pair whose
+        score exceeds it has no result and ErrOverMaxScore in the error list (see align_arrays)."""
         if len(qs) != len(ts):
             raise ValueError("qs and ts differ in length")
         if not qs:
             return [], []
-        return _results_and_errors(self.align_arrays(*make_blob(qs, ts)))
+        return _results_and_errors(self.align_arrays(*make_blob(qs, ts), max_score=max_score))
 
     # -- diagnostics ----------------------------------------------------------------------------
     def last_timing(self) -> Timing:
@@ -585,6 +595,7 @@ def _results_and_errors(br: "BatchResult"):
         else:
             results.append(None)
             errors.append(ErrEmptySeq if st == L.PAIR_EMPTY else ErrSeqTooLong if st == L.PAIR_TOO_LONG
+                          else ErrOverMaxScore if st == L.PAIR_OVER_MAX
                           else WfaError("wfa: out of device memory for this pair"))
     return results, errors
 

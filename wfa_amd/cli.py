@@ -9,6 +9,8 @@ Options:  -g  do not use global alignment          -a  do not use adaptive reduc
           -N  do not output alignment (benchmark)  -t  only show the aligned region
           -s  score only: print "align-score : N" per pair (no alignment is computed)
           -S  score matrix: every query against every target, one line of tab-separated scores per query
+          -b N  score bound: a pair whose score exceeds N stops early and prints "align-score : >N" and a blank line
+                instead of its block (with -s: instead of its score); the exit code stays 0
 """
 from __future__ import annotations
 
@@ -59,8 +61,14 @@ def main(argv=None) -> int:
     ap.add_argument("-s", dest="score_only", action="store_true", help="score only: print the alignment score of each pair")
     ap.add_argument("-S", dest="score_matrix", action="store_true",
                     help="score matrix: every query against every target, one line of tab-separated scores per query")
+    ap.add_argument("-b", dest="bound", type=int, default=0, metavar="N",
+                    help="score bound: a pair whose score exceeds N is not aligned further and prints \"align-score : >N\"")
     ap.add_argument("seqs", nargs="*")
     args = ap.parse_args(argv)
+
+    if not 0 <= args.bound < 1 << 32:
+        print("flag -b takes a score between 0 (no bound) and 4294967295.", file=sys.stderr)
+        return 1
 
     import wfa_amd as wfa
     if args.infile == "":
@@ -95,9 +103,13 @@ def main(argv=None) -> int:
             sys.stdout.flush()
             return 0
         if args.score_only:  # wfahip_score_batch: the forward pass alone
-            status, scores = algn.ScoreBatch([p[0] for p in pairs], [p[1] for p in pairs])
+            status, scores = algn.ScoreBatch([p[0] for p in pairs], [p[1] for p in pairs], max_score=args.bound)
             out = sys.stdout
             for st, sc in zip(status, scores):
+                if st == wfa._lib.PAIR_OVER_MAX:
+                    if not args.no_output:
+                        out.write(f"align-score : >{args.bound}\n")
+                    continue
                 if st != wfa._lib.PAIR_OK:
                     print(pair_error(st), file=sys.stderr)
                     return 1
@@ -105,9 +117,13 @@ def main(argv=None) -> int:
                     out.write(f"align-score : {int(sc)}\n")
             out.flush()
             return 0
-        results, errors = algn.AlignBatch([p[0] for p in pairs], [p[1] for p in pairs])
+        results, errors = algn.AlignBatch([p[0] for p in pairs], [p[1] for p in pairs], max_score=args.bound)
         out = sys.stdout
         for (q, t), r, err in zip(pairs, results, errors):
+            if err is wfa.ErrOverMaxScore:  # (not an error of the run: the pair is above the caller's bound)
+                if not args.no_output:
+                    out.write(f"align-score : >{args.bound}\n\n")
+                continue
             if err is not None:  # checkError: print and exit 1 (wfa-go.go:117-119,185-190)
                 print(err, file=sys.stderr)
                 return 1

@@ -245,8 +245,24 @@ struct wfahip_ctx {
     const uint4    *dbg_meta  = nullptr;
     uint64_t        dbg_words = 0, dbg_first = 0, dbg_n = 0;
     uint32_t        dbg_fmt = 0, dbg_g = 1;
+    uint32_t        max_score = 0;  // wfahip_align_batch_bounded and the full-path legs of the score entries, for the duration of their call (BoundScope):
+                                    // the bound align_device stops and filters by (0 = none) -- slices, the autopacked path and every retry see it here
     wfahip_timing timing{};
     char          last_error[256] = {0};
+};
+
+// sets the context's score bound for the scope of a call and puts back what was there
+struct BoundScope {
+    wfahip_ctx *c;
+    uint32_t    keep;
+    BoundScope(wfahip_ctx *ctx, uint32_t max_score) : c(ctx), keep(ctx ? ctx->max_score : 0u) {
+        if (c) c->max_score = max_score;
+    }
+    ~BoundScope() {
+        if (c) c->max_score = keep;
+    }
+    BoundScope(const BoundScope &) = delete;
+    BoundScope &operator=(const BoundScope &) = delete;
 };
 
 

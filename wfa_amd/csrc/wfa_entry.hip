@@ -119,7 +119,7 @@ int unpack_results(const std::vector<uint32_t> &rec, const std::vector<uint64_t>
     for (uint64_t i = 0; i < n; i++) {  // ops are re-packed in pair order (device order is completion order)
         const uint32_t *r  = &rec[i * REC_WORDS];
         uint32_t        st = r[REC_STATUS];
-        out->status[i]     = (st == ST_OK || st == ST_EMPTY || st == ST_TOO_LONG) ? (int32_t)st : WFAHIP_PAIR_NO_MEMORY;
+        out->status[i]     = (st == ST_OK || st == ST_EMPTY || st == ST_TOO_LONG || st == ST_OVER_MAX) ? (int32_t)st : WFAHIP_PAIR_NO_MEMORY;
         if (st != ST_OK) continue;
         out->score[i]       = r[REC_SCORE];
         out->tbegin[i]      = (int32_t)r[REC_TBEGIN];
@@ -757,6 +757,16 @@ extern "C" int wfahip_align_batch(wfahip_ctx *ctx, const wfahip_params *p, const
                                   uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
                                   const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs,
                                   wfahip_results *out) {
+    WFAHIP_GUARD(align_batch_entry(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, out))
+}
+
+// the same under a score bound: the context carries it to the slices, the autopacked path and every retry (align_device)
+extern "C" int wfahip_align_batch_bounded(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob,
+                                          uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                                          const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs,
+                                          uint32_t max_score, wfahip_results *out) {
+    if (!ctx || !p || !out) return WFAHIP_ERR_BAD_ARG;  // (before the context is touched)
+    BoundScope bound(ctx, max_score);
     WFAHIP_GUARD(align_batch_entry(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, out))
 }
 

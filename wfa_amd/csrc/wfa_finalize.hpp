@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void fin_gather(const FinParams F) {
     const uint64_t  dst = F.blk_sum[i / (FIN_BLOCK * FIN_ITEMS)] + F.loc_off[i];
     const uint32_t  len = ok ? r[REC_OPS_LEN] : 0u;
     if (lane == 0) {
-        F.status[i]      = (st == ST_OK || st == ST_EMPTY || st == ST_TOO_LONG) ? (int32_t)st : 4 /* WFAHIP_PAIR_NO_MEMORY */;
+        F.status[i]      = (st == ST_OK || st == ST_EMPTY || st == ST_TOO_LONG || st == ST_OVER_MAX) ? (int32_t)st : 4 /* WFAHIP_PAIR_NO_MEMORY */;
         F.score[i]       = ok ? r[REC_SCORE] : 0u;
         F.tbegin[i]      = ok ? (int32_t)r[REC_TBEGIN] : 0;
         F.tend[i]        = ok ? (int32_t)r[REC_TEND] : 0;

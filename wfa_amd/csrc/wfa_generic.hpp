@@ -96,6 +96,7 @@ __global__ __launch_bounds__(64 * WAVES) void wfa_generic_kernel(const KParams P
         uint64_t       top     = 0;  // next free arena word
         uint32_t       n_ent   = 0;  // directory entries written
         bool           overflow = false, done = false;
+        bool           over_max = false;  // a global pair whose score is above P.max_score: every row up to the bound was computed, none terminated
         uint32_t       s_final = 0;
         uint64_t       my_cells = 0;
         auto dir_ptr  = [&](uint32_t idx) { return A + cap - (uint64_t)DIR_WORDS * (idx + 1); };
@@ -103,6 +104,10 @@ __global__ __launch_bounds__(64 * WAVES) void wfa_generic_kernel(const KParams P
         const DirEnt none = {0ull, 0, 0, 0u, {0u, 0u, 0u}};
 
         for (uint32_t s = 0;; s += g) {
+            if (glob && P.max_score != 0u && s > P.max_score) {  // (semi-global pairs run on: their end cell is searched over all rows; the host filters them)
+                over_max = true;
+                break;
+            }
             const uint32_t si = s / g;
             // sources: M[s-x], M[s-o-e], I[s-e] / D[s-e]  (wfa.go:557-560; missing when diff > s)
             const DirEnt eX = (s >= x) ? load_ent(si - x / g) : none;
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(64 * WAVES) void wfa_generic_kernel(const KParams P
                     uint32_t ws = s, wn = n_ent, wfin = s_final;
                     uint64_t wtop = top, wcells = 0;
                     const uint32_t wflags =
-                        wave_mode_steps<MODE>(P, sv, A, cap, gring, wring, P.wave_rows, n, m, glob, ws, wtop, wn, wfin, wcells, nullptr);
+                        wave_mode_steps<MODE, true>(P, sv, A, cap, gring, wring, P.wave_rows, n, m, glob, ws, wtop, wn, wfin, wcells, nullptr);
                     my_cells += wcells;
                     if (tid == 0) {
                         unsigned int *const ur = reinterpret_cast<unsigned int *>(red);
@@ -161,9 +166,10 @@ __global__ __launch_bounds__(64 * WAVES) void wfa_generic_kernel(const KParams P
                     s = ur[0], top = (uint64_t)ur[1] | ((uint64_t)ur[2] << 32), n_ent = ur[3];
                     if (ur[4] & WAVE_DONE) done = true, s_final = ur[5];
                     if (ur[4] & WAVE_OVERFLOW) overflow = true;
+                    if (ur[4] & WAVE_OVER_MAX) over_max = true;
                 }
                 __syncthreads();
-                if (done || overflow) break;
+                if (done || overflow || over_max) break;
                 s -= g;  // the row at s is wider than 64: the workgroup-wide step
                 continue;
             }
@@ -298,6 +304,10 @@ __global__ __launch_bounds__(64 * WAVES) void wfa_generic_kernel(const KParams P
         atomicAdd(reinterpret_cast<unsigned int *>(&red[10]), (unsigned int)(my_cells & 0xFFFFFFFFull));
         __syncthreads();
 
+        if (over_max) {  // final: the record, no redo entry
+            if (tid < REC_WORDS) rec[tid] = (tid == REC_STATUS) ? (uint32_t)ST_OVER_MAX : 0u;
+            continue;
+        }
         if (overflow || !done) {
             if (tid == 0) {
                 rec[REC_STATUS] = ST_REDO_ARENA;

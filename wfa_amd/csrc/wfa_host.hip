@@ -5,6 +5,7 @@
 // entry points return WFAHIP_ERR_NO_DEVICE.
 #include <map>
 #include "wfa_ctx.hpp"
+#include "wfa_bound.hpp"
 // (the kernels' headers for their constants and device functions; the forward kernels are instantiated per penalty shape in
 // wfa_fwd_s*.hip, wfa_duo_kernel in wfa_duo.hip, the long-pair kernels in wfa_long.hip: this unit keeps the router, the
 // non-template kernels of the pipeline -- packing, backtrace, result assembly, the generator -- and the two first-generation
@@ -245,6 +246,35 @@ __global__ __launch_bounds__(256) void wfa_unpack_pairs_kernel(const KParams P, 
             *reinterpret_cast<uint4 *>(blob + off[q] + 16ull * j) = make_uint4(o[0], o[1], o[2], o[3]);
         }
     }
+}
+
+// Score bound (wfahip_align_batch_bounded; wfa_bound.hpp).  A pass whose arena rows reach the bound has handed on, as
+// ST_REDO_ARENA, exactly the pairs that ran out of them: their score is above the bound.  This kernel makes those entries of
+// the pass's redo list final before the host fetches it: the record becomes {ST_OVER_MAX, 0, ..} and the entry's status
+// ST_OVER_MAX, which the host drops from the list.  (The backtrace kernel that may run beside it never touches the record of
+// a pair that was handed on.)
+__global__ __launch_bounds__(256) void wfa_bound_redo_kernel(uint32_t *__restrict__ redo_list, const uint32_t *__restrict__ redo_count, uint32_t *__restrict__ rec) {
+    const uint32_t n = *redo_count;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        if (redo_list[2u * i + 1u] != ST_REDO_ARENA) continue;
+        uint4 *const r4 = reinterpret_cast<uint4 *>(rec + (uint64_t)redo_list[2u * i] * REC_WORDS);
+        const uint4  z  = make_uint4(0u, 0u, 0u, 0u);
+        r4[0] = make_uint4(ST_OVER_MAX, 0u, 0u, 0u), r4[1] = z, r4[2] = z, r4[3] = z;
+        redo_list[2u * i + 1u] = ST_OVER_MAX;
+    }
+}
+
+// ... and the filter at the end of a bounded call, over all records: what finished with a score above the bound where nothing
+// stopped it earlier (semi-global pairs, the team kernels, the directory arenas) becomes the same record.  Its CIGAR ops stay
+// in the op buffer, unreferenced.
+__global__ __launch_bounds__(256) void wfa_bound_filter_kernel(uint32_t *__restrict__ rec, uint64_t n, uint32_t max_score) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint4 *const r4 = reinterpret_cast<uint4 *>(rec + i * REC_WORDS);
+    const uint4  h  = r4[0];
+    if (h.x != ST_OK || h.y <= max_score) return;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    r4[0] = make_uint4(ST_OVER_MAX, 0u, 0u, 0u), r4[1] = z, r4[2] = z, r4[3] = z;
 }
 
 
@@ -615,6 +645,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
     P.redo_list  = static_cast<uint32_t *>(ctx->redo.p);
     set_penalties(P, p);
     P.census = ctx->opt_census ? 1u : 0u;
+    P.max_score = ctx->max_score;  // (0 unless a bounded entry is calling: BoundScope)
     P.rec = static_cast<uint32_t *>(d_rec);
     P.ops = static_cast<uint64_t *>(d_ops), P.ops_cap = ops_cap;
 
@@ -847,12 +878,18 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             const uint32_t pairs_wave   = kind >= 13 ? 1 : kind == 10 ? 64 : bkind == 5 ? 1 : bkind == 9 ? 2 : (kind == 4 || kind == 6 || kind == 8 ? 8 : (kind >= 2 ? 4 : 2));
             // blocked kernels: fixed-pitch arena, no directory.  64-diagonal window: 16 words per base = 250 scores at
             // 1 kbp; 256-diagonal window (kind 5, the retry rung): 128 words per base = 500 scores at 1 kbp
-            const uint64_t words        = bkind == 5   ? std::max<uint64_t>((words_dir * 16 * arena_mult + 511) & ~511ull, 8192)
-                                          : bkind == 9 ? std::max<uint64_t>((words_dir * 4 * arena_mult + 511) & ~511ull, 4096)
-                                          : kind == 8 ? std::max<uint64_t>((words_dir * arena_mult + 511) & ~511ull, 1024)  // 16-bit words
-                                          : kind == 10 ? std::max<uint64_t>((words_dir * arena_mult + 511) & ~511ull, 1024)  // rows of 32 x 16 bit
-                                          : kind >= 3 ? std::max<uint64_t>((words_dir * 2 * arena_mult + 511) & ~511ull, 2048)
+            const uint64_t words_min    = bkind == 5 ? 8192 : bkind == 9 ? 4096 : (kind == 8 || kind == 10) ? 1024 : 2048;
+            const uint64_t words_free   = bkind == 5   ? std::max<uint64_t>((words_dir * 16 * arena_mult + 511) & ~511ull, words_min)
+                                          : bkind == 9 ? std::max<uint64_t>((words_dir * 4 * arena_mult + 511) & ~511ull, words_min)
+                                          : kind == 8 ? std::max<uint64_t>((words_dir * arena_mult + 511) & ~511ull, words_min)  // 16-bit words
+                                          : kind == 10 ? std::max<uint64_t>((words_dir * arena_mult + 511) & ~511ull, words_min)  // rows of 32 x 16 bit
+                                          : kind >= 3 ? std::max<uint64_t>((words_dir * 2 * arena_mult + 511) & ~511ull, words_min)
                                                       : words_dir;
+            // a score bound sizes the fixed-pitch rows: no more of them than the bound can reach.  When the rows reach it, a pair
+            // that runs out of them is above the bound and final (wfa_bound.hpp)
+            const uint32_t pitch        = bound_row_pitch(kind);
+            const uint64_t words        = bound_cap_words(words_free, pitch, words_min, P.max_score, P.g);
+            const bool     bound_final  = bound_covers(words, pitch, P.max_score, P.g);
             P.arena_words = words, P.compact_fmt = kind == 10 ? 8u : kind == 8 ? DUO_ARENA_FMT : kind == 6 ? 5u : bkind == 5 ? 4u : bkind == 9 ? 6u : (kind >= 3 ? (WFA_BLK_TILED ? 3u : 1u) : 0u);
             const uint32_t waves_lds    = (uint32_t)std::min<size_t>(32, LDS_MAX_BYTES / lds_bytes);
             const bool     overlap      = ctx->opt_overlap != 0;
@@ -1005,8 +1042,14 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 for (uint64_t c = (n_chunks >= 2 ? n_chunks - 2 : 0); c < n_chunks; c++)
                     HIP_TRY(hipStreamWaitEvent(st, ctx->evpool[4 * c + 3], 0));
             uint32_t hc[CTRL_WORDS];
+            if (bound_final) {  // (one launch over the device list: these can be most of a batch)
+                hipLaunchKernelGGL(wfa_bound_redo_kernel, dim3((uint32_t)std::min<uint64_t>((count + 255) / 256, 1024)), dim3(256), 0, st, P.redo_list, P.redo_count, P.rec);
+                HIP_TRY(hipGetLastError());
+            }
             if (!detach_bt) HIP_TRY(hipEventRecord(ctx->ev1, st));  // (the end of the call if nothing follows)
             if ((rc2 = fetch_ctrl(hc, &redo_out))) return rc2;  // (detach_bt: the forward kernel is done, the backtrace may still run)
+            // (they leave the list here: no rung, no learned row count and no count of handed-on pairs sees them)
+            if (bound_final) redo_out.erase(std::remove_if(redo_out.begin(), redo_out.end(), [](uint64_t e) { return (uint32_t)(e >> 32) == ST_OVER_MAX; }), redo_out.end());
             if (detach_bt) ctx->bt_pending = true;
             else ctrl_fresh = true, std::memcpy(hc_last, hc, sizeof hc_last);
             for (uint64_t c = 0; c < n_chunks; c++) {
@@ -1701,7 +1744,13 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         ctx->learn_key = lkey, ctx->learn_level = learned_now;
     }
     if (ctx->bt_pending) HIP_TRY(hipStreamWaitEvent(st, ctx->evBtB, 0));
-    if (!no_memory.empty() || ctx->bt_pending) ctrl_fresh = false;
+    if (!no_memory.empty() || ctx->bt_pending || P.max_score != 0u) ctrl_fresh = false;
+    // score bound: every record of an aligned pair is written by now (the detached backtrace has been waited for above); inside the synchronised
+    // region -- the control words are fetched behind it
+    if (P.max_score != 0u) {
+        hipLaunchKernelGGL(wfa_bound_filter_kernel, dim3((uint32_t)((n_pairs + 255) / 256)), dim3(256), 0, st, P.rec, n_pairs, P.max_score);
+        HIP_TRY(hipGetLastError());
+    }
     if (!ctrl_fresh) HIP_TRY(hipEventRecord(ctx->ev1, st));
 
     for (uint32_t pid : no_memory) {
@@ -1749,6 +1798,17 @@ extern "C" int wfahip_align_batch_device(wfahip_ctx *ctx, const wfahip_params *p
                                          uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap,
                                          uint64_t *ops_needed, void *stream) {
     if (!ctx) return WFAHIP_ERR_BAD_ARG;
+    return align_device(ctx, p, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs, max_len,
+                        d_rec, d_ops, ops_cap, ops_needed, static_cast<hipStream_t>(stream), false);
+}
+
+extern "C" int wfahip_align_batch_bounded_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_seq_blob,
+                                                 uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
+                                                 const void *d_t_off, const void *d_t_len, uint64_t n_pairs,
+                                                 uint32_t max_len, uint32_t max_score, void *d_rec, void *d_ops, uint64_t ops_cap,
+                                                 uint64_t *ops_needed, void *stream) {
+    if (!ctx || !p) return WFAHIP_ERR_BAD_ARG;  // (before the context is touched)
+    BoundScope bound(ctx, max_score);
     return align_device(ctx, p, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs, max_len,
                         d_rec, d_ops, ops_cap, ops_needed, static_cast<hipStream_t>(stream), false);
 }

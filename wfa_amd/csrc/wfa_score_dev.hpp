@@ -16,7 +16,7 @@
 //                           offsets and lengths in compact arrays align_device() takes as they are -- the offsets keep pointing into
 //                           the caller's blob
 //   wfa_score_finish_kernel {status, score} records -> the caller's d_status / d_score; the records of the full path's pairs -> the
-//                           same, with max_score applied as score_batch_impl applies it
+//                           same (the full path ran under the call's max_score: its records say ST_OVER_MAX themselves)
 //
 // Lists in batch order come from a scan, not from a per-pair atomic: every selection is two launches over tiles of SD_TILE items --
 // count (tile sums -> blk[]), then write (rank = blk[tile] + rank within the tile) -- with wfa_score_scan_kernel, one workgroup
@@ -66,7 +66,7 @@ struct SDParams {
     uint32_t       *d_score;
     const uint32_t *rec;        // nullptr: from score_out; else the records of pairs r_id[first ..] of the full path
     uint64_t        first;
-    uint32_t        max_score;
+    uint32_t        max_score;  // (the call's bound; the full path gets it through the context)
 };
 
 #ifdef WFA_SCORE_UNIT
@@ -274,8 +274,8 @@ __global__ __launch_bounds__(SD_BLOCK) void wfa_score_finish_kernel(const SDPara
     }
     const uint32_t i  = S.r_id[S.first + j];
     uint32_t       st = S.rec[j * REC_WORDS + REC_STATUS], sc = S.rec[j * REC_WORDS + REC_SCORE];
-    if (!(st == (uint32_t)ST_OK || st == (uint32_t)ST_EMPTY || st == (uint32_t)ST_TOO_LONG)) st = ST_NO_MEMORY;  // (unpack_results' rule)
-    if (st == (uint32_t)ST_OK && S.max_score != 0u && sc > S.max_score) st = ST_OVER_MAX;
+    // (unpack_results' rule; the full path ran under the call's bound and has said ST_OVER_MAX itself)
+    if (!(st == (uint32_t)ST_OK || st == (uint32_t)ST_EMPTY || st == (uint32_t)ST_TOO_LONG || st == (uint32_t)ST_OVER_MAX)) st = ST_NO_MEMORY;
     S.d_status[i] = (int32_t)st, S.d_score[i] = st == (uint32_t)ST_OK ? sc : 0u;
 }
 #endif  // WFA_SCORE_UNIT

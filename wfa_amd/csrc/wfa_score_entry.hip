@@ -172,13 +172,13 @@ int score_fallback(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_b
         qo[k] = q_off[s.first], ql[k] = q_len[s.first], to[k] = t_off[s.second], tl[k] = t_len[s.second];
     }
     wfahip_results r;
-    const int      rc = align_batch_entry(ctx, p, seq_blob, blob_bytes, qo.data(), ql.data(), to.data(), tl.data(), n, &r);
-    if (rc) return rc;
-    for (uint64_t k = 0; k < n; k++) {
-        const uint32_t st = (uint32_t)r.status[k], sc = r.score[k];
-        if (st == ST_OK && max_score != 0u && sc > max_score) put(k, (uint32_t)ST_OVER_MAX, 0u);
-        else put(k, st, sc);
+    int            rc;
+    {
+        BoundScope bound(ctx, max_score);  // (the full path stops and filters by it: wfahip_align_batch_bounded's path)
+        rc = align_batch_entry(ctx, p, seq_blob, blob_bytes, qo.data(), ql.data(), to.data(), tl.data(), n, &r);
     }
+    if (rc) return rc;
+    for (uint64_t k = 0; k < n; k++) put(k, (uint32_t)r.status[k], r.score[k]);
     wfahip_results_free(&r);
     const wfahip_timing &f = ctx->timing;
     tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = std::max(tm.arena_bytes, f.arena_bytes);
@@ -451,7 +451,8 @@ static int score_batch_device_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
             uint64_t ops_cap = std::min<uint64_t>(sum_len, 2ull * fb_max * nb) / 4 + 8 * nb + 1024;
             for (int attempt = 0;; attempt++) {
                 if ((rc = ensure(ctx, ctx->out_ops, ops_cap * 8))) return rc;
-                uint64_t needed = 0;
+                uint64_t   needed = 0;
+                BoundScope bound(ctx, max_score);  // (the full path stops and filters by it)
                 rc = align_device(ctx, p, d_blob, blob_bytes, S.r_qoff + a, S.r_qlen + a, S.r_toff + a, S.r_tlen + a, nb, fb_max, ctx->out_rec.p,
                                   ctx->out_ops.p, ops_cap, &needed, st, false);
                 if (rc == WFAHIP_ERR_OOM && needed > ops_cap && attempt == 0) {

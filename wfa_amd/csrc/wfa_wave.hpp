@@ -15,7 +15,7 @@
 namespace wfa {
 
 constexpr int WAVE_DIR_RING = 64;  // directory entries in LDS (sources reach back < 64 scores)
-enum : uint32_t { WAVE_DONE = 1u, WAVE_OVERFLOW = 2u, WAVE_WIDE = 4u };
+enum : uint32_t { WAVE_DONE = 1u, WAVE_OVERFLOW = 2u, WAVE_WIDE = 4u, WAVE_OVER_MAX = 8u };
 
 // Runs score steps from score s (whose row is known to be at most 64 diagonals wide) until the alignment ends
 // (WAVE_DONE: s = s_final = the final score, its entry written), the arena is full (WAVE_OVERFLOW) or the row at
@@ -26,7 +26,9 @@ enum : uint32_t { WAVE_DONE = 1u, WAVE_OVERFLOW = 2u, WAVE_WIDE = 4u };
 // and directory share the slot (the rows grow up from its start, the directory down from `cap`: row_end is ignored); else the
 // rows live in a page of their own that ends at row_end (wfa_team_kernel's paged arena) and WAVE_OVERFLOW means "this page
 // is full", unless the directory is.
-template <int MODE>
+// BOUND (wfa_generic_kernel only; the team kernels' instances are compiled without it): a global pair stops with WAVE_OVER_MAX
+// when the score to compute is above P.max_score -- every row up to the bound exists then and none terminated.
+template <int MODE, bool BOUND = false>
 WFA_DEV uint32_t wave_mode_steps(const KParams &P, const SeqView<MODE> &sv, uint32_t *const A, const uint64_t cap, DirEnt *const ring,
                                  uint32_t *const wring, const uint32_t wave_rows, const int n, const int m, const bool glob, uint32_t &s,
                                  uint64_t &top, uint32_t &n_ent, uint32_t &s_final, uint64_t &my_cells, unsigned long long *n_steps,
@@ -66,6 +68,12 @@ WFA_DEV uint32_t wave_mode_steps(const KParams &P, const SeqView<MODE> &sv, uint
     uint64_t utop = (uint64_t)rfl((uint32_t)top) | ((uint64_t)rfl((uint32_t)(top >> 32)) << 32);
     const uint32_t dx = x / g, doe = oe / g, de = e / g;
     for (;; su += g, sj++) {
+        if constexpr (BOUND) {
+            if (WFA_RARE(glob && P.max_score != 0u && su > P.max_score)) {
+                wflags = WAVE_OVER_MAX;
+                break;
+            }
+        }
         int xlo = 0, xw = 0, olo = 0, ow_ = 0, elo = 0, ew = 0;
         if (su >= x) {
             const int2 v = ring_lw[((sj - dx) % WAVE_DIR_RING) * 4u + 1u];

@@ -42,7 +42,7 @@ constexpr int      MaxSeqLen   = (1 << 29) - 1;
 constexpr uint64_t MaskLower32 = 4294967295ull;
 constexpr uint64_t OpM = 'M', OpD = 'D', OpI = 'I', OpX = 'X', OpH = 'H';
 
-enum class Error { None = 0, EmptySeq, SeqTooLong, BadAdaptiveOption, NoMemory, Device };
+enum class Error { None = 0, EmptySeq, SeqTooLong, BadAdaptiveOption, NoMemory, Device, OverMaxScore };
 inline const char *ErrorText(Error e) {
     switch (e) {
     case Error::None: return "";
@@ -51,6 +51,7 @@ inline const char *ErrorText(Error e) {
     case Error::BadAdaptiveOption: return "cutoff step should not be 0";                       // wfa.go:136
     case Error::NoMemory: return "wfa: out of device memory for this pair";
     case Error::Device: return "wfa: device error";
+    case Error::OverMaxScore: return "wfa: alignment score exceeds max_score";  // (AlignBatch with a bound)
     }
     return "";
 }
@@ -196,6 +197,12 @@ class Aligner {
     // GPUs, wfahip_create_multi) the batch is sharded over them.
     int AlignBatch(const std::vector<std::string> &qs, const std::vector<std::string> &ts,
                    std::vector<AlignmentResult> &results, std::vector<Error> &errors, wfahip_multi *multi = nullptr) {
+        return AlignBatch(qs, ts, 0u, results, errors, multi);
+    }
+    // ... under a score bound (wfahip_align_batch_bounded; one GPU): a pair whose score exceeds max_score stops early, has no
+    // result and Error::OverMaxScore; max_score == 0: no bound
+    int AlignBatch(const std::vector<std::string> &qs, const std::vector<std::string> &ts, uint32_t max_score,
+                   std::vector<AlignmentResult> &results, std::vector<Error> &errors, wfahip_multi *multi = nullptr) {
         const size_t n = qs.size();
         results.assign(n, {});
         errors.assign(n, Error::None);
@@ -218,10 +225,16 @@ class Aligner {
         }
         const wfahip_params prm = params();
         wfahip_results      out{};
+        if (multi && max_score) {  // (no multi-GPU variant of the bounded entry)
+            errors.assign(n, Error::Device);
+            return WFAHIP_ERR_UNSUPPORTED;
+        }
         const int rc = multi ? wfahip_align_batch_multi(multi, &prm, blob.data(), blob.size(), q_off.data(), q_len.data(),
                                                         t_off.data(), t_len.data(), n, &out)
-                             : wfahip_align_batch(ctx_, &prm, blob.data(), blob.size(), q_off.data(), q_len.data(),
-                                                  t_off.data(), t_len.data(), n, &out);
+                       : max_score ? wfahip_align_batch_bounded(ctx_, &prm, blob.data(), blob.size(), q_off.data(), q_len.data(),
+                                                                t_off.data(), t_len.data(), n, max_score, &out)
+                                   : wfahip_align_batch(ctx_, &prm, blob.data(), blob.size(), q_off.data(), q_len.data(),
+                                                        t_off.data(), t_len.data(), n, &out);
         return unpack(rc, out, results, errors);
     }
 
@@ -255,6 +268,7 @@ class Aligner {
             }
             case WFAHIP_PAIR_EMPTY: errors[i] = Error::EmptySeq; break;
             case WFAHIP_PAIR_TOO_LONG: errors[i] = Error::SeqTooLong; break;
+            case WFAHIP_PAIR_OVER_MAX: errors[i] = Error::OverMaxScore; break;
             default: errors[i] = Error::NoMemory; break;
             }
         }
