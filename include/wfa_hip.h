@@ -300,6 +300,32 @@ int  wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const ui
                                const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff,
                                const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
 
+/* Score only on pre-packed input: wfahip_score_batch over the words of wfahip_pack_pairs, so that a caller packs once, scores as
+ * often as needed and aligns the survivors (wfahip_align_batch_packed with a subset of the same offsets) on ONE buffer.  Layout as
+ * above: 16 bases per word, code (ascii >> 1) & 3, every sequence at a word boundary and followed by one pad word; pair i is
+ * packed[q_woff[i] ..] (q_len[i] bases) against packed[t_woff[i] ..].  Valid only for what was pure uppercase ACGT.
+ * The offsets may come in any order and may REPEAT: one packed query may face fifty packed targets without being stored fifty
+ * times, and a target may be the query of another pair.  The bits of a sequence's last word beyond its last base, and its pad
+ * word, may hold anything: no result depends on them.
+ * For every pair, status and score equal what wfahip_score_batch returns for the unpacked bytes under the same p and max_score
+ * (WFAHIP_PAIR_OK / _EMPTY / _TOO_LONG / _NO_MEMORY / _OVER_MAX, score 0 unless OK), global or semi-global, wf-adaptive on or off,
+ * any penalties.  Release out with wfahip_scores_free.
+ * Whole-call errors, checked before the device is touched: WFAHIP_ERR_BAD_ARG for a null ctx, p or out, for packed null with
+ * n_words > 0, with n_pairs > 0 for a null offset or length array, and for a pair, neither empty nor over WFAHIP_MAX_SEQ_LEN, one
+ * of whose sequences has woff + wfahip_packed_words(len) > n_words (an empty or too long pair's offsets are never looked at); then
+ * the params as wfahip_align_batch checks them.  n_pairs == 0 returns WFAHIP_OK with a zeroed out.
+ * The n_words words cross PCIe once, a quarter of the bytes, and the four arrays behind them; nothing else of the batch does.  The
+ * same kernels do the work, in instances whose prologue copies a pair's words into LDS where the byte instances load and pack
+ * bytes; wfa_score_long_kernel reads the long global pairs where they lie in the uploaded words (its table is built from the
+ * offsets: no sequence is packed or uploaded twice).  The pairs the kernels hand back -- a band over 248 diagonals, a semi-global
+ * read over 2 047 bases, a penalty shape without an instance, fewer than "score_long_min" long pairs -- have their words, and only
+ * theirs, gathered into a buffer of the entry's own and go through the full path of wfahip_align_batch_packed under the bound.
+ * wfahip_last_timing as after wfahip_score_batch (main_kernel_kind 19 / 23 / 20, n_retried_pairs = pairs that took the full path,
+ * arena_bytes = 0 unless some did). */
+int  wfahip_score_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                               const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                               uint64_t n_pairs, uint32_t max_score, wfahip_scores *out);
+
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns
  * at once with the pair's ticket (0, 1, 2, ... since the last collect) -- and collects all results with ONE batch

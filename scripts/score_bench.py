@@ -14,7 +14,13 @@ Device leg (--device, KERNELS.md 4j): the legs become `score` (wfahip_score_batc
 (wfahip_align_batch_device on the same buffers), alternating per step; the scores of all three are compared in every step,
 outside the timed region.
 
+Packed leg (--packed, KERNELS.md 4l): the legs become `score` (wfahip_score_batch on the bytes) and `score_packed`
+(wfahip_score_batch_packed on the same pairs, packed ONCE by wfahip_pack_pairs before the steps and timed apart: "pack_ms"),
+alternating per step; --other-lib adds the parent's wfahip_score_batch as the yardstick.  Per leg also "upload_bytes_computed": what a
+call uploads by the entries' rules (with the default gate of 64 long pairs) -- computed here, not read from the library or a trace.
+
     python scripts/score_bench.py [--configs c3,g3] [--pairs 1000000] [--steps 5]
+    python scripts/score_bench.py --packed --configs c3,g3,L5 [--other-lib parent/wfa_amd/lib/libwfahip.so]
     python scripts/score_bench.py --device --configs c3,g3,L5 [--other-lib parent/wfa_amd/lib/libwfahip.so]
     python scripts/score_bench.py --configs L5,l5 [--other-lib parent/wfa_amd/lib/libwfahip.so]
 """
@@ -120,6 +126,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=None, help="pairs of c3 / g3 (default 1e6); scales L5 down when given")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--device", action="store_true", help="legs on device-resident input: score (host entry), score_device, align_device")
+    ap.add_argument("--packed", action="store_true", help="legs on 2-bit packed input: score (bytes) and score_packed, packed once")
     ap.add_argument("--other-lib", default=None, help="libwfahip.so of another build: its wfahip_score_batch runs as a third leg")
     args = ap.parse_args()
     import torch
@@ -138,6 +145,22 @@ def main():
         fns = [("align", lambda: al.align_arrays(*arrays), al), ("score", lambda: al.score_arrays(*arrays), al)]
         if args.device:
             fns = [("score", lambda: al.score_arrays(*arrays), al)] + device_legs(w, al, arrays, glob, length, err)
+        extra, upload = {}, {}
+        if args.packed:
+            t0 = time.perf_counter()
+            packed, q_woff, t_woff = w.pack_pairs(*arrays, n_threads=16)
+            extra["pack_ms"] = (time.perf_counter() - t0) * 1e3
+            pk = (packed, q_woff, arrays[2], t_woff, arrays[4])
+            fns = [("score", lambda: al.score_arrays(*arrays), al), ("score_packed", lambda: al.score_arrays_packed(*pk), al)]
+            # bytes a call uploads: the blob or the words, the two offset and the two length arrays (none when every pair is long),
+            # and for the global pairs beyond 2 047 bases their table -- and, in the byte entry, their words, which it packs itself
+            lng = (np.maximum(arrays[2], arrays[4]) > 2047) if glob else np.zeros(pairs, bool)
+            n_long = int(lng.sum()) if lng.sum() >= 64 else 0
+            long_words = int((((arrays[2][lng].astype(np.int64) + 15) // 16 + 1) + ((arrays[4][lng].astype(np.int64) + 15) // 16 + 1)).sum()) if n_long else 0
+            n_arr = 0 if n_long == pairs else 24 * pairs
+            by = (0 if n_long == pairs else int(arrays[0].size)) + n_arr + 4 * long_words + 32 * n_long
+            upload = {"score": by, "score_packed": 4 * int(packed.size) + n_arr + 32 * n_long, "score_other": by}
+        ref_leg = "score" if args.device or args.packed else "align"
         other = None
         if args.other_lib:
             other = OtherLib(args.other_lib, w, glob)
@@ -153,20 +176,23 @@ def main():
                 dt = (time.perf_counter() - t0) * 1e3
                 t = who.last_timing()
                 legs[leg].append((dt, t.kernel_ms, t.main_kernel_kind, t.n_retried_pairs, t.arena_bytes))
-            if args.device:
+            if args.device or args.packed:
                 ref_status, want = res["score"]
             else:
                 ref_status, want = res["align"].status, np.where(res["align"].status == 0, res["align"].score, 0)
             for leg in legs:  # the scores are compared in every step
-                if leg != ("score" if args.device else "align"):
+                if leg != ref_leg:
                     st, sc = res[leg]() if callable(res[leg]) else res[leg]
                     assert np.array_equal(st, ref_status) and np.array_equal(sc, want), (name, leg)
-        out = {"config": name, "pairs": pairs, "steps": args.steps}
+        out = {"config": name, "pairs": pairs, "steps": args.steps, **extra}
         for leg, v in legs.items():
             wall = float(np.median([x[0] for x in v]))
             out[leg] = {"pairs_per_s": pairs / wall * 1e3, "wall_ms": wall, "kernel_ms": float(np.median([x[1] for x in v])),
                         "main_kernel_kind": v[-1][2], "n_retried_pairs": v[-1][3], "arena_bytes": v[-1][4],
                         "wall_ms_all": [round(x[0], 2) for x in v], "wall_ms_spread": round(max(x[0] for x in v) - min(x[0] for x in v), 2)}
+            if leg in upload:
+                out[leg]["upload_bytes_computed"] = upload[leg]
+            out[leg]["kernel_ms_all"] = [round(x[1], 2) for x in v]
         out["scores_equal"] = True
         print(json.dumps(out), flush=True)
         if other:

@@ -28,7 +28,7 @@ EXPORTS = [
     "wfahip_generate_pairs_device", "wfahip_align_pair", "wfahip_last_error", "wfahip_debug_clock",
     "wfahip_debug_team_compact", "wfahip_score_batch", "wfahip_scores_free", "wfahip_score_matrix",
     "wfahip_debug_score_long_list", "wfahip_score_batch_device", "wfahip_debug_score_device_list",
-    "wfahip_align_batch_bounded", "wfahip_align_batch_bounded_device",
+    "wfahip_align_batch_bounded", "wfahip_align_batch_bounded_device", "wfahip_score_batch_packed",
 ]
 
 
@@ -89,6 +89,8 @@ def lib():
         L.wfahip_score_batch.restype = C.c_int
         L.wfahip_score_batch.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, C.POINTER(Scores)]
         L.wfahip_scores_free.argtypes = [C.POINTER(Scores)]
+        L.wfahip_score_batch_packed.restype = C.c_int
+        L.wfahip_score_batch_packed.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, C.POINTER(Scores)]
         L.wfahip_score_matrix.restype = C.c_int
         L.wfahip_score_matrix.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, u64, vp, vp, u64, u32, vp, vp, u64]
         L.wfahip_debug_score_long_list.restype = C.c_int

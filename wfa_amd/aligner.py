@@ -311,6 +311,33 @@ class Aligner:
         finally:
             L.lib().wfahip_scores_free(C.byref(res))
 
+    def score_arrays_packed(self, packed, q_woff, q_len, t_woff, t_len, max_score: int = 0):
+        """score_arrays on pre-packed 2-bit input (include/wfa_hip.h: wfahip_score_batch_packed): takes what pack_pairs() returns,
+        and the same buffer then serves align_arrays_packed for the pairs worth aligning.  Offsets may repeat and come in any order;
+        a quarter of the bytes cross PCIe.  (status, score) equal score_arrays' on the unpacked bytes."""
+        n = int(len(q_len))
+        packed = np.ascontiguousarray(packed, dtype=np.uint32)
+        q_woff = np.ascontiguousarray(q_woff, dtype=np.uint64)
+        t_woff = np.ascontiguousarray(t_woff, dtype=np.uint64)
+        q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+        if len(q_woff) != n or len(t_woff) != n or len(t_len) != n:
+            raise ValueError("offset and length arrays differ in length")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        res = L.Scores()
+        prm = self._params()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = L.lib().wfahip_score_batch_packed(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff),
+                                               vp(t_len), n, int(max_score), C.byref(res))
+        L.check(rc, "wfahip_score_batch_packed" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        try:
+            if n == 0:
+                return np.zeros(0, np.int32), np.zeros(0, np.uint32)
+            return (np.ctypeslib.as_array(res.status, shape=(n,)).copy(), np.ctypeslib.as_array(res.score, shape=(n,)).copy())
+        finally:
+            L.lib().wfahip_scores_free(C.byref(res))
+
     def ScoreBatch(self, qs: Sequence[bytes], ts: Sequence[bytes], max_score: int = 0):
         """(status, score) arrays of the pairs (qs[i], ts[i]): see score_arrays."""
         if len(qs) != len(ts):

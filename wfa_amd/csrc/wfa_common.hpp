@@ -131,11 +131,12 @@ struct KParams {
     // ---- score-only kernels (wfa_score.hpp, wfa_wide_kernel<.., SCORE = true>): no arena, no backtrace
     uint2    *score_out;             // per pair of the batch (index = pair id): {status, score}
     uint32_t  max_score;             // a pair whose score would exceed it stops with ST_OVER_MAX (0 = no bound)
-    // ---- score matrix (wfahip_score_matrix: wfa_score_kernel<true>, wfa_wide_kernel<.., SCORE, MATRIX = true>; wfa_matrix.hpp).  The
+    // ---- score matrix (wfahip_score_matrix: wfa_score_kernel<STAGE_MATRIX>, wfa_wide_kernel<.., SCORE, STAGE_MATRIX>; wfa_matrix.hpp).  The
     // workgroup of index idx takes cell (mx_r0 + idx / mx_cols, mx_c0 + idx % mx_cols) of the matrix and writes score_out[idx]
     // (appended last: the kernel arguments of every other kernel keep their offsets)
     const uint4    *mx_seq;          // per sequence of the table: {word offset lo, hi, length, MXF_* flags}; queries first
-    const uint32_t *mx_words;        // the table's 2-bit packed sequences (wfahip_pack_pairs' layout: word-aligned, one pad word)
+    const uint32_t *mx_words;        // the table's 2-bit packed sequences (wfahip_pack_pairs' layout: word-aligned, one pad word); the packed
+                                     // pair-list instances (STAGE_PACKED): the caller's words, which q_off / t_off then count
     uint64_t        mx_r0, mx_c0;    // the tile's first query and first target
     uint64_t        mx_tbase;        // table index of target 0 (n_q; 0 when the targets are the queries)
     uint32_t        mx_cols;         // targets of the tile

@@ -4,7 +4,7 @@
 //                  long-pair ladder behind it (align_device)
 //   wfa_entry.hip  the host entries: wfahip_align_batch (sliced upload / alignment / download), packed input,
 //                  wfahip_align_pair, submit / collect, the results cache
-//   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_device, wfahip_score_matrix -- a
+//   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_packed, wfahip_score_batch_device, wfahip_score_matrix -- a
 //                  router each over the launch section, the geometry and the full-path fallback they share
 //   wfa_debug.hip  parity and measurement aids: wavefront dumps, the compact arenas, the device-side generator, the clock probe
 #pragma once
@@ -339,6 +339,9 @@ int unpack_results(const std::vector<uint32_t> &rec, const std::vector<uint64_t>
 // wfahip_align_batch behind its guard: the full path the score entries send the pairs their kernels hand back through
 int align_batch_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
                       const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
+// wfahip_align_batch_packed behind its guard: the same for wfahip_score_batch_packed, over a word buffer of that entry's own
+int align_batch_packed_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
 
 // ---- defined in wfa_host.hip
 // the device-resident core behind every entry (exception-safe: the host entry calls it while its upload / download threads are joinable)
@@ -348,11 +351,12 @@ int align_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_blob, ui
 // one workgroup of wfa_backtrace_kernel behind a lone-pair forward launch (wfahip_align_pair)
 hipError_t wfa_launch_backtrace_one(const wfa::KParams &P, hipStream_t st);
 
-// ---- defined in wfa_score.hip: the launches of the score-only kernels (matrix: the instances that take the cells of a tile)
+// ---- defined in wfa_score.hip: the launches of the score-only kernels (stage: wfa_matrix.hpp's STAGE_* -- the byte instances, the
+// matrix ones that take the cells of a tile, the packed pair-list ones; the long kernel's list instance takes packed words as it is)
 namespace wfa {
 struct SDParams;
-hipError_t wfa_launch_score(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
-hipError_t wfa_launch_wide_score(bool matrix, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_score(int stage, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_wide_score(int stage, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st);
 }  // namespace wfa

@@ -771,14 +771,19 @@ extern "C" int wfahip_align_batch_bounded(wfahip_ctx *ctx, const wfahip_params *
 }
 
 // ---- pre-packed input (a quarter of the bytes cross PCIe)
+int align_batch_packed_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out) {
+    if (!ctx || !out || (!packed && n_words)) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs && (!q_woff || !t_woff)) return WFAHIP_ERR_BAD_ARG;
+    static const uint32_t no_words[4] = {0, 0, 0, 0};
+    return align_batch_impl(ctx, p, nullptr, n_words * 16, q_woff, q_len, t_woff, t_len, n_pairs, out, packed ? packed : no_words);
+}
+
 extern "C" int wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
                                          const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff,
                                          const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out) {
-    if (!ctx || !out || (!packed && n_words)) return WFAHIP_ERR_BAD_ARG;
     try {
-        if (n_pairs && (!q_woff || !t_woff)) return WFAHIP_ERR_BAD_ARG;
-        static const uint32_t no_words[4] = {0, 0, 0, 0};
-        return align_batch_impl(ctx, p, nullptr, n_words * 16, q_woff, q_len, t_woff, t_len, n_pairs, out, packed ? packed : no_words);
+        return align_batch_packed_entry(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, n_pairs, out);
     } catch (const std::bad_alloc &) {
         return WFAHIP_ERR_OOM;
     } catch (...) {

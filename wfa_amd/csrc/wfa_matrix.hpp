@@ -2,10 +2,17 @@
 // target).  The host packs each of the n_q + n_t sequences ONCE into a table of 2-bit words and flags it once; a workgroup
 // finds its cell in a rectangular tile, copies the two sequences' packed words into LDS (no byte loads, no packing per cell)
 // and runs the row loop of the kernel it is an instance of, unchanged.
+// The packed pair-list instances (wfahip_score_batch_packed) share the copy: their pairs come as a list of word offsets and lengths
+// over words the CALLER packed (wfahip_pack_pairs' layout), tested per pair as the byte instances test theirs.
 #pragma once
 #include "wfa_common.hpp"
 
 namespace wfa {
+
+// where a score kernel's prologue takes its pair from (template argument STAGE of wfa_score_kernel and the score instances of
+// wfa_wide_kernel): bytes of the call's blob, 2-bit packed by the workgroup (stage_pack); a cell of a tile over the call's sequence
+// table; a pair of the list P.q_off / q_len / t_off / t_len whose offsets count WORDS of P.mx_words
+enum : int { STAGE_BYTES = 0, STAGE_MATRIX = 1, STAGE_PACKED = 2 };
 
 // flags of a sequence of the table (KParams::mx_seq[i].w); a cell takes the status of its two sequences' flags, OR-ed, in the
 // order the kernels test a pair: empty, too long, longer than the kernels take, a byte outside ACGT
@@ -22,7 +29,15 @@ __device__ inline void mx_cell(const KParams &P, uint32_t idx, uint4 &qd, uint4 
     const auto     rfl = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     qd = make_uint4(rfl(a.x), rfl(a.y), rfl(a.z), rfl(a.w)), td = make_uint4(rfl(b.x), rfl(b.y), rfl(b.z), rfl(b.w));
 }
-// words 0 .. (len + 15) / 16 of a packed sequence (the last one the zero pad word) into LDS: stage_pack's layout
+// entry of pair `pair` of a packed pair list (wave-uniform): {word offset lo, hi, length, 0}
+__device__ inline uint4 pk_entry(const uint64_t *woff, uint32_t pair, uint32_t len) {
+    const uint64_t o   = woff[pair];
+    const auto     rfl = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    return make_uint4(rfl((uint32_t)o), rfl((uint32_t)(o >> 32)), len, 0u);
+}
+// words 0 .. (len + 15) / 16 of a packed sequence (the last one its pad word) into LDS: stage_pack's layout.  (Caller-packed words:
+// the pad word and the bits of the last word beyond the sequence may hold anything -- SeqView<0>::lcp clamps to the sequence ends,
+// the seeds read bases inside them)
 template <int G>
 __device__ inline void mx_stage(const uint32_t *words, const uint4 &d, uint32_t *dst, int tid) {
     const uint32_t *const src = words + ((uint64_t)d.y << 32 | d.x);

@@ -1,6 +1,7 @@
 // wfa_score.hip -- translation unit of the score-only kernels behind wfahip_score_batch: wfa_score_kernel (global pairs, any
 // penalty shape score_shape_ok() takes; wfa_score_long_kernel for reads beyond its 2 047 bases) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
-// wfa_fwd_shape.inc), and their matrix instances behind wfahip_score_matrix; and the routing kernels of wfahip_score_batch_device
+// wfa_fwd_shape.inc), their matrix instances behind wfahip_score_matrix and their packed pair-list instances behind
+// wfahip_score_batch_packed; and the routing kernels of wfahip_score_batch_device
 // (wfa_score_dev.hpp).  The routers are wfa_score_entry.hip (score_batch_impl, score_batch_device_impl, score_matrix_impl); the
 // launches below are declared for them in wfa_ctx.hpp.
 #define WFA_NO_AUX_KERNELS 1
@@ -12,14 +13,15 @@
 
 namespace wfa {
 
-// (MATRIX: the instances of wfahip_score_matrix -- a cell of the score matrix per workgroup, wfa_matrix.hpp)
-template <bool MATRIX>
+// (STAGE_MATRIX: the instances of wfahip_score_matrix -- a cell of the score matrix per workgroup; STAGE_PACKED: those of
+// wfahip_score_batch_packed -- a pair of a list over caller-packed words; wfa_matrix.hpp)
+template <int STAGE>
 static hipError_t launch_score(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     if (lds_bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wfa_score_kernel<MATRIX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wfa_score_kernel<STAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(wfa_score_kernel<MATRIX>, dim3(grid), dim3(64), lds_bytes, st, P);
+    hipLaunchKernelGGL(wfa_score_kernel<STAGE>, dim3(grid), dim3(64), lds_bytes, st, P);
     return hipGetLastError();
 }
 
@@ -35,7 +37,7 @@ hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, s
 
 // wfa_wide_kernel<.., SCORE = true> of penalty shape `shape` (wfa_fwd.hpp: fwd_shape()): phase 0 with `waves` waves per pair (1 or 4),
 // phase 1 with one -- as wfa_launch_wide (wfa_host.hip) launches the full-path instances
-template <bool MATRIX>
+template <int STAGE>
 static hipError_t launch_wide_score(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     const auto go = [&](auto kern, int nw) -> hipError_t {
         if (lds_bytes > 64 * 1024) {
@@ -46,9 +48,9 @@ static hipError_t launch_wide_score(int shape, int phase, int waves, const KPara
         return hipGetLastError();
     };
 #define WFA_WIDE_SCORE_SHAPE(I, DX_, DOE_)                                                                      \
-    case 3 * I: return go(wfa_wide_kernel<DX_, DOE_, 0, 1, true, MATRIX>, 1);                                   \
-    case 3 * I + 1: return go(wfa_wide_kernel<DX_, DOE_, 0, 4, true, MATRIX>, 4);                               \
-    case 3 * I + 2: return go(wfa_wide_kernel<DX_, DOE_, 1, 1, true, MATRIX>, 1);
+    case 3 * I: return go(wfa_wide_kernel<DX_, DOE_, 0, 1, true, STAGE>, 1);                                   \
+    case 3 * I + 1: return go(wfa_wide_kernel<DX_, DOE_, 0, 4, true, STAGE>, 4);                               \
+    case 3 * I + 2: return go(wfa_wide_kernel<DX_, DOE_, 1, 1, true, STAGE>, 1);
     switch (shape * 3 + (phase ? 2 : (waves > 1 ? 1 : 0))) {
         WFA_WIDE_SCORE_SHAPE(0, 2, 4)
         WFA_WIDE_SCORE_SHAPE(1, 1, 3)
@@ -61,17 +63,30 @@ static hipError_t launch_wide_score(int shape, int phase, int waves, const KPara
     return hipErrorInvalidValue;
 }
 
-// (instantiated in this order, so that the kernels keep their places in the code object: the batch instances, then the matrix ones)
-template hipError_t launch_score<false>(const KParams &, uint32_t, size_t, hipStream_t);
-template hipError_t launch_wide_score<false>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
-template hipError_t launch_score<true>(const KParams &, uint32_t, size_t, hipStream_t);
-template hipError_t launch_wide_score<true>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
+// (instantiated in this order, so that the kernels keep their places in the code object: the batch instances, then the matrix ones,
+// then the packed pair-list ones)
+template hipError_t launch_score<STAGE_BYTES>(const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_wide_score<STAGE_BYTES>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_score<STAGE_MATRIX>(const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_wide_score<STAGE_MATRIX>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_score<STAGE_PACKED>(const KParams &, uint32_t, size_t, hipStream_t);
+template hipError_t launch_wide_score<STAGE_PACKED>(int, int, int, const KParams &, uint32_t, size_t, hipStream_t);
 
-hipError_t wfa_launch_score(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
-    return !matrix ? launch_score<false>(P, grid, lds_bytes, st) : launch_score<true>(P, grid, lds_bytes, st);
+hipError_t wfa_launch_score(int stage, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    switch (stage) {
+    case STAGE_BYTES: return launch_score<STAGE_BYTES>(P, grid, lds_bytes, st);
+    case STAGE_MATRIX: return launch_score<STAGE_MATRIX>(P, grid, lds_bytes, st);
+    case STAGE_PACKED: return launch_score<STAGE_PACKED>(P, grid, lds_bytes, st);
+    }
+    return hipErrorInvalidValue;
 }
-hipError_t wfa_launch_wide_score(bool matrix, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
-    return !matrix ? launch_wide_score<false>(shape, phase, waves, P, grid, lds_bytes, st) : launch_wide_score<true>(shape, phase, waves, P, grid, lds_bytes, st);
+hipError_t wfa_launch_wide_score(int stage, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    switch (stage) {
+    case STAGE_BYTES: return launch_wide_score<STAGE_BYTES>(shape, phase, waves, P, grid, lds_bytes, st);
+    case STAGE_MATRIX: return launch_wide_score<STAGE_MATRIX>(shape, phase, waves, P, grid, lds_bytes, st);
+    case STAGE_PACKED: return launch_wide_score<STAGE_PACKED>(shape, phase, waves, P, grid, lds_bytes, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 // the routing kernels of wfahip_score_batch_device (wfa_score_dev.hpp): kernel `k` (SDK_*) over `grid` workgroups of SD_BLOCK threads

@@ -18,6 +18,9 @@
 // SCORE_MAX_LEN (ST_REDO_LDS) -- is handed back to the host, which aligns those pairs on the full path.
 // MATRIX (wfahip_score_matrix): the workgroup's pair is a cell of a tile of the score matrix and its sequences come packed from the
 // call's sequence table (wfa_matrix.hpp); the row loop is the same.
+// STAGE_PACKED (wfahip_score_batch_packed): the pair comes from the list like the byte form's, but P.q_off / P.t_off count words of
+// P.mx_words, which the caller packed: the words are copied into LDS as the matrix form copies them -- no byte load, no packing, no
+// ACGT test.
 #pragma once
 #include "wfa_device.hpp"
 #include "wfa_matrix.hpp"
@@ -38,7 +41,7 @@ inline bool score_shape_ok(uint32_t dx, uint32_t doe, uint32_t de) {
 }
 
 #ifdef WFA_SCORE_UNIT  // (the kernel lives in wfa_score.hip only; the host units take the constants)
-template <bool MATRIX = false>
+template <int STAGE = STAGE_BYTES>
 __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int       lane = (int)threadIdx.x;
@@ -58,6 +61,7 @@ __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
     };
     constexpr int BIG = 0x3FFFFFFF;
 
+    constexpr bool MATRIX = STAGE == STAGE_MATRIX;
     const uint32_t idx = blockIdx.x;
     if (idx >= P.chunk_n) return;
     const uint32_t pair = MATRIX ? idx : P.chunk_first + idx;  // (MATRIX: the cell's slot of the tile's output)
@@ -79,7 +83,10 @@ __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
     if (nq > 0x1FFFFFFFu || mt > 0x1FFFFFFFu) return emit(ST_TOO_LONG, 0u);      // wfa.go:207-209
     const uint32_t ml = nq > mt ? nq : mt;
     if (ml > SCORE_MAX_LEN || (ml + 15u) / 16u + 1u > SW) return emit(ST_REDO_LDS, 0u);
-    {
+    if constexpr (STAGE == STAGE_PACKED) {
+        mx_stage<64>(P.mx_words, pk_entry(P.q_off, pair, nq), lq, lane);
+        mx_stage<64>(P.mx_words, pk_entry(P.t_off, pair, mt), lt, lane);
+    } else {
         bool bad = stage_pack<64>(P.blob, P.q_off[pair], nq, lq, lane);
         bad |= stage_pack<64>(P.blob, P.t_off[pair], mt, lt, lane);
         if (__ballot(bad) != 0ull) return emit(ST_REDO_BYTES, 0u);  // a byte outside ACGT: the byte-compare path takes the pair

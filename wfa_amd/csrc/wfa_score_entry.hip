@@ -1,5 +1,6 @@
 // wfa_score_entry.hip -- the score-only entries of the C-ABI (include/wfa_hip.h): wfahip_score_batch (host arrays),
-// wfahip_score_batch_device (device-resident input) and wfahip_score_matrix (every query against every target).  The forward pass
+// wfahip_score_batch_packed (host arrays over caller-packed 2-bit words), wfahip_score_batch_device (device-resident input) and
+// wfahip_score_matrix (every query against every target).  The forward pass
 // without arena or backtrace: wfa_score_kernel for global pairs, wfa_score_long_kernel for global reads beyond its length, the score
 // instances of wfa_wide_kernel for semi-global ones (all launched by wfa_score.hip); whatever they hand back goes through the
 // full path of wfahip_align_batch (wfa_entry.hip).  One router per entry over what they share: the route a call's penalties
@@ -97,7 +98,7 @@ extern "C" void wfahip_scores_free(wfahip_scores *s) {
     s->status = nullptr, s->score = nullptr, s->n = 0;
 }
 
-// ---- what the three routers share
+// ---- what the four routers share
 namespace {
 constexpr uint64_t SD_FB_PAIRS    = 1ull << 20;  // wfahip_score_batch_device, pairs per call of the full path: 64 MB of records
 constexpr uint64_t MX_TILE_GLOBAL = 1ull << 22;  // wfahip_score_matrix, cells per tile of wfa_score_kernel<true>: 32 MB of {status, score}
@@ -142,14 +143,15 @@ int score_geometry(wfahip_ctx *ctx, KParams &P, uint32_t L, uint64_t in_flight, 
     return WFAHIP_OK;
 }
 // ... and the launch of one of them, the P.chunk_n pairs P names: wfa_score_kernel, or the wide kernel's phase 0 and, under
-// wf-adaptive, its phase 1 (matrix: the instances that take the cells of a tile)
-int score_launch_short(wfahip_ctx *ctx, bool matrix, const ScoreRoute &R, const ScoreGeom &G, const KParams &P, hipStream_t st, wfahip_timing &tm) {
+// wf-adaptive, its phase 1 (stage: the instances that take the pairs as P names them -- STAGE_BYTES, STAGE_MATRIX for the cells of a
+// tile, STAGE_PACKED for a list over caller-packed words)
+int score_launch_short(wfahip_ctx *ctx, int stage, const ScoreRoute &R, const ScoreGeom &G, const KParams &P, hipStream_t st, wfahip_timing &tm) {
     if (R.glob) {
-        HIP_TRY(wfa_launch_score(matrix, P, P.chunk_n, G.lds_g, st));
+        HIP_TRY(wfa_launch_score(stage, P, P.chunk_n, G.lds_g, st));
     } else {
-        HIP_TRY(wfa_launch_wide_score(matrix, R.shape, 0, G.waves, P, P.chunk_n, G.lds_w, st));
+        HIP_TRY(wfa_launch_wide_score(stage, R.shape, 0, G.waves, P, P.chunk_n, G.lds_w, st));
         if (G.two_phase) {
-            HIP_TRY(wfa_launch_wide_score(matrix, R.shape, 1, 1, P, P.chunk_n, G.lds_n, st));
+            HIP_TRY(wfa_launch_wide_score(stage, R.shape, 1, 1, P, P.chunk_n, G.lds_n, st));
             tm.n_launches++;
         }
     }
@@ -157,6 +159,24 @@ int score_launch_short(wfahip_ctx *ctx, bool matrix, const ScoreRoute &R, const 
     return WFAHIP_OK;
 }
 
+// The full path's call and its bookkeeping, shared by the byte and the packed fallback: align(&r) aligns the n pairs the caller laid
+// out (under the call's bound), put(k, status, score) takes pair k's result, and the inner call's timing is folded into tm.
+template <class Align, class Put>
+int score_fallback_run(wfahip_ctx *ctx, uint64_t n, uint32_t max_score, bool on_kernel, wfahip_timing &tm, const Align &align, const Put &put) {
+    wfahip_results r;
+    int            rc;
+    {
+        BoundScope bound(ctx, max_score);  // (the full path stops and filters by it: wfahip_align_batch_bounded's path)
+        rc = align(&r);
+    }
+    if (rc) return rc;
+    for (uint64_t k = 0; k < n; k++) put(k, (uint32_t)r.status[k], r.score[k]);
+    wfahip_results_free(&r);
+    const wfahip_timing &f = ctx->timing;
+    tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = std::max(tm.arena_bytes, f.arena_bytes);
+    if (!on_kernel) tm.main_kernel_ms += f.main_kernel_ms, tm.n_main_launches += f.n_main_launches, tm.main_kernel_kind = f.main_kernel_kind;
+    return WFAHIP_OK;
+}
 // The full path for n pairs the kernels handed back (bytes outside ACGT, a band or a length they cannot hold, a shape without an
 // instance), only the score kept: pair k is query pick(k).first against target pick(k).second of the caller's arrays, and its
 // result goes to put(k, status, score) -- ST_OVER_MAX beyond max_score, as the kernels say it.  The timing of the inner call is
@@ -171,28 +191,19 @@ int score_fallback(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_b
         const std::pair<uint64_t, uint64_t> s = pick(k);
         qo[k] = q_off[s.first], ql[k] = q_len[s.first], to[k] = t_off[s.second], tl[k] = t_len[s.second];
     }
-    wfahip_results r;
-    int            rc;
-    {
-        BoundScope bound(ctx, max_score);  // (the full path stops and filters by it: wfahip_align_batch_bounded's path)
-        rc = align_batch_entry(ctx, p, seq_blob, blob_bytes, qo.data(), ql.data(), to.data(), tl.data(), n, &r);
-    }
-    if (rc) return rc;
-    for (uint64_t k = 0; k < n; k++) put(k, (uint32_t)r.status[k], r.score[k]);
-    wfahip_results_free(&r);
-    const wfahip_timing &f = ctx->timing;
-    tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = std::max(tm.arena_bytes, f.arena_bytes);
-    if (!on_kernel) tm.main_kernel_ms += f.main_kernel_ms, tm.n_main_launches += f.n_main_launches, tm.main_kernel_kind = f.main_kernel_kind;
-    return WFAHIP_OK;
+    return score_fallback_run(
+        ctx, n, max_score, on_kernel, tm,
+        [&](wfahip_results *r) { return align_batch_entry(ctx, p, seq_blob, blob_bytes, qo.data(), ql.data(), to.data(), tl.data(), n, r); }, put);
 }
 }  // namespace
 
-// The launch section of a score batch, shared by wfahip_score_batch and wfahip_score_batch_device: P names the batch (device
-// pointers), score_out, the penalties and max_score.  LDS sizing from max_len, chunks of 2^24 (global) / 2^18 (semi-global: the wide
+// The launch section of a score batch, shared by wfahip_score_batch, wfahip_score_batch_packed and wfahip_score_batch_device: P names
+// the batch (device pointers; stage says whether its offsets count bytes of P.blob or words of P.mx_words), score_out, the
+// penalties and max_score.  LDS sizing from max_len, chunks of 2^24 (global) / 2^18 (semi-global: the wide
 // kernel's checkpoints take WIDE_CKPT_WORDS words per pair of a chunk) pairs, the wide kernel's two phases under wf-adaptive, and
 // the n_listed pairs of ctx->mx_seq / mx_words on wfa_score_long_kernel behind the short launch.  Records ctx->ev0 before the
 // first launch and ctx->ev1 behind the last; synchronises nothing.  n_long: the long pairs of the batch (listed or not).
-static int score_launch(wfahip_ctx *ctx, KParams &P, const ScoreRoute &R, uint64_t n_pairs, uint32_t max_len, bool skip_short, uint64_t n_listed,
+static int score_launch(wfahip_ctx *ctx, int stage, KParams &P, const ScoreRoute &R, uint64_t n_pairs, uint32_t max_len, bool skip_short, uint64_t n_listed,
                         uint64_t n_long, hipStream_t st, wfahip_timing &tm, bool &long_main) {
     int            rc;
     const uint32_t L     = std::min<uint32_t>(max_len, R.glob ? SCORE_MAX_LEN : WIDE_MAX_LEN);  // (longer pairs come back ST_REDO_LDS)
@@ -204,7 +215,7 @@ static int score_launch(wfahip_ctx *ctx, KParams &P, const ScoreRoute &R, uint64
     HIP_TRY(hipEventRecord(ctx->ev0, st));
     for (uint64_t c0 = 0; c0 < n_pairs && !skip_short; c0 += chunk) {
         P.chunk_first = (uint32_t)c0, P.chunk_n = (uint32_t)std::min<uint64_t>(chunk, n_pairs - c0);
-        if ((rc = score_launch_short(ctx, false, R, G, P, st, tm))) return rc;
+        if ((rc = score_launch_short(ctx, stage, R, G, P, st, tm))) return rc;
     }
     // the listed long pairs, behind wfa_score_kernel on the same stream: their slots (ST_REDO_LDS there) take the long kernel's result
     long_main = n_listed > n_pairs - n_long;  // it took more pairs of the call than the short kernel
@@ -292,7 +303,7 @@ static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
         P.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), P.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p);
         P.score_out = static_cast<uint2 *>(ctx->score_out.p), P.max_score = max_score;
         bool long_main = false;
-        if ((rc = score_launch(ctx, P, R, n_pairs, max_len, skip_short, n_listed, lp.ids.size(), st, tm, long_main))) return rc;
+        if ((rc = score_launch(ctx, STAGE_BYTES, P, R, n_pairs, max_len, skip_short, n_listed, lp.ids.size(), st, tm, long_main))) return rc;
         HIP_TRY(hipMemcpyAsync(res.data(), ctx->score_out.p, n_pairs * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         float ms = 0;
@@ -329,6 +340,155 @@ extern "C" int wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const
                                   const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
                                   wfahip_scores *out) {
     WFAHIP_GUARD(score_batch_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, max_score, out))
+}
+
+// ---- score only on caller-packed input (wfahip_score_batch_packed): score_batch_impl over the words of wfahip_pack_pairs.  The n_words
+// words go up once, into ctx->mx_words, and the four arrays behind them; the packed pair-list instances of the score kernels copy a
+// pair's words into LDS from there (q_woff / t_woff are their P.q_off / P.t_off), and wfa_score_long_kernel's table points INTO the
+// same words -- eight words per long pair built here, no sequence packed or uploaded a second time.  What the kernels hand back is
+// gathered, those pairs' words only, into a buffer of this entry's own and aligned through the packed full path.
+namespace {
+// words of one sequence as wfahip_pack_pairs writes them: the bits of the last word beyond the last base and the pad word zero
+void copy_packed_seq(const uint32_t *src, uint32_t len, uint32_t *dst) {
+    const uint32_t nw = (len + 15u) >> 4, tail = len & 15u;
+    std::memcpy(dst, src, (size_t)nw * 4);
+    if (tail) dst[nw - 1] &= (1u << (2u * tail)) - 1u;
+    dst[nw] = 0u;
+}
+}  // namespace
+
+static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                                   const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
+                                   wfahip_scores *out) {
+    // (every check before any device work, and none dereferences ctx)
+    if (!ctx || !p || !out) return WFAHIP_ERR_BAD_ARG;
+    std::memset(out, 0, sizeof *out);
+    if (!packed && n_words) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs && (!q_woff || !q_len || !t_woff || !t_len)) return WFAHIP_ERR_BAD_ARG;
+    // every pair that is neither empty nor too long has the words of both sequences, pad words included, inside the buffer (written so
+    // that a hostile 64-bit offset cannot wrap the sum around); the same pass finds the longest read and the long global pairs
+    uint32_t max_len = 1;
+    uint64_t n_long  = 0;
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (!(q_len[i] && t_len[i] && q_len[i] <= WFAHIP_MAX_SEQ_LEN && t_len[i] <= WFAHIP_MAX_SEQ_LEN)) continue;
+        const uint64_t qw = wfahip_packed_words(q_len[i]), tw = wfahip_packed_words(t_len[i]);
+        if (q_woff[i] > n_words || qw > n_words - q_woff[i] || t_woff[i] > n_words || tw > n_words - t_woff[i]) return WFAHIP_ERR_BAD_ARG;
+        const uint32_t ml = std::max(q_len[i], t_len[i]);
+        max_len = std::max(max_len, ml);
+        n_long += ml > SCORE_MAX_LEN;
+    }
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_pairs == 0) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const auto t_start = std::chrono::steady_clock::now();
+    std::vector<uint2> res(n_pairs);
+    wfahip_timing      tm{};
+    KParams            P{};
+    const ScoreRoute   R = score_route(P, p);
+    if (R.on_kernel) {
+        // ---- global pairs beyond wfa_score_kernel's length, when the call holds at least "score_long_min" of them: listed for
+        // wfa_score_long_kernel where they lie in the caller's words
+        const bool         use_long = R.glob && n_pairs <= UINT32_MAX && n_long != 0 && (int64_t)n_long >= ctx->opt_score_long_min;
+        std::vector<uint4> ltab;  // two entries per long pair
+        if (use_long) {
+            ltab.reserve(2 * n_long);
+            for (uint64_t i = 0; i < n_pairs; i++) {
+                if (!(q_len[i] && t_len[i] && q_len[i] <= WFAHIP_MAX_SEQ_LEN && t_len[i] <= WFAHIP_MAX_SEQ_LEN)) continue;
+                if (std::max(q_len[i], t_len[i]) <= SCORE_MAX_LEN) continue;
+                ltab.push_back(make_uint4((uint32_t)q_woff[i], (uint32_t)(q_woff[i] >> 32), q_len[i], (uint32_t)i));
+                ltab.push_back(make_uint4((uint32_t)t_woff[i], (uint32_t)(t_woff[i] >> 32), t_len[i], 0u));
+            }
+        }
+        const uint64_t n_listed   = ltab.size() / 2;
+        const bool     skip_short = use_long && n_long == n_pairs;  // every pair is long: nothing for wfa_score_kernel
+        hipStream_t    st         = ctx->stream;
+        if ((rc = ensure(ctx, ctx->score_out, n_pairs * 8))) return rc;
+        if ((rc = ensure(ctx, ctx->mx_words, (size_t)(n_words + 4) * 4))) return rc;  // (+16 bytes, as in_packed has)
+        ctx->sd_n_words = ctx->sd_n_listed = 0;  // (what wfahip_score_batch_device left there is gone)
+        if (n_words) HIP_TRY(hipMemcpyAsync(ctx->mx_words.p, packed, (size_t)n_words * 4, hipMemcpyHostToDevice, st));
+        if (!skip_short) {
+            if ((rc = ensure(ctx, ctx->in_qoff, n_pairs * 8))) return rc;
+            if ((rc = ensure(ctx, ctx->in_toff, n_pairs * 8))) return rc;
+            if ((rc = ensure(ctx, ctx->in_qlen, n_pairs * 4))) return rc;
+            if ((rc = ensure(ctx, ctx->in_tlen, n_pairs * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->in_qoff.p, q_woff, n_pairs * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_toff.p, t_woff, n_pairs * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+        }
+        if (n_listed) {
+            if ((rc = ensure(ctx, ctx->mx_seq, ltab.size() * 16))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->mx_seq.p, ltab.data(), ltab.size() * 16, hipMemcpyHostToDevice, st));
+        }
+        P.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
+        P.q_off = static_cast<const uint64_t *>(ctx->in_qoff.p), P.t_off = static_cast<const uint64_t *>(ctx->in_toff.p);  // (in words)
+        P.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), P.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p);
+        P.score_out = static_cast<uint2 *>(ctx->score_out.p), P.max_score = max_score;
+        bool long_main = false;
+        if ((rc = score_launch(ctx, STAGE_PACKED, P, R, n_pairs, max_len, skip_short, n_listed, n_long, st, tm, long_main))) return rc;
+        HIP_TRY(hipMemcpyAsync(res.data(), ctx->score_out.p, n_pairs * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        tm.kernel_ms = tm.main_kernel_ms = ms;
+        tm.main_kernel_kind = R.glob ? (long_main ? 23u : 19u) : 20u;
+    } else {
+        for (uint64_t i = 0; i < n_pairs; i++) res[i] = make_uint2(ST_REDO_BAND, 0u);
+    }
+    // ---- what the kernels handed back (a band or a length they cannot hold, a shape without an instance; never ST_REDO_BYTES): those
+    // pairs' words, query then target at fresh offsets, as wfahip_pack_pairs would have written them -- the full path under the bound
+    std::vector<uint64_t> fb;
+    for (uint64_t i = 0; i < n_pairs; i++)
+        if (res[i].x >= ST_REDO_BYTES) fb.push_back(i);
+    if (!fb.empty()) {
+        const uint64_t        n = fb.size();
+        std::vector<uint64_t> qo(n), to(n);
+        std::vector<uint32_t> ql(n), tl(n);
+        uint64_t              pos = 0;
+        // (a shape without an instance hands back EVERY pair, the empty and the too long ones too: the full path says their status from
+        // the lengths alone, and their offsets, which nothing has validated, are never looked at -- they are laid out as wfahip_pack_pairs
+        // lays them out, a pad word each)
+        std::vector<uint8_t> valid(n);
+        for (uint64_t k = 0; k < n; k++) {
+            const uint64_t i = fb[k];
+            ql[k] = q_len[i], tl[k] = t_len[i];
+            valid[k] = ql[k] && tl[k] && ql[k] <= WFAHIP_MAX_SEQ_LEN && tl[k] <= WFAHIP_MAX_SEQ_LEN;
+            qo[k] = pos, pos += wfahip_packed_words(valid[k] ? ql[k] : 0);
+            to[k] = pos, pos += wfahip_packed_words(valid[k] ? tl[k] : 0);
+        }
+        std::vector<uint32_t> words(pos + 4);
+        parallel_ranges(0, n, (unsigned)std::min<uint64_t>(host_pack_threads(16, true), pos / 65536 + 1), [&](uint64_t a, uint64_t b) {
+            for (uint64_t k = a; k < b; k++) {
+                if (!valid[k]) continue;  // (the vector's zeros are its two pad words)
+                copy_packed_seq(packed + q_woff[fb[k]], ql[k], words.data() + qo[k]);
+                copy_packed_seq(packed + t_woff[fb[k]], tl[k], words.data() + to[k]);
+            }
+        });
+        if ((rc = score_fallback_run(
+                 ctx, n, max_score, R.on_kernel, tm,
+                 [&](wfahip_results *r) { return align_batch_packed_entry(ctx, p, words.data(), pos, qo.data(), ql.data(), to.data(), tl.data(), n, r); },
+                 [&](uint64_t k, uint32_t st, uint32_t sc) { res[fb[k]] = make_uint2(st, sc); })))
+            return rc;
+    }
+    tm.n_retried_pairs = (uint32_t)fb.size();
+    out->status = static_cast<int32_t *>(std::malloc(n_pairs * 4));
+    out->score  = static_cast<uint32_t *>(std::malloc(n_pairs * 4));
+    if (!out->status || !out->score) {
+        wfahip_scores_free(out);
+        return WFAHIP_ERR_OOM;
+    }
+    out->n = n_pairs;
+    for (uint64_t i = 0; i < n_pairs; i++) out->status[i] = (int32_t)res[i].x, out->score[i] = res[i].x == ST_OK ? res[i].y : 0u;
+    tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    ctx->timing = tm;
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_score_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                         const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                         uint64_t n_pairs, uint32_t max_score, wfahip_scores *out) {
+    WFAHIP_GUARD(score_batch_packed_impl(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, n_pairs, max_score, out))
 }
 
 // ---- score only on device-resident input (wfahip_score_batch_device): score_batch_impl with everything it does on the host done by
@@ -424,7 +584,7 @@ static int score_batch_device_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
         P.blob = S.blob, P.blob_bytes = blob_bytes, P.q_off = S.q_off, P.t_off = S.t_off, P.q_len = S.q_len, P.t_len = S.t_len;
         P.score_out = S.score_out, P.max_score = max_score;
         bool long_main = false;
-        if ((rc = score_launch(ctx, P, R, n_pairs, max_len, skip_short, n_listed, use_long ? n_long : 0, st, tm, long_main))) return rc;
+        if ((rc = score_launch(ctx, STAGE_BYTES, P, R, n_pairs, max_len, skip_short, n_listed, use_long ? n_long : 0, st, tm, long_main))) return rc;
         tm.main_kernel_kind = R.glob ? (long_main ? 23u : 19u) : 20u;
     }
     // ---- what they handed back (every pair, for a shape without an instance): counted, then gathered in pair order
@@ -648,7 +808,7 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
                     const uint64_t lr = n_lng[t.r0 + t.rr] - n_lng[t.r0], lc = n_lng[tb + t.c0 + t.cc] - n_lng[tb + t.c0];
                     some_long = lr != 0 || lc != 0, all_long = lr == t.rr || lc == t.cc;
                 }
-                if (!all_long && (rc = score_launch_short(ctx, true, R, G, P, st, tm))) return rc;
+                if (!all_long && (rc = score_launch_short(ctx, STAGE_MATRIX, R, G, P, st, tm))) return rc;
                 if (some_long) {
                     KParams PL = P;
                     PL.lds_seq_words = score_long_window(ctx->opt_score_long_window);

@@ -74,11 +74,14 @@ __host__ __device__ inline uint32_t wide_lds_words_narrow(uint32_t seq_words) { 
 // reduce), and one {status, score} per pair goes to P.score_out
 // MATRIX (SCORE only; wfahip_score_matrix): the workgroup's pair is cell idx of a tile of the score matrix, its sequences come packed
 // from the call's sequence table (wfa_matrix.hpp), and its {status, score} goes to P.score_out[idx]; the row loop is the same
-template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1, bool SCORE = false, bool MATRIX = false>
+// STAGE_PACKED (SCORE only; wfahip_score_batch_packed): the pair of the list as in the byte form, its sequences copied from the
+// words the caller packed (P.q_off / P.t_off count words of P.mx_words) -- no byte load, no packing, no ACGT test
+template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1, bool SCORE = false, int STAGE = STAGE_BYTES>
 __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(const KParams P) {
     static_assert(DX >= 1 && DOE >= 1 && DX <= 4 && DOE <= 4, "ring depths of one to four score steps");
     static_assert(NW == 1 || (PHASE == 0 && (NW == 2 || NW == 4)), "the narrow phase is one wave");
-    static_assert(SCORE || !MATRIX, "the matrix instances are score instances");
+    static_assert(SCORE || STAGE == STAGE_BYTES, "the matrix and the packed pair-list instances are score instances");
+    constexpr bool MATRIX = STAGE == STAGE_MATRIX;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int       tid  = (int)threadIdx.x;
     const int       lane = tid & 63;
@@ -149,7 +152,12 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
             status = ST_TOO_LONG;  // wfa.go:207-209
         else if ((nq > mt ? nq : mt) > WIDE_MAX_LEN || ((nq > mt ? nq : mt) + 15u) / 16u + 1u > SW || (PHASE == 0 && wide_row_hw(nq > mt ? nq : mt) > WH))
             status = ST_REDO_LDS;
-        if (status == ST_PENDING) {
+        if constexpr (STAGE == STAGE_PACKED) {
+            if (status == ST_PENDING) {
+                mx_stage<64 * NW>(P.mx_words, pk_entry(P.q_off, pair, nq), lq, tid);
+                mx_stage<64 * NW>(P.mx_words, pk_entry(P.t_off, pair, mt), lt, tid);
+            }
+        } else if (status == ST_PENDING) {
             bool bad = stage_pack<64 * NW>(P.blob, P.q_off[pair], nq, lq, tid);
             bad |= stage_pack<64 * NW>(P.blob, P.t_off[pair], mt, lt, tid);
             bool anybad;
