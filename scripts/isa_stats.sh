@@ -1,6 +1,7 @@
 #!/bin/bash
-# Static instruction mix of one kernel in build/*.s (after `make asm`).  Usage: scripts/isa_stats.sh <mangled-name-substring>
-S=build/asm/wfa_host-hip-amdgcn-amd-amdhsa-gfx950.s
+# Static instruction mix of one kernel in build/*.s (after `make asm`).  Usage: [UNIT=wfa_duo] scripts/isa_stats.sh <mangled-name-substring>
+# (UNIT: the translation unit that holds the kernel, default wfa_host; wfa_duo_kernel: UNIT=wfa_duo scripts/isa_stats.sh wfa_duo_kernelILb0ELi2ELi4E)
+S=build/asm/${UNIT:-wfa_host}-hip-amdgcn-amd-amdhsa-gfx950.s
 K=${1:-wfa_blk_kernelILi16E}
 python3 - "$S" "$K" <<'PY'
 import sys, re

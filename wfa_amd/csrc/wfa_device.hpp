@@ -62,6 +62,13 @@ struct SeqView<0> {
         int w = p >> 4;
         return __funnelshift_r(s[w], s[w + 1], (uint32_t)(p & 15) * 2u);
     }
+    // 32-base window starting at base p, the first 16 bases in .x (needs TWO readable words after the last data word:
+    // the pad word and whatever follows it -- the caller clamps what it counts by the bases that are left)
+    static WFA_DEV uint2 win32(const uint32_t *s, int p) {
+        const int      w  = p >> 4;
+        const uint32_t sh = (uint32_t)(p & 15) * 2u;
+        return make_uint2(__funnelshift_r(s[w], s[w + 1], sh), __funnelshift_r(s[w + 1], s[w + 2], sh));
+    }
     // longest common prefix of q[v:], t[h:] (0-based v, h), clamped to the sequence ends.
     // Equals what the 8-byte block loop + byte tail of wfa.go:410-454 add up to.
     WFA_DEV int lcp(int v, int h) const {

@@ -158,8 +158,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
 
 #ifdef WFA_STAMPS  // diagnostic build (scripts/stamps.sh): time per phase and event counts, summed over the waves
     unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
-    unsigned long long evt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // wave-steps, restructuring rounds, rounds that move rings, parks, resumes,
-                                                            // pairs started, running half-rows, pairs handed on
+    unsigned long long evt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // wave-steps, restructuring rounds, rounds that move rings, parks,
+                                                            // resumes, pairs started, running half-rows, pairs handed on; 8..10: wave-steps that enter
+                                                            // WF_EXTEND's continuation, its outer rounds (a candidate per lane), its inner rounds (windows)
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
 #endif
     const auto pair_of = [&](uint32_t idx) { return P.work ? P.work[idx] : P.chunk_first + idx; };
@@ -638,46 +639,110 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         }
         WFA_STAMP(2);  // next + store
 
-        // ------------------------------------------------------------ WF_EXTEND (wfa.go:381-458), first 16 bases
-        uint32_t cmask = 0u;
+        // ------------------------------------------------------------ WF_EXTEND (wfa.go:381-458)
+        bool nz[PP];  // the cell exists: an extension only adds to an offset, so the test made here holds for the rest of the step
+        if constexpr (WFA_DUO_EXTEND == 0) {  // the form before (wfa_duo_cfg.hpp): first 16 bases, then a candidate at a time, 16 bases a round
+            uint32_t cmask = 0u;
 #pragma unroll
-        for (int p = 0; p < PP; p++) {
-            const int      h    = (int)nM[p];
-            uint32_t       rem;  // max(lim - h, 0): one saturating subtraction
-            asm("v_sub_u32_e64 %0, %1, %2 clamp" : "=v"(rem) : "v"(lim[p]), "v"(h));
-            const uint32_t room = h ? rem : 0u;
-            const int      v    = h - (k0 + p);
-            const uint32_t xr   = SeqView<0>::win16(lq, v) ^ SeqView<0>::win16(lt, h);
-            const uint32_t rn   = umin2(ffbl_raw(xr) >> 1, room);
-            nM[p] += umin2(rn, 16u);
-            if (rn > 16u) cmask |= 1u << p;
-        }
-        while (__ballot(cmask != 0u) != 0ull) {
-            const int psel = (int)ffbl_raw(cmask);
-            int       h = 0, lm = 0;
+            for (int p = 0; p < PP; p++) {
+                const int      h    = (int)nM[p];
+                uint32_t       rem;  // max(lim - h, 0): one saturating subtraction
+                asm("v_sub_u32_e64 %0, %1, %2 clamp" : "=v"(rem) : "v"(lim[p]), "v"(h));
+                const uint32_t room = h ? rem : 0u;
+                const int      v    = h - (k0 + p);
+                const uint32_t xr   = SeqView<0>::win16(lq, v) ^ SeqView<0>::win16(lt, h);
+                const uint32_t rn   = umin2(ffbl_raw(xr) >> 1, room);
+                nM[p] += umin2(rn, 16u);
+                if (rn > 16u) cmask |= 1u << p;
+            }
+            if (__ballot(cmask != 0u) != 0ull) WFA_EVT(8, 1);
+            while (__ballot(cmask != 0u) != 0ull) {
+                WFA_EVT(9, 1);
+                const int psel = (int)ffbl_raw(cmask);
+                int       h = 0, lm = 0;
 #pragma unroll
-            for (int p = 0; p < PP; p++)
-                if (psel == p) h = (int)nM[p], lm = lim[p];
-            const int kd = k0 + psel;
-            bool      go = cmask != 0u;
-            do {
-                const int      rem = lm - h;
-                const uint32_t xr  = SeqView<0>::win16(lq, h - kd) ^ SeqView<0>::win16(lt, h);
-                const uint32_t cnt = umin2(ffbl_raw(xr) >> 1, (uint32_t)imin2(imax2(rem, 0), 16));
-                h += go ? (int)cnt : 0;
-                go = go && xr == 0u && rem > 16;
-            } while (__ballot(go) != 0ull);
+                for (int p = 0; p < PP; p++)
+                    if (psel == p) h = (int)nM[p], lm = lim[p];
+                const int kd = k0 + psel;
+                bool      go = cmask != 0u;
+                do {
+                    WFA_EVT(10, 1);
+                    const int      rem = lm - h;
+                    const uint32_t xr  = SeqView<0>::win16(lq, h - kd) ^ SeqView<0>::win16(lt, h);
+                    const uint32_t cnt = umin2(ffbl_raw(xr) >> 1, (uint32_t)imin2(imax2(rem, 0), 16));
+                    h += go ? (int)cnt : 0;
+                    go = go && xr == 0u && rem > 16;
+                } while (__ballot(go) != 0ull);
 #pragma unroll
-            for (int p = 0; p < PP; p++)
-                if (psel == p) nM[p] = (uint32_t)h;
-            cmask &= cmask - 1u;
+                for (int p = 0; p < PP; p++)
+                    if (psel == p) nM[p] = (uint32_t)h;
+                cmask &= cmask - 1u;
+            }
+#pragma unroll
+            for (int p = 0; p < PP; p++) nz[p] = nM[p] != 0u;
+        } else {
+            // first 16 bases of the lane's four diagonals.  A cell that runs on is a CANDIDATE; the candidates of diagonal p are a lane
+            // mask in scalar registers (the compare's own result), and everything that decides -- any candidate left? which one does a
+            // lane take? does a lane go on? -- is scalar arithmetic on those masks: no flag register to build, test and clear.
+            unsigned long long cm[PP];
+#pragma unroll
+            for (int p = 0; p < PP; p++) {
+                int h = (int)nM[p];
+                nz[p] = h != 0;
+                // (hides from the compiler that h is below 65 536: knowing it, it forms the text's word address as shift, mask and add;
+                // for a value it knows nothing about as shift and shift-add, as it does for the query's)
+                asm("" : "+v"(h));
+                uint32_t rem;  // max(lim - h, 0): one saturating subtraction
+                asm("v_sub_u32_e64 %0, %1, %2 clamp" : "=v"(rem) : "v"(lim[p]), "v"(h));
+                const uint32_t room = nz[p] ? rem : 0u;
+                const int      v    = h - (k0 + p);
+                const uint32_t xr   = SeqView<0>::win16(lq, v) ^ SeqView<0>::win16(lt, h);
+                const uint32_t rn   = umin2(ffbl_raw(xr) >> 1, room);
+                nM[p] = (uint32_t)h + umin2(rn, 16u);
+                cm[p] = __builtin_amdgcn_ballot_w64(rn > 16u);  // (room >= 17: at least one base is left after the 16)
+            }
+            static_assert(PP == 4, "candidate masks of four diagonals");
+            unsigned long long pend = cm[0] | cm[1] | cm[2] | cm[3];
+            if (pend != 0ull) WFA_EVT(8, 1);
+            // continuation: every lane takes its lowest candidate, and the wave runs them together, 32 bases a round
+            while (pend != 0ull) {
+                WFA_EVT(9, 1);
+                const unsigned long long s0 = cm[0], s1 = cm[1] & ~cm[0], s2 = cm[2] & ~(cm[0] | cm[1]), s3 = cm[3] & ~(cm[0] | cm[1] | cm[2]);
+                const bool sel[PP] = {__builtin_amdgcn_inverse_ballot_w64(s0), __builtin_amdgcn_inverse_ballot_w64(s1),
+                                      __builtin_amdgcn_inverse_ballot_w64(s2), __builtin_amdgcn_inverse_ballot_w64(s3)};
+                // a lane without a candidate gets h = lm = 0: nothing left, so it counts nothing and never asks for another round
+                uint32_t h  = sel[PP - 1] ? nM[PP - 1] : 0u;
+                int      kd = k0 + PP - 1;
+#pragma unroll
+                for (int p = PP - 2; p >= 0; p--) h = sel[p] ? nM[p] : h, kd = sel[p] ? k0 + p : kd;
+                // lim[] of that diagonal (a candidate has more than 16 bases left: the lower bound of 1 in lim[] cannot bind)
+                const uint32_t lm = __builtin_amdgcn_inverse_ballot_w64(pend) ? (uint32_t)imin2(n + kd, m) : 0u;
+                // A round counts min(matching bases, bases left, 32); exactly 32 asks for another round.  A lane that has stopped adds
+                // nothing in the rounds the others still need: it stands on a mismatch (the next window counts 0) or on lm (0 left; also
+                // after a round that used up exactly 32: one round for nothing, then it stops).  h <= lm throughout.  The windows may read
+                // one word past a sequence's pad word -- the other sequence, the next buffer or the park area, all inside the wave's LDS:
+                // the count never exceeds the bases left, so none of that can count as a match.
+                unsigned long long go;
+                do {
+                    WFA_EVT(10, 1);
+                    const uint2    wq = SeqView<0>::win32(lq, (int)h - kd), wt = SeqView<0>::win32(lt, (int)h);
+                    const uint32_t b  = umin2(ffbl_raw(wq.x ^ wt.x), ffbl_raw(wq.y ^ wt.y) | 32u);  // first differing bit of the 64; all ones: none
+                    const uint32_t t  = umin2(umin2(b >> 1, lm - h), 32u);
+                    h += t;
+                    go = __builtin_amdgcn_ballot_w64(t == 32u);
+                } while (go != 0ull);
+#pragma unroll
+                for (int p = 0; p < PP; p++) nM[p] = sel[p] ? h : nM[p];
+                cm[0] &= ~s0, cm[1] &= ~s1, cm[2] &= ~s2, cm[3] &= ~s3;
+                pend = cm[0] | cm[1] | cm[2] | cm[3];
+            }
         }
         WFA_STAMP(3);  // extend
 
         // ------------------------------------------------------------ ends reached? termination (wfa.go:235-239)
-        bool nz[PP], hit[PP], hitl = false;
+        bool hit[PP], hitl = false;
 #pragma unroll
-        for (int p = 0; p < PP; p++) nz[p] = nM[p] != 0u, hit[p] = nM[p] >= (uint32_t)lim[p], hitl |= hit[p];
+        for (int p = 0; p < PP; p++) hit[p] = nM[p] >= (uint32_t)lim[p], hitl |= hit[p];
         bool       term    = false;
         const bool hit_any = __ballot(hitl) != 0ull;
         bool       ghit    = false;
@@ -855,7 +920,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     if (lane == 0 && P.debug_info) {
         unsigned long long *acc = reinterpret_cast<unsigned long long *>(P.debug_info);
         for (int i = 0; i < 8; i++) atomicAdd(acc + i, stamp_acc[i]);
-        for (int i = 0; i < 8; i++) atomicAdd(acc + 8 + i, evt[i]);
+        for (int i = 0; i < 16; i++) atomicAdd(acc + 8 + i, evt[i]);
     }
 #endif
 }

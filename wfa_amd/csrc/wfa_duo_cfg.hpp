@@ -25,6 +25,11 @@ namespace wfa {
 #ifndef WFA_DUO_GROUP_MAJOR
 #define WFA_DUO_GROUP_MAJOR 2
 #endif
+// WF_EXTEND of the score step (wfa_duo.hpp): 1 = candidates as lane masks, continuation 32 bases a round (the default);
+// 0 = the form before it (cmask in a register, 16 bases a round), kept for A/B builds: scripts/mkvariant.sh <name> -DWFA_DUO_EXTEND=0
+#ifndef WFA_DUO_EXTEND
+#define WFA_DUO_EXTEND 1
+#endif
 // Arena layout of wfa_duo_kernel (16-bit words; a lane's four diagonals of a score are one 8-byte store, and 8 scores of them
 // one 64-byte piece, in every one of the three):
 //   0  CompactView fmt 7 (round 3) -- tiles of 8 scores x 64 diagonals (1 KB), inside a tile [diagonal / 4][score & 7][diagonal & 3]:

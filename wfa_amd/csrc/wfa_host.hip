@@ -823,8 +823,8 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         P.min_xe        = std::min(P.x, P.e);
 #ifdef WFA_STAMPS
         static DevBuf stampbuf;
-        if ((rc = ensure(ctx, stampbuf, 128))) return rc;
-        HIP_TRY(hipMemsetAsync(stampbuf.p, 0, 128, st));
+        if ((rc = ensure(ctx, stampbuf, 192))) return rc;  // 8 phase sums + 16 event counts (wfa_duo_kernel counts 11; the others 8)
+        HIP_TRY(hipMemsetAsync(stampbuf.p, 0, 192, st));
         P.debug_info = static_cast<uint32_t *>(stampbuf.p);
 #endif
         // one pass over `count` pairs (identity range when list == nullptr); returns the {pair,status} redo entries
@@ -1322,11 +1322,15 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             }
 #ifdef WFA_STAMPS
             {
-                unsigned long long acc[16];
-                HIP_TRY(hipMemcpy(acc, P.debug_info, 128, hipMemcpyDeviceToHost));
+                unsigned long long acc[24];
+                HIP_TRY(hipMemcpy(acc, P.debug_info, 192, hipMemcpyDeviceToHost));
                 std::fprintf(stderr, "[events] wave-steps %llu  slow %llu  hit %llu  reduce %llu  found %llu  found pair-steps %llu  "
                              "continuation iterations %llu  running pair-steps %llu\n", acc[8], acc[9], acc[10], acc[11], acc[12],
                              acc[13], acc[14], acc[15]);
+                // (wfa_duo_kernel only: its eight counts above are wave-steps, restructuring rounds, rounds that move rings, parks, resumes,
+                // pairs started, running half-rows, pairs handed on -- wfa_duo.hpp)
+                std::fprintf(stderr, "[duo extend] wave-steps into the continuation %llu  outer rounds %llu  inner rounds %llu\n", acc[16], acc[17],
+                             acc[18]);
                 unsigned long long tot = 0;
                 for (int i = 0; i < 6; i++) tot += acc[i];
                 const char *nm[6] = {"refill", "next", "extend", "ranges+reduce", "stores", "ring+finish+window"};
