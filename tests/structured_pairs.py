@@ -1,6 +1,6 @@
 """Batches on which WF_EXTEND, the read ends and tied next() sources are what can go wrong (a helper module, no test).
 
-structured_batch(n_pairs, l_min, l_max, seed) builds one batch (once per parameter set) in the layout of wfa_amd.make_blob
+structured_batch(n_pairs, l_min, l_max, seed, wide_every=0) builds one batch (once per parameter set) in the layout of wfa_amd.make_blob
 -- every sequence starts on a 16-byte boundary -- and returns (data, kinds): data = (blob, q_off, q_len, t_off, t_len), read-only;
 kinds[i] names how pair i was built.  The kinds are dealt by index (i mod 10) as tests/test_duo_extend_gpu.py deals them:
   * "ident" (i mod 10 == 0): q == t, one run over the whole read;
@@ -14,15 +14,24 @@ kinds[i] names how pair i was built.  The kinds are dealt by index (i mod 10) as
     window reads the pad word and beyond, and only the clamp by the bases that are left keeps padding from counting;
   * "rep" (5): both reads the same repeat of unit A, C, AC, GT or ACG, lengths 0, 1, 2 or 4 apart, 0 or 2 substitutions by a base
     the unit does not contain, either read the query: every diagonal of a row runs long in the same step, and the sources of
-    next() tie.
-What holds for every batch:
+    next() tie;
+  * "wide" (only with wide_every = w > 0: i mod w == w // 2, whatever i mod 10 would have dealt): t random, q = t with ten
+    substitutions spread evenly over the read, as tests/test_duo_extend_gpu.py builds them -- score 40 at 4/6/2, where without
+    wf-adaptive the band outgrows what wfa_duo_kernel gives a narrow pair.  wide_every = 0 draws nothing from the generator:
+    the batches without wide pairs are what they were before the argument existed.
+What holds for every batch (its wide pairs aside, which have ten substitutions and no gap):
   * the LONGER read of a pair has l_min .. l_max bases -- no read is longer than l_max; the shorter one is at most 4 bases shorter
     (max |m - n| = 4) -- and in every tenth pair of each kind the longer read has exactly l_max bases;
   * every byte is A, C, G or T;
   * a pair differs by at most four substitutions and one 1-base gap ("runs"), one substitution and a 3-base gap ("end"), or two
     substitutions and a 4-base gap ("rep"): at 4/6/2 the global score is at most 24.
 tests/test_structured_pairs.py proves from the oracle alone, for the batches and penalties the GPU tests use, that every row
-next() computes spans at most 28 diagonals and every stored M cell lies within 14 diagonals of the main one, wf-adaptive on or off."""
+next() computes spans at most 28 diagonals and every stored M cell lies within 14 diagonals of the main one, wf-adaptive on or
+off -- and what it proves of the wide pairs' rows instead.
+
+The seam batches put these pairs where the router's integer arithmetic changes a kernel or a layout (wfa_host.hip:
+seq_words = (max_len + 15) / 16 + 1; wfa_duo_kernel's slot PW = 4 + 2 * ((seq_words + 1) & ~1) words, 256 / PW pairs per fetch).
+Every DUO_SEAMS batch spans 16 bases, l_max a multiple of 16: one seq_words class, the longest reads filling its last word."""
 import functools
 
 import numpy as np
@@ -38,6 +47,17 @@ LANE = (400, 224, 240, 20250302)      # up to wfa_lane_kernel's 240 bases; (15 p
 LANE_EDGE = {L: (64, L, L, 20250303 + L) for L in (239, 240, 241)}  # every longer read at, one under and one over the limit
 SCORE_EDGE = (64, 2040, 2047, 20250304)  # up against SCORE_MAX_LEN = 2 047 and the 16-bit ring offsets of the score kernels
 SCORE_LONG = (64, 2048, 2060, 20250305)  # just past it: wfa_score_long_kernel's
+# (n_pairs, l_min, l_max, seed, wide_every) -- wfa_duo_kernel: the 16-base class at both ends of every pairs-per-fetch class (8, 7, 7,
+# 6, 6, 5, 5, 4, 4, 3, 3, 2, 2, 1, 1 pairs); 4 099 pairs: not divisible by 2 .. 8, the queue ends on a partial fetch of every size
+DUO_CLASSES = ((193, 208), (209, 224), (225, 240), (241, 256), (257, 272), (273, 288), (321, 336), (337, 352), (449, 464), (465, 480),
+               (609, 624), (625, 640), (961, 976), (977, 992), (1985, 2000))
+DUO_SEAMS = {c: (4099, c[0], c[1], 20250400 + c[1], 50) for c in DUO_CLASSES}
+# wfa_blk_kernel, 16 lanes: one base past wfa_duo_kernel's 2 000; up to long_min_len = 4 000; up to lds_d = 20 464 of 20 480 bytes
+# (option long = 0); and the far side of that gate
+BLK_SEAMS = {(2001, 2016): (209, 2001, 2016, 20250501), (3985, 4000): (64, 3985, 4000, 20250502),
+             (10193, 10208): (64, 10193, 10208, 20250503), (10209, 10224): (16, 10209, 10224, 20250504)}
+LONG_SEAM = (64, 4001, 4016, 20250505)  # the shortest reads of the sliding-window kernels: the default window repositions once
+S200 = (209, 200, 200, 20250506)        # one base past the short-read instance's max_len < 200
 
 
 def _other(base):
@@ -89,14 +109,25 @@ def _repeat_pair(rng, L, unit, d, n_sub):
     return (a, b) if rng.integers(0, 2) else (b, a)
 
 
+def _wide_pair(rng, L):
+    """ten substitutions, evenly spread (each within 5 bases of its place)"""
+    t = ACGT[rng.integers(0, 4, L)]
+    q = t.copy()
+    for p in np.linspace(12, L - 12, 10).astype(int) + rng.integers(-5, 6, 10):
+        _subst(q, int(p))
+    return q, t
+
+
 @functools.lru_cache(maxsize=None)
-def structured_batch(n_pairs, l_min, l_max, seed):
-    assert 120 <= l_min <= l_max
+def structured_batch(n_pairs, l_min, l_max, seed, wide_every=0):
+    assert 120 <= l_min <= l_max and wide_every >= 0
     rng = np.random.default_rng(seed)
-    seen = {"ident": 0, "runs": 0, "end": 0, "rep": 0}
+    seen = {"ident": 0, "runs": 0, "end": 0, "rep": 0, "wide": 0}
     pairs, kinds = [], []
     for i in range(n_pairs):
         kind = {0: "ident", 3: "end", 7: "end", 5: "rep"}.get(i % 10, "runs")
+        if wide_every and i % wide_every == wide_every // 2:
+            kind = "wide"
         L = int(rng.integers(l_min, l_max + 1))
         if seen[kind] % 10 == 9:
             L = l_max
@@ -109,6 +140,8 @@ def structured_batch(n_pairs, l_min, l_max, seed):
             pair = _end_pair(rng, L, *ENDS[j % len(ENDS)])
         elif kind == "rep":
             pair = _repeat_pair(rng, L, *REPS[j % len(REPS)])
+        elif kind == "wide":
+            pair = _wide_pair(rng, L)
         else:
             pair = _runs_pair(rng, L, *PLAN[(j * 7 + j // len(PLAN)) % len(PLAN)])
         pairs.append(pair), kinds.append(kind)

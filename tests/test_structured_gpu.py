@@ -30,8 +30,9 @@ def _want(batch, glob, pen, ad, ops=True):
     return O.align_batch(_oracle_params(glob, ad, pen), *structured_batch(*batch)[0], n_threads=8, want_ops=ops)
 
 
-def _full(batch, glob, pen, ad, opts, kind, none_handed_on, what):
-    """twice through one aligner over a poisoned arena: kind, records, CIGARs; returns the aligner (still open)"""
+def _full(batch, glob, pen, ad, opts, kind, none_handed_on, what, max_handed_on=None, packed=False):
+    """twice through one aligner over a poisoned arena: kind, records, CIGARs; returns the aligner (still open).
+    max_handed_on: a bound on n_retried_pairs where some pairs may leave; packed: through pack_pairs and align_arrays_packed"""
     data = structured_batch(*batch)[0]
     want = _want(batch, glob, pen, ad)
     assert not np.any(want.status)
@@ -39,14 +40,19 @@ def _full(batch, glob, pen, ad, opts, kind, none_handed_on, what):
     for k, v in opts.items():
         al.set_option(k, v)
     al.set_option("arena_poison", 1)
+    if packed:
+        import wfa_amd
+        words, qw, tw = wfa_amd.pack_pairs(*data)
     for rep in range(2):
-        got = al.align_arrays(*data)
+        got = al.align_arrays_packed(words, qw, data[2], tw, data[4]) if packed else al.align_arrays(*data)
         tm = al.last_timing()
         print(f"{what} pen={pen} ad={ad} rep={rep}: kind {tm.main_kernel_kind}, handed on {tm.n_retried_pairs}")
         if kind is not None:
             assert tm.main_kernel_kind == kind
         if none_handed_on:
             assert tm.n_retried_pairs == 0, f"{what}: pairs left the kernel, their records come from the one behind it"
+        if max_handed_on is not None:
+            assert tm.n_retried_pairs <= max_handed_on, f"{what}: more pairs left the kernel than could have had to"
         assert_batch_equal(got, want, f"{what} pen={pen} ad={ad} rep={rep}")
     return al
 
