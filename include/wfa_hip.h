@@ -123,7 +123,10 @@ typedef struct {
                                   (sliding sequence windows: reads of any length, 64 / 128 / 256 diagonals), 14 / 15 = wfa_blk_kernel<64, 1, false, 1 / 2, .., LONG>
                                   (a wave per pair, one / two diagonals per lane: batches too small to fill the GPU),
                                   16 = wfa_blk_kernel<64, 1, false, 1, false, false> (wfahip_align_pair: one launch, forward pass and backtrace),
-                                  18 = wfa_wide_kernel (round 6: semi-global reads up to 2 047 bases, a workgroup per pair with the rows in 16-bit LDS rings),
+                                  18 = wfa_wide_kernel (round 6: semi-global reads up to 2 047 bases, a workgroup per pair with the rows in 16-bit LDS rings;
+                                  reported whenever one of its launches ran -- a batch of mixed lengths is one launch per length class, and its reads
+                                  beyond 2 047 bases take the ladder: n_packed_pairs = pairs it finished, n_retried_pairs = all the others,
+                                  main_kernel_ms / n_main_launches summed over the classes, arena_bytes the largest class's),
                                   17 = wfa_teamc_kernel (wide wavefronts: a team of workgroups per pair, one backtrace word per diagonal),
                                   19 = wfa_score_kernel (wfahip_score_batch, global pairs), 20 = wfa_wide_kernel<.., SCORE> (wfahip_score_batch,
                                   semi-global pairs), 21 = wfa_score_kernel<MATRIX> (wfahip_score_matrix, global alignment),
@@ -291,7 +294,9 @@ int  wfahip_score_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const vo
  * only for pure uppercase ACGT input -- the reference compares raw bytes (wfa.go:408-454), so anything else must use
  * wfahip_align_batch.  wfahip_pack_pairs is the host-side packer (n_threads host threads; returns
  * WFAHIP_ERR_UNSUPPORTED if a byte outside ACGT is found); packed must hold the sum over all sequences of
- * wfahip_packed_words(len) words.  Results are identical to wfahip_align_batch on the unpacked bytes. */
+ * wfahip_packed_words(len) words.  Results are identical to wfahip_align_batch on the unpacked bytes.
+ * Semi-global batches take wfa_wide_kernel as the byte entry's do (its instances with a packed prologue copy a pair's words
+ * into LDS: no bytes in between); the pairs it hands on are expanded for the ladder like any other pass's. */
 uint64_t wfahip_packed_words(uint32_t len);
 int  wfahip_pack_pairs(const uint8_t *seq_blob, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off,
                        const uint32_t *t_len, uint64_t n_pairs, int n_threads, uint32_t *packed, uint64_t *q_woff,
@@ -401,10 +406,18 @@ int  wfahip_last_timing(const wfahip_ctx *ctx, wfahip_timing *out);
  *                          what outgrows that retries on the 16-lane instance                         default 1
  *   "blk_wide"  0|1        pairs whose band leaves the 64-diagonal window retry on the same kernel with a
  *                          wave per pair (256 diagonals) before the generic kernel takes them       default 1
- *   "wide"  0|1|3          semi-global batches of reads up to "wide_max_len" bases (default 2 047, the kernel's limit) and at least
- *                          "wide_min_pairs" pairs (default 64) start on wfa_wide_kernel (round 6: a workgroup per pair, the
- *                          rows in 16-bit LDS rings of any width; two launches per chunk under wf-adaptive -- wide rows, then
- *                          the narrow tail from a checkpoint); 3: one launch per chunk; 0: on the generic ladder     default 1
+ *   "wide"  0|1|3          the pairs of a semi-global batch whose reads have up to 2 047 bases start on wfa_wide_kernel (round 6: a
+ *                          workgroup per pair, the rows in 16-bit LDS rings of any width; two launches per chunk under wf-adaptive --
+ *                          wide rows, then the narrow tail from a checkpoint) when there are at least "wide_min_pairs" of them
+ *                          (default 64), whatever else the batch holds: longer pairs take the ladder.  3: one launch per chunk;
+ *                          0: on the generic ladder.  "wide_max_len" below 2 047: the batch's longest read decides for the whole
+ *                          batch, as before there were length classes                                               default 1
+ *   "wide_bin_min_pairs"   batches of at least this many pairs are cut into length classes on the device (wfahip_wide_class_bounds;
+ *                          a launch per class, sized by the class's own longest read; a class of fewer than "wide_min_pairs"
+ *                          pairs rides with the next larger one); smaller batches are one class sized by min(longest read,
+ *                          2 047) and the kernel hands the longer pairs on                                        default 4096
+ *   "wide_classes"  0|1    0: a batch that is cut into classes runs as ONE class sized by its longest classed read (A/B runs,
+ *                          tests)                                                                                   default 1
  *   "wide_waves"  0|1|4    waves per pair in its first launch: 0 = by the rings' size (four above 12 KB)          default 0
  *   "matrix_tile_cells"    wfahip_score_matrix: cells per tile (0 = automatic: 4 194 304 global, 262 144 semi-global; tests force
  *                          small tiles so that the tiles split rows and columns)                                default 0
@@ -501,6 +514,20 @@ int  wfahip_debug_score_long_list(const uint8_t *seq_blob, const uint64_t *q_off
  * wfahip_debug_score_long_list returns for the same batch.  *n_words == 0 (and NULL arrays) when that call ran no long pairs on
  * wfa_score_long_kernel; valid until the next score call on ctx.  Caller frees *words and *table with wfahip_free. */
 int  wfahip_debug_score_device_list(wfahip_ctx *ctx, uint32_t **words, uint64_t *n_words, uint32_t **table, uint64_t *n_listed);
+
+/* The length classes semi-global batches are cut into before wfa_wide_kernel takes them: upper bounds of max(q_len, t_len),
+ * strictly ascending, the last one 2 047.  Host only, no device.  Fills bounds[0 .. min(cap, count)) (bounds may be NULL when
+ * cap is 0) and returns the count. */
+int  wfahip_wide_class_bounds(uint32_t *bounds, int cap);
+
+/* Debug / test aid: the plan kernels alone (wfa_wide_plan_*: count per tile, scan, scatter) over host length arrays.  *ids:
+ * n_pairs pair indices -- per class the ascending list of its pairs, class after class, then the ascending list of the pairs
+ * the wide kernel is not offered (both sequences non-empty and within WFAHIP_MAX_SEQ_LEN, the longer one beyond 2 047 bases; a
+ * pair with an empty or over-long sequence is of the smallest class).  counts[c] / longest[c] for each class c of
+ * wfahip_wide_class_bounds (longest: over the class's pairs with two valid sequences, 0 if none); *n_ladder: the length of the
+ * last list.  Caller frees *ids with wfahip_free. */
+int  wfahip_debug_wide_plan(wfahip_ctx *ctx, const uint32_t *q_len, const uint32_t *t_len, uint64_t n_pairs, uint32_t **ids,
+                            uint64_t *counts, uint32_t *longest, uint64_t *n_ladder);
 
 /* Synthetic input generator (host): the seeded dataset spec of DESIGN.md (mirrors what
  * WFA's generate_dataset, used by README.md:298-306, produces: random ACGT pattern of length

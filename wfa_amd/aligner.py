@@ -586,6 +586,29 @@ class Aligner:
             L.lib().wfahip_free(words)
         return arr, int(fmt.value), tuple(int(x) for x in meta)
 
+    def debug_wide_plan(self, q_len, t_len):
+        """(lists, counts, longest, ladder) of the length-class plan of a semi-global batch with these lengths, from the plan
+        kernels alone (include/wfa_hip.h: wfahip_debug_wide_plan): lists[c] = the pair indices of class c of
+        wide_class_bounds(), ascending; counts / longest per class; ladder = the pairs wfa_wide_kernel is not offered."""
+        q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+        n, nc = int(len(q_len)), len(wide_class_bounds())
+        if len(t_len) != n:
+            raise ValueError("q_len and t_len differ in length")
+        ids = C.POINTER(C.c_uint32)()
+        counts, longest, n_ladder = (C.c_uint64 * nc)(), (C.c_uint32 * nc)(), C.c_uint64()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        L.check(L.lib().wfahip_debug_wide_plan(self._ctx, vp(q_len), vp(t_len), n, C.byref(ids), counts, longest, C.byref(n_ladder)),
+                "wfahip_debug_wide_plan")
+        try:
+            flat = np.ctypeslib.as_array(ids, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint32)
+        finally:
+            L.lib().wfahip_free(ids)
+        counts = [int(c) for c in counts]
+        cuts = np.cumsum([0] + counts)
+        lists = [flat[cuts[c]:cuts[c + 1]] for c in range(nc)]
+        return lists, counts, [int(x) for x in longest], flat[cuts[nc]:cuts[nc] + int(n_ladder.value)]
+
     def Plot(self, q: bytes, t: bytes, component: str = "M", notChangeToMatch: bool = False, maxScore: int = -1) -> str:
         """(*Aligner).Plot (wfa_component_plot.go:41): the component table, from the DEVICE wavefronts of one pair."""
         wf, _ = self.debug_wavefronts(q, t)
@@ -625,6 +648,15 @@ def _results_and_errors(br: "BatchResult"):
                           else ErrOverMaxScore if st == L.PAIR_OVER_MAX
                           else WfaError("wfa: out of device memory for this pair"))
     return results, errors
+
+
+def wide_class_bounds() -> List[int]:
+    """Upper bounds of the length classes semi-global batches are cut into (include/wfa_hip.h: wfahip_wide_class_bounds):
+    strictly ascending, the last one 2 047.  Host only."""
+    n = L.lib().wfahip_wide_class_bounds(None, 0)
+    b = (C.c_uint32 * n)()
+    L.lib().wfahip_wide_class_bounds(b, n)
+    return [int(x) for x in b]
 
 
 def pack_pairs(blob, q_off, q_len, t_off, t_len, n_threads: int = 8):

@@ -195,6 +195,11 @@ struct wfahip_ctx {
                                                   // half otherwise), 1 or 4 forced (tests)
     bool          opt_wide_exact           = false; // ... 1: no packed fast path in the wide rows (tests)
     int64_t       opt_wide_min_pairs       = 64;  // ... from this many pairs on (fewer: the one-workgroup-per-pair kernel, whose workgroup is larger than a wave)
+    int64_t       opt_wide_bin_min_pairs   = 4096;// ... batches of at least this many pairs are cut into length classes on the device (wfa_wide_plan.hpp), a launch per class,
+                                                  // and what is longer than 2 047 bases goes to the ladder directly; smaller ones are ONE class sized by min(longest read, 2 047)
+                                                  // and the kernel hands the longer pairs on (ST_REDO_LDS)
+    int64_t       opt_wide_classes         = 1;   // ... 0: a planned batch runs as one class sized by its longest classed read (A/B runs, tests)
+    DevBuf        wide_ids, wide_blk, wide_ctl;   // ... the plan: the classes' pair lists then the ladder's, the tile sums, the control words
     int64_t       opt_duo                  = 1;   // reads of 240+ bases start on wfa_duo_kernel (8 or 16 lanes per pair, changing while the pair runs):
                                                   // 0 never, 1 for batches of at least opt_duo_min_pairs (below that its start-up -- a wave takes one new pair
                                                   // per step -- costs more than the fuller rows give: 1e5 pairs 2.6 vs 2.3 ms), 2 always
@@ -359,4 +364,9 @@ hipError_t wfa_launch_score(int stage, const KParams &P, uint32_t grid, size_t l
 hipError_t wfa_launch_wide_score(int stage, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st);
+// ---- defined in wfa_wide_pk.hip: wfa_wide_kernel's full-alignment instances with the packed prologue, and the three launches of the
+// length-class plan (wfa_wide_plan.hpp)
+struct WPParams;
+hipError_t wfa_launch_wide_packed(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_wide_plan(const WPParams &S, hipStream_t st);
 }  // namespace wfa

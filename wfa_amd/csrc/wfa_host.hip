@@ -21,6 +21,7 @@
 #include "wfa_fwd.hpp"
 #include "wfa_long.hpp"
 #include "wfa_wide.hpp"
+#include "wfa_wide_plan.hpp"
 
 using namespace wfa;
 static_assert(TEAM_SOLO_MAX == 4096, "wfa_ctx.hpp: default of opt_team_solo_max");
@@ -50,7 +51,10 @@ hipError_t wfa_launch_pair(int shape, bool lds_arena, const KParams &P, size_t l
     return hipErrorInvalidValue;
 }
 // wfa_wide_kernel of penalty shape `shape` (wfa_fwd.hpp: fwd_shape()); phase 0 with `waves` waves per pair (1 or 4), phase 1 with one
-hipError_t wfa_launch_wide(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+// (stage: STAGE_BYTES, or STAGE_PACKED for the instances that copy the packed words of a host entry: wfa_wide_pk.hip)
+hipError_t wfa_launch_wide(int stage, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    if (stage == STAGE_PACKED) return wfa_launch_wide_packed(shape, phase, waves, P, grid, lds_bytes, st);
+    if (stage != STAGE_BYTES) return hipErrorInvalidValue;
     const auto go = [&](auto kern, int nw) -> hipError_t {
         if (lds_bytes > 64 * 1024) {  // (per device: the attribute belongs to the kernel as loaded there)
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -353,7 +357,8 @@ extern "C" void wfahip_destroy(wfahip_ctx *ctx) {
     }
     for (DevBuf *b : {&ctx->arena, &ctx->fin, &ctx->team_ctl, &ctx->arena2, &ctx->meta2, &ctx->doneq, &ctx->ctrl, &ctx->redo, &ctx->work, &ctx->meta, &ctx->in_blob, &ctx->in_qoff, &ctx->in_qlen,
                       &ctx->in_toff, &ctx->in_tlen, &ctx->out_rec, &ctx->out_ops, &ctx->in_packed, &ctx->in_small, &ctx->prepack, &ctx->one_ctl, &ctx->page_ctl, &ctx->xbuf, &ctx->wide_ckpt, &ctx->score_out,
-                      &ctx->mx_seq, &ctx->mx_words, &ctx->mx_out, &ctx->sd_ctl, &ctx->sd_blk, &ctx->sd_list, &ctx->sd_redo})
+                      &ctx->mx_seq, &ctx->mx_words, &ctx->mx_out, &ctx->sd_ctl, &ctx->sd_blk, &ctx->sd_list, &ctx->sd_redo, &ctx->wide_ids, &ctx->wide_blk,
+                      &ctx->wide_ctl})
         release(*b);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -485,6 +490,10 @@ static int set_option_impl(wfahip_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_wide = value;
     else if (k == "wide_min_pairs")
         ctx->opt_wide_min_pairs = value;
+    else if (k == "wide_bin_min_pairs")
+        ctx->opt_wide_bin_min_pairs = value;
+    else if (k == "wide_classes")
+        ctx->opt_wide_classes = value;
     else if (k == "matrix_tile_cells")
         ctx->opt_matrix_tile_cells = value > 0 ? value : 0;
     else if (k == "score_long_min")
@@ -549,6 +558,53 @@ extern "C" int wfahip_last_timing(const wfahip_ctx *ctx, wfahip_timing *out) {
 extern "C" void wfahip_free(void *p) { std::free(p); }
 
 extern "C" const char *wfahip_last_error(const wfahip_ctx *ctx) { return ctx ? ctx->last_error : ""; }
+
+extern "C" int wfahip_wide_class_bounds(uint32_t *bounds, int cap) {
+    for (int c = 0; bounds && c < WIDE_N_CLASSES && c < cap; c++) bounds[c] = wide_class_bound(c);
+    return WIDE_N_CLASSES;
+}
+
+// the plan kernels alone (wfa_wide_plan.hpp), as align_device launches them, over host length arrays
+static int debug_wide_plan_impl(wfahip_ctx *ctx, const uint32_t *q_len, const uint32_t *t_len, uint64_t n_pairs, uint32_t **ids, uint64_t *counts,
+                                uint32_t *longest, uint64_t *n_ladder) {
+    *ids = nullptr, *n_ladder = 0;
+    for (int c = 0; c < WIDE_N_CLASSES; c++) counts[c] = 0, longest[c] = 0;
+    if (n_pairs > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs == 0) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t    st    = ctx->stream;
+    const uint32_t tiles = (uint32_t)((n_pairs + WP_TILE - 1) / WP_TILE);
+    int rc;
+    if ((rc = ensure(ctx, ctx->in_qlen, n_pairs * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->in_tlen, n_pairs * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->wide_ctl, WPC_WORDS * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->wide_blk, (size_t)WP_CATS * tiles * 4))) return rc;
+    if ((rc = ensure(ctx, ctx->wide_ids, n_pairs * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+    WPParams S{};
+    S.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), S.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p), S.n = n_pairs, S.tiles = tiles;
+    S.blk = static_cast<uint32_t *>(ctx->wide_blk.p), S.ctl = static_cast<uint32_t *>(ctx->wide_ctl.p), S.ids = static_cast<uint32_t *>(ctx->wide_ids.p);
+    HIP_TRY(wfa_launch_wide_plan(S, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t pc[WPC_WORDS];
+    HIP_TRY(hipMemcpy(pc, S.ctl, sizeof pc, hipMemcpyDeviceToHost));
+    uint32_t *h = static_cast<uint32_t *>(std::malloc((size_t)n_pairs * 4));
+    if (!h) return WFAHIP_ERR_OOM;
+    if (hipMemcpy(h, S.ids, n_pairs * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        std::free(h);
+        return WFAHIP_ERR_HIP;
+    }
+    for (int c = 0; c < WIDE_N_CLASSES; c++) counts[c] = pc[WPC_COUNT + c], longest[c] = pc[WPC_LONGEST + c];
+    *n_ladder = pc[WPC_COUNT + WIDE_N_CLASSES], *ids = h;
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_debug_wide_plan(wfahip_ctx *ctx, const uint32_t *q_len, const uint32_t *t_len, uint64_t n_pairs, uint32_t **ids, uint64_t *counts,
+                                      uint32_t *longest, uint64_t *n_ladder) {
+    if (!ctx || !q_len || !t_len || !ids || !counts || !longest || !n_ladder) return WFAHIP_ERR_BAD_ARG;
+    WFAHIP_GUARD(debug_wide_plan_impl(ctx, q_len, t_len, n_pairs, ids, counts, longest, n_ladder))
+}
 
 // Core: everything device-resident.  keep_debug: run with one slot and keep ctrl debug words.
 static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_blob, uint64_t blob_bytes,
@@ -674,72 +730,158 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
     // ---- semi-global short reads (round 6): wfa_wide_kernel -- a wave per pair, the last rows as 16-bit offsets in LDS rings of
     //      any width, one 16-bit backtrace word per diagonal in the arena -- + the lane-per-pair backtrace kernel, chunk by chunk.
     //      What it cannot hold (bytes outside ACGT, an arena that overflows) goes to the ladder below, like the leftovers of pass 1.
-    if (ctx->opt_packed && ctx->opt_wide != 0 && !debug_single && ctx->force_mode < 0 && !P.global_alignment && P.e != 0u && max_len <= WIDE_MAX_LEN &&
-        (int64_t)max_len <= ctx->opt_wide_max_len && (int64_t)n_pairs >= ctx->opt_wide_min_pairs && !ctx->pk_words) {
+    //      A batch of mixed lengths is cut into the length classes of wfa_wide.hpp first (the plan: wfa_wide_plan.hpp), and every class
+    //      is a launch of its own, sized by its own longest read; pairs beyond the kernel's 2 047 bases go to the ladder directly.
+    const int wide_shape = (!P.global_alignment && P.e != 0u) ? fwd_shape(P.x / P.g, P.oe / P.g, P.e / P.g) : -1;
+    if (ctx->opt_packed && ctx->opt_wide != 0 && !debug_single && ctx->force_mode < 0 && wide_shape >= 0 && (int64_t)n_pairs >= ctx->opt_wide_min_pairs) {
         const uint32_t dx = P.x / P.g, doe = P.oe / P.g, de = P.e / P.g;
-        const int      shape = fwd_shape(dx, doe, de);
-        if (shape >= 0) {
-            const uint32_t seq_words = (max_len + 15) / 16 + 1;
-            const uint32_t row_hw    = wide_row_hw(max_len);
-            const size_t   lds_bytes = (size_t)wide_lds_words(seq_words, max_len) * 4;
-            // rows: with wf-adaptive the n + m - 1 seeds live for a dozen score steps, then a band of a few dozen diagonals; without it
-            // every row keeps them.  (A pair that needs more is re-run by the ladder: ST_REDO_ARENA.)
-            uint64_t words = P.adaptive ? 36ull * max_len + 4096 : 2ull * max_len * (uint64_t)(max_len / 3 + 64) / 2 + 8192;
-            if (ctx->opt_packed_arena_bytes > 0) words = std::max<uint64_t>(1024, ctx->opt_packed_arena_bytes / 4);
-            words = (words + 511) & ~511ull;
-            const uint64_t budget = (uint64_t)((double)ctx->total_mem * 0.35);
-            const uint64_t chunk  = std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, std::min<uint64_t>(budget / (words * 4ull),
-                                                                             ctx->opt_chunk_pairs > 0 ? (uint64_t)ctx->opt_chunk_pairs : ~0ull)));
-            if ((rc = ensure(ctx, ctx->arena, (size_t)(words * 4ull * chunk)))) return rc;
-            if ((rc = ensure(ctx, ctx->meta, chunk * 16))) return rc;
+        const int      shape = wide_shape;
+        const int      stage = ctx->pk_words ? STAGE_PACKED : STAGE_BYTES;  // (packed host entries: the prologue copies the uploaded words)
+        // one launch sequence (chunks of phase 0, phase 1 under wf-adaptive, backtrace) over `n` pairs -- list[0 .. n), device; nullptr: the
+        // identity range -- with everything sized by `longest`
+        struct WideRun {
+            const uint32_t *list;
+            uint64_t        n;
+            uint32_t        longest;
+            uint32_t        seq_words, row_hw;
+            size_t          lds_bytes, lds_narrow;
+            int             waves;
+            uint64_t        words, chunk;
+        };
+        std::vector<WideRun> runs;
+        uint64_t n_ladder = 0;         // pairs the wide kernel is not offered (the plan's last list)
+        uint32_t ladder_longest = 0;
+        const bool     per_pair = ctx->opt_wide_max_len >= (int64_t)WIDE_MAX_LEN;  // (option wide_max_len below the kernel's limit: the batch's longest read decides, as it used to)
+        const bool     lists    = per_pair && (int64_t)n_pairs >= ctx->opt_wide_bin_min_pairs;
+        const uint32_t one_len  = std::min(max_len, WIDE_MAX_LEN);
+        if (!per_pair) {
+            if ((int64_t)max_len <= ctx->opt_wide_max_len) runs.push_back(WideRun{nullptr, n_pairs, max_len});
+        } else if ((!lists && max_len <= WIDE_MAX_LEN) || wide_class_of(max_len) == 0) {
+            runs.push_back(WideRun{nullptr, n_pairs, one_len});  // a small batch, or reads of the smallest class only: one class, no plan
+        } else {
+            // the plan (a small batch with a read beyond 2 047 bases: its counts alone -- whether the kernel would be offered enough pairs;
+            // one class then, and the kernel hands the longer pairs on itself)
+            const uint32_t tiles = (uint32_t)((n_pairs + WP_TILE - 1) / WP_TILE);
+            if ((rc = ensure(ctx, ctx->wide_ctl, WPC_WORDS * 4))) return rc;
+            if ((rc = ensure(ctx, ctx->wide_blk, (size_t)WP_CATS * tiles * 4))) return rc;
+            if (lists && (rc = ensure(ctx, ctx->wide_ids, n_pairs * 4))) return rc;
+            WPParams S{};
+            S.q_len = P.q_len, S.t_len = P.t_len, S.n = n_pairs, S.tiles = tiles;
+            S.blk = static_cast<uint32_t *>(ctx->wide_blk.p), S.ctl = static_cast<uint32_t *>(ctx->wide_ctl.p);
+            S.ids = lists ? static_cast<uint32_t *>(ctx->wide_ids.p) : nullptr;
+            HIP_TRY(wfa_launch_wide_plan(S, st));
+            HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, S.ctl, WPC_WORDS * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            uint32_t pc[WPC_WORDS];
+            std::memcpy(pc, ctx->hpin + HPIN_CTRL, sizeof pc);
+            ctx->timing.n_launches += lists ? 3 : 2;
+            const uint64_t n_l = pc[WPC_COUNT + WIDE_N_CLASSES], n_classed = n_pairs - n_l;
+            if ((int64_t)n_classed < ctx->opt_wide_min_pairs) {
+                // too few pairs for the kernel: the call is routed as it was before there were classes
+            } else if (!lists) {
+                runs.push_back(WideRun{nullptr, n_pairs, one_len});
+            } else {
+                n_ladder = n_l, ladder_longest = pc[WPC_LONGEST + WIDE_N_CLASSES];
+                // a class with fewer pairs than a launch is worth rides with the next larger non-empty one (their lists are neighbours
+                // in ids[]), unless it is the largest; "wide_classes" 0: all of them do
+                int last = -1;
+                for (int c = 0; c < WIDE_N_CLASSES; c++)
+                    if (pc[WPC_COUNT + c]) last = c;
+                uint64_t at = 0, acc_at = 0, acc_n = 0;
+                uint32_t acc_len = 0;
+                for (int c = 0; c <= last; c++) {
+                    const uint64_t cnt = pc[WPC_COUNT + c];
+                    if (cnt == 0) continue;
+                    if (acc_n == 0) acc_at = at;
+                    acc_n += cnt, at += cnt, acc_len = std::max(acc_len, pc[WPC_LONGEST + c]);
+                    if (c == last || (ctx->opt_wide_classes != 0 && (int64_t)acc_n >= ctx->opt_wide_min_pairs)) {
+                        runs.push_back(WideRun{S.ids + acc_at, acc_n, std::max(acc_len, 1u)});
+                        acc_n = 0, acc_len = 0;
+                    }
+                }
+                if (runs.size() == 1 && n_ladder == 0) runs[0].list = nullptr;  // one class, nothing else: the identity range, as for a uniform batch
+            }
+        }
+        if (!runs.empty()) {
             // two launches per chunk when wf-adaptive narrows the rows: the first runs the wide rows, the second -- rings of 256
             // diagonals, the CU's full complement of waves -- the rest (wfa_wide.hpp)
             const bool two_phase = P.adaptive != 0 && ctx->opt_wide >= 1 && ctx->opt_wide != 3;
-            if (two_phase && (rc = ensure(ctx, ctx->wide_ckpt, (size_t)chunk * WIDE_CKPT_WORDS * 4))) return rc;
+            size_t   arena_need = 0, meta_need = 0, ckpt_need = 0;
+            uint64_t ev_need = 0;
+            for (WideRun &r : runs) {
+                const uint32_t len = r.longest;
+                r.seq_words = (len + 15) / 16 + 1;
+                r.row_hw    = wide_row_hw(len);
+                r.lds_bytes = (size_t)wide_lds_words(r.seq_words, len) * 4;
+                r.lds_narrow = (size_t)wide_lds_words_narrow(r.seq_words) * 4;
+                // rows: with wf-adaptive the n + m - 1 seeds live for a dozen score steps, then a band of a few dozen diagonals; without it
+                // every row keeps them.  (A pair that needs more is re-run by the ladder: ST_REDO_ARENA.)
+                uint64_t words = P.adaptive ? 36ull * len + 4096 : 2ull * len * (uint64_t)(len / 3 + 64) / 2 + 8192;
+                if (ctx->opt_packed_arena_bytes > 0) words = std::max<uint64_t>(1024, ctx->opt_packed_arena_bytes / 4);
+                r.words = (words + 511) & ~511ull;
+                // a pair of a chunk costs its arena slot and, in two phases, its checkpoint
+                const uint64_t budget = (uint64_t)((double)ctx->total_mem * 0.35);
+                const uint64_t per_pair_bytes = r.words * 4ull + (two_phase ? (uint64_t)WIDE_CKPT_WORDS * 4ull : 0ull);
+                r.chunk = std::max<uint64_t>(1, std::min<uint64_t>(r.n, std::min<uint64_t>(budget / per_pair_bytes,
+                                                                  ctx->opt_chunk_pairs > 0 ? (uint64_t)ctx->opt_chunk_pairs : ~0ull)));
+                // waves per pair in the first phase: rings above 12 KB leave a SIMD fewer than three one-wave workgroups -- four waves share them
+                r.waves = ctx->opt_wide_waves > 0 ? ctx->opt_wide_waves : (r.lds_bytes > 12 * 1024 ? 4 : 1);
+                arena_need = std::max(arena_need, (size_t)(r.words * 4ull * r.chunk)), meta_need = std::max(meta_need, (size_t)r.chunk * 16);
+                ckpt_need  = std::max(ckpt_need, (size_t)r.chunk * WIDE_CKPT_WORDS * 4);
+                ev_need += 3 * ((r.n + r.chunk - 1) / r.chunk);
+            }
+            // (sized for the largest class before the first launch: growing a buffer frees it, and the launches of the class before still use it)
+            if ((rc = ensure(ctx, ctx->arena, arena_need))) return rc;
+            if ((rc = ensure(ctx, ctx->meta, meta_need))) return rc;
+            if (two_phase && (rc = ensure(ctx, ctx->wide_ckpt, ckpt_need))) return rc;
+            ctx->timing.arena_bytes = std::max<uint64_t>(ctx->timing.arena_bytes, arena_need);
             P.wide_ckpt = static_cast<uint32_t *>(ctx->wide_ckpt.p), P.wide_ckpt_on = two_phase ? 1u : 0u, P.wide_exact = ctx->opt_wide_exact ? 1u : 0u;
-            const size_t lds_narrow = (size_t)wide_lds_words_narrow(seq_words) * 4;
-            // waves per pair in the first phase: rings above 12 KB leave a SIMD fewer than three one-wave workgroups -- four waves share them
-            const int wide_waves = ctx->opt_wide_waves > 0 ? ctx->opt_wide_waves : (lds_bytes > 12 * 1024 ? 4 : 1);
-            ctx->timing.arena_bytes = std::max<uint64_t>(ctx->timing.arena_bytes, words * 4ull * chunk);
             P.dx = dx, P.doe = doe, P.de = de, P.dm = std::max(dx, doe) + 1, P.di = de + 1;
-            P.lds_seq_words = seq_words, P.sub_lds_words = row_hw, P.min_xe = std::min(P.x, P.e);
-            P.arena_words = words, P.compact_fmt = WIDE_FMT;
-            P.prepack = nullptr, P.prepack_words = 0, P.done_q = nullptr, P.done_ctl = nullptr, P.n_stream_wgs = 0, P.work = nullptr;
-            const uint64_t n_chunks = (n_pairs + chunk - 1) / chunk;
-            while (ctx->evpool.size() < 4 * n_chunks) {
+            P.min_xe = std::min(P.x, P.e), P.compact_fmt = WIDE_FMT;
+            P.prepack = nullptr, P.prepack_words = 0, P.done_q = nullptr, P.done_ctl = nullptr, P.n_stream_wgs = 0;
+            P.mx_words = ctx->pk_words;
+            while (ctx->evpool.size() < ev_need) {
                 hipEvent_t e;
                 HIP_TRY(hipEventCreate(&e));
                 ctx->evpool.push_back(e);
             }
             ctrl_zeroed = false;
-            for (uint64_t c = 0; c < n_chunks; c++) {
-                const uint64_t c0 = c * chunk, cn = std::min<uint64_t>(chunk, n_pairs - c0);
-                P.arena = static_cast<uint32_t *>(ctx->arena.p), P.pair_meta = static_cast<uint4 *>(ctx->meta.p);
-                P.chunk_first = (uint32_t)c0, P.chunk_n = (uint32_t)cn;
-                if (c > 0) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 4, st));  // queue_head
-                if (ctx->opt_arena_poison) HIP_TRY(hipMemsetAsync(P.arena, 0xA5, (size_t)(words * 4ull * cn), st));
-                const uint32_t grid = (uint32_t)cn;  // (a workgroup -- one wave -- per pair)
-                HIP_TRY(hipEventRecord(ctx->evpool[4 * c], st));
-                HIP_TRY(wfa_launch_wide(shape, 0, wide_waves, P, grid, lds_bytes, st));
-                if (two_phase) HIP_TRY(wfa_launch_wide(shape, 1, 1, P, grid, lds_narrow, st));
-                HIP_TRY(hipEventRecord(ctx->evpool[4 * c + 1], st));
-                hipLaunchKernelGGL(wfa_backtrace_kernel, dim3((uint32_t)((cn + BT_THREADS - 1) / BT_THREADS)), dim3(BT_THREADS), 0, st, P);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(ctx->evpool[4 * c + 3], st));
+            uint64_t ev_i = 0, last_cn = 0;
+            for (const WideRun &r : runs) {
+                P.lds_seq_words = r.seq_words, P.sub_lds_words = r.row_hw, P.arena_words = r.words;
+                for (uint64_t c0 = 0; c0 < r.n; c0 += r.chunk) {
+                    const uint64_t cn = std::min<uint64_t>(r.chunk, r.n - c0);
+                    P.arena = static_cast<uint32_t *>(ctx->arena.p), P.pair_meta = static_cast<uint4 *>(ctx->meta.p);
+                    P.work = r.list ? r.list + c0 : nullptr;  // (slot idx of the chunk is pair work[idx])
+                    P.chunk_first = (uint32_t)c0, P.chunk_n = (uint32_t)cn;
+                    if (ev_i > 0) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 4, st));  // queue_head
+                    if (ctx->opt_arena_poison) HIP_TRY(hipMemsetAsync(P.arena, 0xA5, (size_t)(r.words * 4ull * cn), st));
+                    const uint32_t grid = (uint32_t)cn;  // (a workgroup -- one wave -- per pair)
+                    HIP_TRY(hipEventRecord(ctx->evpool[ev_i], st));
+                    HIP_TRY(wfa_launch_wide(stage, shape, 0, r.waves, P, grid, r.lds_bytes, st));
+                    if (two_phase) HIP_TRY(wfa_launch_wide(stage, shape, 1, 1, P, grid, r.lds_narrow, st));
+                    HIP_TRY(hipEventRecord(ctx->evpool[ev_i + 1], st));
+                    hipLaunchKernelGGL(wfa_backtrace_kernel, dim3((uint32_t)((cn + BT_THREADS - 1) / BT_THREADS)), dim3(BT_THREADS), 0, st, P);
+                    HIP_TRY(hipGetLastError());
+                    HIP_TRY(hipEventRecord(ctx->evpool[ev_i + 2], st));
+                    ev_i += 3, last_cn = cn;
+                }
             }
+            P.work = nullptr;
             uint32_t              hc[CTRL_WORDS];
             std::vector<uint64_t> redo;
             HIP_TRY(hipEventRecord(ctx->ev1, st));
             if ((rc = fetch_ctrl(hc, &redo))) return rc;
-            ctrl_fresh = true, std::memcpy(hc_last, hc, sizeof hc_last);
-            for (uint64_t c = 0; c < n_chunks; c++) {
+            ctrl_fresh = n_ladder == 0, std::memcpy(hc_last, hc, sizeof hc_last);
+            for (uint64_t e = 0; e < ev_i; e += 3) {
                 float msF = 0, msB = 0;
-                HIP_TRY(hipEventElapsedTime(&msF, ctx->evpool[4 * c], ctx->evpool[4 * c + 1]));
-                HIP_TRY(hipEventElapsedTime(&msB, ctx->evpool[4 * c + 1], ctx->evpool[4 * c + 3]));
+                HIP_TRY(hipEventElapsedTime(&msF, ctx->evpool[e], ctx->evpool[e + 1]));
+                HIP_TRY(hipEventElapsedTime(&msB, ctx->evpool[e + 1], ctx->evpool[e + 2]));
                 ctx->timing.kernel_ms += msF + msB, ctx->timing.main_kernel_ms += msF, ctx->timing.n_main_launches++, ctx->timing.n_launches += 2;
+                if (std::getenv("WFAHIP_DEBUG_TIMING")) std::fprintf(stderr, "[wfahip] wide: launch %llu forward %.3f ms backtrace %.3f ms\n", (unsigned long long)(e / 3), msF, msB);
             }
             if (std::getenv("WFAHIP_WIDE_TRACE")) {  // (debug aid: why the pairs of the last chunk were handed on -- the kernel leaves {status, score index, reason, span})
-                const uint64_t cn = n_pairs - (n_chunks - 1) * chunk;
+                const uint64_t cn = last_cn;
                 std::vector<uint32_t> hm(4 * cn);
                 HIP_TRY(hipMemcpy(hm.data(), ctx->meta.p, 16 * cn, hipMemcpyDeviceToHost));
                 std::map<uint64_t, uint32_t> tally;
@@ -752,15 +894,49 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 for (const auto &kv : tally) std::fprintf(stderr, "[wfahip] wide: status %u reason %u: %u pairs of %llu\n", (uint32_t)(kv.first >> 32), (uint32_t)kv.first, kv.second, (unsigned long long)cn);
             }
             ctx->timing.main_kernel_kind = 18;
-            ctx->timing.n_packed_pairs   = (uint32_t)(n_pairs - redo.size());
-            ctx->timing.n_retried_pairs += (uint32_t)redo.size();
-            Job jb, ja;
+            ctx->timing.n_packed_pairs   = (uint32_t)(n_pairs - redo.size() - n_ladder);
+            ctx->timing.n_retried_pairs += (uint32_t)(redo.size() + n_ladder);
+            // what the kernel hands back for its bytes or its arena is within the kernel's lengths: jobs sized by the longest classed read;
+            // what it hands back for its length (ST_REDO_LDS: a small batch, no plan) keeps the batch's bound.  (A batch without a read
+            // beyond the kernel's limit: the batch's bound for all of them, as before.)
+            uint32_t wide_longest = 0;
+            for (const WideRun &r : runs) wide_longest = std::max(wide_longest, r.longest);
+            Job jb, ja, jl;
             jb.mode = 1, jb.level = 0, jb.all = false;
             ja.mode = 0, ja.level = 0, ja.all = false;
-            for (uint64_t e : redo) ((uint32_t)(e >> 32) == ST_REDO_BYTES ? jb : ja).pairs.push_back((uint32_t)e);
+            jl.mode = 0, jl.level = 0, jl.all = false;
+            if (max_len > WIDE_MAX_LEN) jb.max_len = ja.max_len = wide_longest;
+            for (uint64_t e : redo) {
+                const uint32_t stw = (uint32_t)(e >> 32);
+                (stw == ST_REDO_BYTES ? jb : (stw == ST_REDO_LDS && max_len > WIDE_MAX_LEN ? jl : ja)).pairs.push_back((uint32_t)e);
+            }
             std::sort(ja.pairs.begin(), ja.pairs.end());
-            for (Job *jp : {&ja, &jb})
+            for (Job *jp : {&ja, &jb, &jl})
                 if (!jp->pairs.empty()) jobs.push_back(std::move(*jp));
+            // the pairs the kernel was not offered: jobs of their own, sized by their own longest read -- split where the team kernel
+            // starts, as pass 1 splits its leftovers
+            if (n_ladder) {
+                Job js, jt;
+                js.mode = 0, js.level = 0, js.all = false, js.max_len = ladder_longest;
+                jt.mode = 0, jt.level = 0, jt.all = false, jt.max_len = ladder_longest;
+                std::vector<uint32_t> ids(n_ladder);
+                HIP_TRY(hipMemcpy(ids.data(), static_cast<const uint32_t *>(ctx->wide_ids.p) + (n_pairs - n_ladder), n_ladder * 4, hipMemcpyDeviceToHost));
+                if (ctx->opt_team_min_len > 0 && (int64_t)ladder_longest >= ctx->opt_team_min_len) {
+                    std::vector<uint32_t> ql(n_pairs), tl(n_pairs);
+                    HIP_TRY(hipMemcpy(ql.data(), d_q_len, n_pairs * 4, hipMemcpyDeviceToHost));
+                    HIP_TRY(hipMemcpy(tl.data(), d_t_len, n_pairs * 4, hipMemcpyDeviceToHost));
+                    js.max_len = 0;
+                    for (uint32_t pid : ids) {
+                        const uint32_t l = std::max(ql[pid], tl[pid]);
+                        if ((int64_t)l < ctx->opt_team_min_len) js.pairs.push_back(pid), js.max_len = std::max(js.max_len, l);
+                        else jt.pairs.push_back(pid);
+                    }
+                } else {
+                    js.pairs = std::move(ids);
+                }
+                if (!js.pairs.empty()) jobs.push_back(std::move(js));
+                if (!jt.pairs.empty()) jobs.push_back(std::move(jt));
+            }
             first = false, packed_done = true;
         }
     }
@@ -1736,7 +1912,8 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 const uint32_t stw = (uint32_t)(ent[i] >> 32);
                 (stw == ST_REDO_WIDE ? jw : (stw == ST_REDO_BYTES || stw == ST_REDO_LDS ? jb : ja)).pairs.push_back((uint32_t)ent[i]);
             }
-            ctx->timing.n_retried_pairs += n_redo - (uint32_t)jw.pairs.size();  // (a pair the scouts hand on has not failed anything)
+            // (a pair the scouts hand on has not failed anything; behind wfa_wide_kernel every pair it did not finish has been counted already, once)
+            if (ctx->timing.main_kernel_kind != 18) ctx->timing.n_retried_pairs += n_redo - (uint32_t)jw.pairs.size();
             if (!jw.pairs.empty()) jobs.push_front(std::move(jw));
             if (!jb.pairs.empty()) jobs.push_back(std::move(jb));
             if (!ja.pairs.empty()) jobs.push_back(std::move(ja));

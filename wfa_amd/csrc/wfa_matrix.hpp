@@ -30,8 +30,9 @@ __device__ inline void mx_cell(const KParams &P, uint32_t idx, uint4 &qd, uint4 
     qd = make_uint4(rfl(a.x), rfl(a.y), rfl(a.z), rfl(a.w)), td = make_uint4(rfl(b.x), rfl(b.y), rfl(b.z), rfl(b.w));
 }
 // entry of pair `pair` of a packed pair list (wave-uniform): {word offset lo, hi, length, 0}
-__device__ inline uint4 pk_entry(const uint64_t *woff, uint32_t pair, uint32_t len) {
-    const uint64_t o   = woff[pair];
+// (shift = 4: the offsets count BYTES of the blob the words stand for, 16 to a word -- the full-alignment path, wfa_scale_offsets_kernel)
+__device__ inline uint4 pk_entry(const uint64_t *woff, uint32_t pair, uint32_t len, uint32_t shift = 0u) {
+    const uint64_t o   = woff[pair] >> shift;
     const auto     rfl = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     return make_uint4(rfl((uint32_t)o), rfl((uint32_t)(o >> 32)), len, 0u);
 }

@@ -38,6 +38,22 @@ namespace wfa {
 
 constexpr uint32_t WIDE_MAX_LEN = 2047;  // 16-bit ring offsets and 12-bit arena offsets (blk_word() in a halfword)
 constexpr uint32_t WIDE_FMT     = 11u;   // CompactView: rows of 16-bit blk_word()s + the 16-byte directory of fmt 0
+// Length classes of a batch (wfa_wide_plan.hpp, align_device): a launch's rings, LDS, waves per pair and arena slots are sized by its
+// longest read, so a batch is cut into classes by max(q_len, t_len) and every class gets a launch of its own.  Upper bounds, ascending,
+// the last one WIDE_MAX_LEN; each step about doubles wide_lds_words() (6.0 / 11.5 / 23 / 52 KB).  176 is the longest read whose ring rows
+// are 448 halfwords -- 150-base reads with their indels stay in the smallest class, whose 6 KB still let a CU hold more one-wave
+// workgroups (26) than its SIMDs take waves (20) -- and 400 the longest whose first-phase LDS stays under the 12 KB at which a launch
+// goes from one wave per pair to four.  THE table: nothing else spells it.
+constexpr int WIDE_N_CLASSES = 4;
+__host__ __device__ constexpr uint32_t wide_class_bound(int c) { return c == 0 ? 176u : c == 1 ? 400u : c == 2 ? 864u : WIDE_MAX_LEN; }
+static_assert(WIDE_N_CLASSES >= 2 && WIDE_N_CLASSES <= 6 && wide_class_bound(WIDE_N_CLASSES - 1) == WIDE_MAX_LEN, "two to six classes, the last one the kernel's limit");
+// class of a read length in [0, WIDE_MAX_LEN]; WIDE_N_CLASSES: longer than the kernel takes
+__host__ __device__ inline int wide_class_of(uint32_t len) {
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < WIDE_N_CLASSES; i++) c += len > wide_class_bound(i) ? 1 : 0;
+    return c;
+}
 // halfwords of one ring row: a slot per diagonal of [-(n-1), m-1] plus guards on both sides, a multiple of 64
 __host__ __device__ inline uint32_t wide_row_hw(uint32_t max_len) { return (2u * max_len + 96u + 63u) & ~63u; }
 // LDS words of a wave: the two packed sequences, then the six rows
@@ -74,13 +90,14 @@ __host__ __device__ inline uint32_t wide_lds_words_narrow(uint32_t seq_words) { 
 // reduce), and one {status, score} per pair goes to P.score_out
 // MATRIX (SCORE only; wfahip_score_matrix): the workgroup's pair is cell idx of a tile of the score matrix, its sequences come packed
 // from the call's sequence table (wfa_matrix.hpp), and its {status, score} goes to P.score_out[idx]; the row loop is the same
-// STAGE_PACKED (SCORE only; wfahip_score_batch_packed): the pair of the list as in the byte form, its sequences copied from the
-// words the caller packed (P.q_off / P.t_off count words of P.mx_words) -- no byte load, no packing, no ACGT test
+// STAGE_PACKED (wfahip_score_batch_packed; full alignment: the host entries with packed input): the pair of the list as in the byte form,
+// its sequences copied from the words the caller packed (P.q_off / P.t_off count words of P.mx_words; full alignment: bytes of the blob
+// those words stand for, 16 to a word) -- no byte load, no packing, no ACGT test
 template <int DX = 2, int DOE = 4, int PHASE = 0, int NW = 1, bool SCORE = false, int STAGE = STAGE_BYTES>
 __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(const KParams P) {
     static_assert(DX >= 1 && DOE >= 1 && DX <= 4 && DOE <= 4, "ring depths of one to four score steps");
     static_assert(NW == 1 || (PHASE == 0 && (NW == 2 || NW == 4)), "the narrow phase is one wave");
-    static_assert(SCORE || STAGE == STAGE_BYTES, "the matrix and the packed pair-list instances are score instances");
+    static_assert(SCORE || STAGE != STAGE_MATRIX, "the matrix instances are score instances");
     constexpr bool MATRIX = STAGE == STAGE_MATRIX;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int       tid  = (int)threadIdx.x;
@@ -154,8 +171,9 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
             status = ST_REDO_LDS;
         if constexpr (STAGE == STAGE_PACKED) {
             if (status == ST_PENDING) {
-                mx_stage<64 * NW>(P.mx_words, pk_entry(P.q_off, pair, nq), lq, tid);
-                mx_stage<64 * NW>(P.mx_words, pk_entry(P.t_off, pair, mt), lt, tid);
+                // (full alignment, packed host entries: P.mx_words = the uploaded words, word i bytes [16 i, 16 i + 16) of the blob P.q_off / P.t_off count)
+                mx_stage<64 * NW>(P.mx_words, pk_entry(P.q_off, pair, nq, SCORE ? 0u : 4u), lq, tid);
+                mx_stage<64 * NW>(P.mx_words, pk_entry(P.t_off, pair, mt, SCORE ? 0u : 4u), lt, tid);
             }
         } else if (status == ST_PENDING) {
             bool bad = stage_pack<64 * NW>(P.blob, P.q_off[pair], nq, lq, tid);
