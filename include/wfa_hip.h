@@ -447,6 +447,9 @@ int  wfahip_last_timing(const wfahip_ctx *ctx, wfahip_timing *out);
  *                                 it did not write in this launch)
  *   "duo_pk"  0|1                 1 (default): wfa_duo_kernel holds its rings as 16-bit pairs; 0: its 32-bit-ring reference
  *                                 wfa_duo32_kernel (tests and A/B runs: both write the same arena words, byte for byte)
+ *   "duo_claim"  1..8             wfa_duo_kernel: the most fetches a wave claims with one atomic on the pair queue's head word; above 1 a
+ *                                 wave also starts with eight entries of its own.  1: one fetch per atomic from entry 0 on, as before
+ *                                 there were blocks (tests and A/B runs: results do not depend on it)                    default 4
  *   "team_paged"  0|1             1 (default): the teams of the long-pair kernel share ONE pool of arena pages -- a pair holds what it
  *                                 needs, up to eight teams run at once -- instead of a slot each sized for the worst pair
  *   "team_xcd"  0|1|2             teams of one XCD's 32 CUs (1); 2 (default): ... and a team that finds all its workgroups on one

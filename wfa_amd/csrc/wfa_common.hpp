@@ -140,6 +140,8 @@ struct KParams {
     uint64_t        mx_r0, mx_c0;    // the tile's first query and first target
     uint64_t        mx_tbase;        // table index of target 0 (n_q; 0 when the targets are the queries)
     uint32_t        mx_cols;         // targets of the tile
+    // ---- wfa_duo_kernel's queue claims (wfa_duo.hpp; appended last for the same reason)
+    uint32_t        duo_claim;       // most fetches a wave claims with one atomic on queue_head, 1 .. 8; 1: one fetch per atomic and no first block
 };
 
 }  // namespace wfa

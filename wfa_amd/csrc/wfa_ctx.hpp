@@ -205,7 +205,9 @@ struct wfahip_ctx {
                                                   // per step -- costs more than the fuller rows give: 1e5 pairs 2.6 vs 2.3 ms), 2 always
     int64_t       opt_duo_min_pairs        = 200000;
     bool          opt_duo_pk               = true;  // wfa_duo_kernel's rings as 16-bit pairs; false: the 32-bit reference wfa_duo32_kernel (tests, A/B)
-    int64_t       opt_duo_short            = 0;   // 1 / 2: batches of short reads (<= 240 bases) use it too, with eight pairs per fetch.  Off: measured
+    int64_t       opt_duo_claim            = 0;   // wfa_duo_kernel: most fetches per queue claim, 1 .. 8; 0 = the compiled default (wfa_duo_cfg.hpp: DUO_CLAIM); 1 = one
+                                                  // fetch per atomic and no first block, the claiming before blocks (tests, A/B)
+    int64_t       opt_duo_short            = 0;  // 1 / 2: batches of short reads (<= 240 bases) use it too, with eight pairs per fetch.  Off: measured
                                                   // SLOWER than the batched 8-lane instance (1e5 x 150 bp: forward 0.317 vs 0.249 ms, 1e6: 1.60 vs 1.43 ms, plus the
                                                   // packing kernel) -- a 150-base pair lives ten steps, so a wave restructures on nearly every step
     int64_t       opt_duo_short_min_pairs  = 50000;

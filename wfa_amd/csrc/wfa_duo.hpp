@@ -151,9 +151,34 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     // (one word of flags, not four bools: hipcc merges the stores to two bools into one store through a selected address,
     // which pins both in scratch memory -- two scratch loads per score step)
     constexpr uint32_t PF_TOK = 1u, PF_LD = 2u, PF_STAGED = 4u, PF_DRY = 8u;  // queue atomic in flight / slot loads in flight / a pair staged in LDS / queue exhausted
-    uint32_t pf = 0u;
+    // Queue claims.  One returning atomic per fetch on the ONE head word is a ceiling of its own: the word serves about 88 claims
+    // a microsecond whatever the waves do in between (KERNELS.md 4a, "Queue claims"), and 1e6 pairs of 1 kbp are 1e6 fetches.
+    // So a wave claims BLOCKS of fetches: [pf_next, pf_end) are the entries it has claimed and not fetched yet, and only an empty
+    // range costs an atomic.
+    //   * the first block needs none: wave w owns [8 w, 8 w + 8) -- a pair per half row; the launch's grid is at most
+    //     ceil(chunk_n / 8) waves, so these blocks are disjoint and cover a prefix -- and the head word, which the host zeroes,
+    //     hands out the entries from 8 * gridDim.x on (claim_base());
+    //   * a claim is B fetches, B = clamp((chunk_n - pf_next) / (2 * gridDim.x * FP), 1, duo_claim) with pf_next the end of the
+    //     wave's last range: guided, so that near the queue's end every claim is one fetch and the launch's tail is what it was
+    //     (a fixed B would leave one wave with up to B - 1 unstarted fetches while the others leave);
+    //   * duo_claim = 1 (debug option): no first block, one fetch per atomic from entry 0 on -- the claiming before blocks.
+    // The head word cannot wrap: a wave stops claiming at the first token at or past chunk_n, so the word ends at most
+    // gridDim.x * duo_claim * FP <= 4 096 * 8 * 8 entries past chunk_n, and a chunk's pairs own an arena of at least 4 KB each
+    // inside a third of the device's memory -- tens of millions of pairs, not 2^32.
+    // duo_claim and gridDim.x ride in the spare bits of the flags word (PF_CLAIM_SHIFT, PF_GRID_SHIFT; wfa_host.hip keeps the grid
+    // under 65 536): the kernel runs at the limit of its scalar registers, and as two more loop invariants they pushed a mask of the
+    // score step out to a vector register's lanes -- two v_readlane a step.  They are read where a wave claims, nowhere else.
+    constexpr uint32_t PF_CLAIM_SHIFT = 8u, PF_GRID_SHIFT = 16u;
+    uint32_t pf = (umax2(1u, umin2(P.duo_claim, (uint32_t)DUO_CLAIM_MAX)) << PF_CLAIM_SHIFT) | (gridDim.x << PF_GRID_SHIFT);
     uint32_t pf_tok = 0u, pf_ld_idx = 0u, pf_idx = 0u, pf_buf = 0u;
     uint32_t st_mask = 0u;  // buffers of the staged pairs, lowest bit = next pair (queue entry pf_idx)
+    uint32_t pf_next = P.duo_claim > 1u ? blockIdx.x * 8u : 0u;
+    uint32_t pf_end  = P.duo_claim > 1u ? umin2(pf_next + 8u, P.chunk_n) : 0u;
+    const auto claim_base = [&]() { return ((pf >> PF_CLAIM_SHIFT) & 15u) > 1u ? (pf >> PF_GRID_SHIFT) * 8u : 0u; };
+    const auto claim_fetches = [&]() {
+        const uint32_t rem = P.chunk_n > pf_next ? P.chunk_n - pf_next : 0u;
+        return umax2(1u, umin2((pf >> PF_CLAIM_SHIFT) & 15u, rem / (2u * (pf >> PF_GRID_SHIFT) * FP)));
+    };
     uint4    pf_w = make_uint4(0u, 0u, 0u, 0u);  // (a slot is at most 256 words: one 16-byte load per lane)
 
 #ifdef WFA_STAMPS  // diagnostic build (scripts/stamps.sh): time per phase and event counts, summed over the waves
@@ -212,8 +237,11 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         park_used = (uint32_t)__builtin_amdgcn_readfirstlane((int)park_used);
         buf_free  = (uint32_t)__builtin_amdgcn_readfirstlane((int)buf_free);
         st_mask   = (uint32_t)__builtin_amdgcn_readfirstlane((int)st_mask);
+        pf_next   = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_next);
+        pf_end    = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_end);
         if ((pf & (PF_LD | PF_STAGED)) == PF_LD) {  // the words loaded an iteration ago go to spare LDS buffers, one per pair
-            const uint32_t cnt = umin2(FP, P.chunk_n - pf_ld_idx);  // pairs this fetch really holds
+            // pairs this fetch really holds: the stage below moved pf_next past them an iteration ago, and nothing has moved it since
+            const uint32_t cnt = pf_next - pf_ld_idx;
             // the cnt lowest free buffers: slot s of the fetch goes to the s-th of them
             st_mask = 0u;
             {
@@ -231,24 +259,34 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             pf_idx = pf_ld_idx, pf = (pf | PF_STAGED) & ~PF_LD;
         }
         if ((pf & (PF_TOK | PF_LD)) == PF_TOK) {  // the queue entry claimed an iteration ago: its slot's words into registers
-            pf_ld_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_tok);
-            const bool have = pf_ld_idx < P.chunk_n;
+            if (pf_next >= pf_end) {  // (the wave's range was empty: the token is an atomic's result, the start of a new range)
+                const uint32_t tok = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_tok) + claim_base();
+                const uint32_t blk = claim_fetches() * FP;  // (what the atomic added: pf_next has not moved since)
+                pf_next = tok, pf_end = tok < P.chunk_n ? umin2(tok + blk, P.chunk_n) : tok;
+            }
+            pf_ld_idx = pf_next;
+            const bool have = pf_next < pf_end;  // (an empty range: the token was at or past chunk_n)
             if (have) {
                 const uint32_t *const slot = P.prepack + (uint64_t)pf_ld_idx * PW;
-                const uint32_t cnt = umin2(FP, P.chunk_n - pf_ld_idx);
+                const uint32_t cnt = umin2(FP, pf_end - pf_next);  // (the last fetch of a range or of the chunk may be partial)
+                pf_next += cnt;
                 if ((uint32_t)lane * 4u < cnt * PW) pf_w = *reinterpret_cast<const uint4 *>(slot + lane * 4);
             }
             pf = (pf & ~PF_TOK) | (have ? PF_LD : PF_DRY);
         }
         if ((pf & (PF_TOK | PF_DRY)) == 0u) {
-            // FP queue entries, by lane 0, result NOT awaited here: the library is built with
+            // The next fetch: from the wave's range when it has entries left -- no memory operation, the token is pf_next -- else
+            // claim_fetches() * FP queue entries, by lane 0, result NOT awaited here: the library is built with
             // -mllvm -amdgpu-atomic-optimizer-strategy=None (Makefile).  With LLVM's atomic optimizer on, this atomicAdd()
             // becomes a wave-aggregated atomic followed AT ONCE by s_waitcnt + v_readfirstlane -- a memory round trip during
             // which the wave's pairs stand still, every four steps; without it the wait sits where the token is read, a
             // score step later.  (An earlier form issued the atomic as inline assembly: same timing, but the compiler then
             // does not know the result is outstanding, and a register copy or a spill of it before the wait would read
             // garbage.  Correct either way with this form; the flag only buys the overlap.)
-            if (lane == 0) pf_tok = atomicAdd(P.queue_head, FP);
+            if (pf_next >= pf_end) {
+                const uint32_t blk = claim_fetches() * FP;
+                if (lane == 0) pf_tok = atomicAdd(P.queue_head, blk);
+            }
             pf |= PF_TOK;
         }
         // ---------------------------------------------------------------- does anything have to change?

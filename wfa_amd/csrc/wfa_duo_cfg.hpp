@@ -30,6 +30,13 @@ namespace wfa {
 #ifndef WFA_DUO_EXTEND
 #define WFA_DUO_EXTEND 1
 #endif
+// Queue claims of the prefetch (wfa_duo.hpp): the most fetches a wave claims with one atomic on the queue's head word, 1 .. 8.  Above 1 a wave
+// also starts with eight entries of its own, no atomic; 1 = one fetch per atomic from entry 0 on (the claiming before blocks), kept for A/B
+// builds -- scripts/mkvariant.sh <name> -DWFA_DUO_CLAIM=1 -- and, as debug option duo_claim, for the tests.  4 measured best: 1e6 x 1 kbp at
+// 4/6/2 14.33 ms a step against 14.35 with 2 and 14.46 with 8, at 2/4/2 9.13 against 9.25 and 9.18 (profiles/r09_duo_claim.txt)
+#ifndef WFA_DUO_CLAIM
+#define WFA_DUO_CLAIM 4
+#endif
 // Arena layout of wfa_duo_kernel (16-bit words; a lane's four diagonals of a score are one 8-byte store, and 8 scores of them
 // one 64-byte piece, in every one of the three):
 //   0  CompactView fmt 7 (round 3) -- tiles of 8 scores x 64 diagonals (1 KB), inside a tile [diagonal / 4][score & 7][diagonal & 3]:
@@ -49,6 +56,9 @@ constexpr int DUO_FETCH_MAX  = 8;                      // short reads: pairs per
 constexpr int DUO_WIDEN_AT   = WFA_DUO_WIDEN_AT;       // a narrow pair whose band spans more diagonals than this widens (a recentred band must fit 32 - 6)
 constexpr int DUO_NARROW_AT  = WFA_DUO_NARROW_AT;      // a wide pair whose band spans at most this many narrows
 constexpr int DUO_WIDE_MAX   = 56;                     // a wide pair whose band spans more is handed on
+constexpr int DUO_CLAIM_MAX  = 8;                      // most fetches per queue claim (KParams::duo_claim, 1 .. DUO_CLAIM_MAX)
+constexpr int DUO_CLAIM      = WFA_DUO_CLAIM;          // ... and the default
+static_assert(DUO_CLAIM >= 1 && DUO_CLAIM <= DUO_CLAIM_MAX, "WFA_DUO_CLAIM: 1 .. 8 fetches per claim");
 
 // pairs one fetch brings in: the slots of consecutive queue entries are contiguous in the prepack buffer, and one
 // 16-byte load per lane covers 256 words -- eight slots of a 150-base pair, one of a 1 kbp pair

@@ -510,6 +510,8 @@ static int set_option_impl(wfahip_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_duo = value;
     else if (k == "duo_pk")
         ctx->opt_duo_pk = value != 0;
+    else if (k == "duo_claim")
+        ctx->opt_duo_claim = (value >= 1 && value <= DUO_CLAIM_MAX) ? value : 0;
     else if (k == "duo_min_pairs")
         ctx->opt_duo_min_pairs = value;
     else if (k == "compact_call_bases")
@@ -1181,6 +1183,10 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 if (ctx->opt_arena_poison) HIP_TRY(hipMemsetAsync(P.arena, 0xA5, (size_t)(words * 4ull * cn), st));
                 HIP_TRY(hipEventRecord(evFa, st));
                 if (kind == 8) {
+                    // (the first blocks of the kernel's queue claims rest on this launch's grid: at most ceil(cn / 8) waves, and the
+                    // kernel keeps the grid in 16 bits of its flags word)
+                    if (grid > 0xFFFFu || pairs_wave != 8) return WFAHIP_ERR_INTERNAL;
+                    P.duo_claim = ctx->opt_duo_claim > 0 ? (uint32_t)ctx->opt_duo_claim : (uint32_t)DUO_CLAIM;
                     HIP_TRY(wfa_launch_duo(shape, P, grid, lds_bytes, st, P.census != 0, ctx->opt_duo_pk));
                 } else if (kind >= 3) {
                     uint32_t fl = (P.census ? (uint32_t)FWD_CENSUS : 0u) | (P.adaptive ? (uint32_t)FWD_ADAPTIVE : 0u);
