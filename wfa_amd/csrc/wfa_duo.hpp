@@ -226,6 +226,87 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         return r;
     };
 
+    // ================================================================ free halves: parked pairs first, then the staged pair
+    // ph = the phase of the NEXT score step: a resumed record's row r, its r-th oldest, goes to M[(ph + r) mod R], and M[ph] is the row that
+    // step replaces.  Two callers: the finish branch of step(), for the half it has just freed (WFA_DUO_FILL, wfa_duo_cfg.hpp), and a
+    // restructuring round of refill() for what the finish could not place.  Wave-uniform throughout -- m_free is a ballot, the masks and
+    // flags are scalars, the staged pair's header words come through readfirstlane -- and the caller follows it with set_derived() and
+    // the wave's two fences.
+    const auto fill = [&](auto ph_c, unsigned long long m_free) __attribute__((always_inline)) {
+        constexpr int ph = decltype(ph_c)::value;
+        while (m_free != 0ull && (park_used != 0u || (pf & PF_STAGED) != 0u)) {
+            const uint32_t oct  = (uint32_t)__builtin_ctzll(m_free) >> 3;  // wave-uniform
+            const bool     mine = ((uint32_t)lane >> 3) == oct;
+            if (park_used != 0u) {
+                const uint32_t rec = (uint32_t)__builtin_ctz(park_used);
+                park_used &= park_used - 1u;
+                WFA_EVT(4, 1);
+                const uint32_t *const pr = park0 + rec * DUO_PARK_WORDS;
+                if (mine) {
+                    // (record row r -> M[(ph + r) mod R]: the phase of the resuming wave, not of the one that parked it)
+                    const uint4 *const w = reinterpret_cast<const uint4 *>(pr + 12 * l7);
+                    const uint4 v0 = w[0], v1 = R > 2 ? w[1] : make_uint4(0u, 0u, 0u, 0u), v2 = w[2];
+                    const uint32_t pw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                    const uint4 *const s4 = reinterpret_cast<const uint4 *>(pr + 96);
+                    const uint4 a0 = s4[0], a1 = s4[1], a2 = s4[2], a3 = s4[3];
+                    const uint32_t plo[4] = {a2.x, a2.y, a2.z, a2.w}, phi[4] = {a3.x, a3.y, a3.z, a3.w};
+#pragma unroll
+                    for (int r = 0; r < R; r++) {
+                        if constexpr (PK) {
+                            M[(ph + r) % R][0] = pw[2 * r], M[(ph + r) % R][1] = pw[2 * r + 1];
+                        } else {
+                            M[(ph + r) % R][0] = pw[2 * r] & 0xFFFFu, M[(ph + r) % R][1] = pw[2 * r] >> 16;
+                            M[(ph + r) % R][2] = pw[2 * r + 1] & 0xFFFFu, M[(ph + r) % R][3] = pw[2 * r + 1] >> 16;
+                        }
+                        rlo[(ph + r) % R] = (int)plo[r], rhi[(ph + r) % R] = (int)phi[r];
+                    }
+                    if constexpr (PK) {
+                        I[0] = v2.x, I[1] = v2.y, D[0] = v2.z, D[1] = v2.w;
+                    } else {
+                        I[0] = v2.x & 0xFFFFu, I[1] = v2.x >> 16, I[2] = v2.y & 0xFFFFu, I[3] = v2.y >> 16;
+                        D[0] = v2.z & 0xFFFFu, D[1] = v2.z >> 16, D[2] = v2.w & 0xFFFFu, D[3] = v2.w >> 16;
+                    }
+                    pidx = a0.x, si = a0.y, cells = a0.z, sbuf = a0.w;
+                    n = (int)a1.x, m = (int)a1.y, kb = (int)a1.z, slow = (a1.w & 1u) != 0u, first_eq = (a1.w & 2u) != 0u;
+                    st = 1, wide = false;
+                }
+                m_free &= ~(0xFFull << (8 * oct));
+                continue;
+            }
+            // the next staged pair: header {n, m, status, -} + packed words, in the lowest buffer of st_mask
+            pf_buf   = (uint32_t)__builtin_ctz(st_mask);
+            st_mask &= st_mask - 1u;
+            const uint32_t this_idx = pf_idx;
+            pf_idx += 1u;
+            const uint32_t *const hb = lds + pf_buf * PW;
+            // (readfirstlane: an LDS load counts as divergent, and a branch on it would turn this wave-uniform loop and
+            // every scalar it updates -- the prefetch flags, the buffer masks -- into per-lane values)
+            const uint32_t nq = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[0]), mt = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[1]);
+            const uint32_t status = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[2]);
+            if (st_mask == 0u) pf &= ~PF_STAGED;
+            if (status != ST_PENDING) {  // empty / too long / does not fit / a byte outside ACGT: no alignment here
+                if (lane == 0) {
+                    P.pair_meta[this_idx] = make_uint4(status, 0u, 0u, 0u);
+                    if (status >= ST_REDO_BYTES) push_redo(P, pair_of(this_idx), status);
+                }
+                buf_free |= 1u << pf_buf;
+                continue;  // (the half stays free; the next staged pair will take it)
+            }
+            WFA_EVT(5, 1);
+            if (mine) {
+                pidx = this_idx, sbuf = pf_buf;
+                n = (int)nq, m = (int)mt;
+                const int Ak = m - n;
+                si = 0, cells = 0, slow = false;
+                kb = -16 + PP * imax2(-3, imin2(3, Ak / (2 * PP)));  // k = 0 (the seed) inside, biased towards Ak
+                first_eq = ((hb[4] ^ hb[4 + SW]) & 3u) == 0u;  // q[0] == t[0] (wfa.go:155)
+                clear_rings();
+                st = 1, wide = false;
+            }
+            m_free &= ~(0xFFull << (8 * oct));
+        }
+    };
+
     // ================================================================ between two score steps
     // prefetch pipeline, then -- only when something has to change -- recentre / widen / narrow / park / resume / start
     const auto refill = [&](auto ph_c) __attribute__((always_inline)) -> bool {
@@ -463,78 +544,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 }
             }
             // ------------------------------------------------------------ free halves: parked pairs first, then the staged pair
-            m_free = __ballot(st == 0);
-            while (m_free != 0ull && (park_used != 0u || (pf & PF_STAGED) != 0u)) {
-                const uint32_t oct  = (uint32_t)__builtin_ctzll(m_free) >> 3;  // wave-uniform
-                const bool     mine = ((uint32_t)lane >> 3) == oct;
-                if (park_used != 0u) {
-                    const uint32_t rec = (uint32_t)__builtin_ctz(park_used);
-                    park_used &= park_used - 1u;
-                    WFA_EVT(4, 1);
-                    const uint32_t *const pr = park0 + rec * DUO_PARK_WORDS;
-                    if (mine) {
-                        // (record row r -> M[(ph + r) mod R]: the phase of the resuming wave, not of the one that parked it)
-                        const uint4 *const w = reinterpret_cast<const uint4 *>(pr + 12 * l7);
-                        const uint4 v0 = w[0], v1 = R > 2 ? w[1] : make_uint4(0u, 0u, 0u, 0u), v2 = w[2];
-                        const uint32_t pw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                        const uint4 *const s4 = reinterpret_cast<const uint4 *>(pr + 96);
-                        const uint4 a0 = s4[0], a1 = s4[1], a2 = s4[2], a3 = s4[3];
-                        const uint32_t plo[4] = {a2.x, a2.y, a2.z, a2.w}, phi[4] = {a3.x, a3.y, a3.z, a3.w};
-#pragma unroll
-                        for (int r = 0; r < R; r++) {
-                            if constexpr (PK) {
-                                M[(ph + r) % R][0] = pw[2 * r], M[(ph + r) % R][1] = pw[2 * r + 1];
-                            } else {
-                                M[(ph + r) % R][0] = pw[2 * r] & 0xFFFFu, M[(ph + r) % R][1] = pw[2 * r] >> 16;
-                                M[(ph + r) % R][2] = pw[2 * r + 1] & 0xFFFFu, M[(ph + r) % R][3] = pw[2 * r + 1] >> 16;
-                            }
-                            rlo[(ph + r) % R] = (int)plo[r], rhi[(ph + r) % R] = (int)phi[r];
-                        }
-                        if constexpr (PK) {
-                            I[0] = v2.x, I[1] = v2.y, D[0] = v2.z, D[1] = v2.w;
-                        } else {
-                            I[0] = v2.x & 0xFFFFu, I[1] = v2.x >> 16, I[2] = v2.y & 0xFFFFu, I[3] = v2.y >> 16;
-                            D[0] = v2.z & 0xFFFFu, D[1] = v2.z >> 16, D[2] = v2.w & 0xFFFFu, D[3] = v2.w >> 16;
-                        }
-                        pidx = a0.x, si = a0.y, cells = a0.z, sbuf = a0.w;
-                        n = (int)a1.x, m = (int)a1.y, kb = (int)a1.z, slow = (a1.w & 1u) != 0u, first_eq = (a1.w & 2u) != 0u;
-                        st = 1, wide = false;
-                    }
-                    m_free &= ~(0xFFull << (8 * oct));
-                    continue;
-                }
-                // the next staged pair: header {n, m, status, -} + packed words, in the lowest buffer of st_mask
-                pf_buf   = (uint32_t)__builtin_ctz(st_mask);
-                st_mask &= st_mask - 1u;
-                const uint32_t this_idx = pf_idx;
-                pf_idx += 1u;
-                const uint32_t *const hb = lds + pf_buf * PW;
-                // (readfirstlane: an LDS load counts as divergent, and a branch on it would turn this wave-uniform loop and
-                // every scalar it updates -- the prefetch flags, the buffer masks -- into per-lane values)
-                const uint32_t nq = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[0]), mt = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[1]);
-                const uint32_t status = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[2]);
-                if (st_mask == 0u) pf &= ~PF_STAGED;
-                if (status != ST_PENDING) {  // empty / too long / does not fit / a byte outside ACGT: no alignment here
-                    if (lane == 0) {
-                        P.pair_meta[this_idx] = make_uint4(status, 0u, 0u, 0u);
-                        if (status >= ST_REDO_BYTES) push_redo(P, pair_of(this_idx), status);
-                    }
-                    buf_free |= 1u << pf_buf;
-                    continue;  // (the half stays free; the next staged pair will take it)
-                }
-                WFA_EVT(5, 1);
-                if (mine) {
-                    pidx = this_idx, sbuf = pf_buf;
-                    n = (int)nq, m = (int)mt;
-                    const int Ak = m - n;
-                    si = 0, cells = 0, slow = false;
-                    kb = -16 + PP * imax2(-3, imin2(3, Ak / (2 * PP)));  // k = 0 (the seed) inside, biased towards Ak
-                    first_eq = ((hb[4] ^ hb[4 + SW]) & 3u) == 0u;  // q[0] == t[0] (wfa.go:155)
-                    clear_rings();
-                    st = 1, wide = false;
-                }
-                m_free &= ~(0xFFull << (8 * oct));
-            }
+            // (what the finish of the step before could not place -- a second half freed there, a pair staged since, a half freed by
+            // a narrowing just now; with WFA_DUO_FILL = 0 every fill)
+            fill(ph_c, __ballot(st == 0));
             set_derived();
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -913,7 +925,16 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
 
         // ------------------------------------------------------------ finish / next score
         const bool fin = run && (term || no_room);
-        if (__ballot(fin) != 0ull) {
+        // (WFA_DUO_FILL: the score index moves on before the finish, not after it -- a pair that finishes keeps its own for pair_meta, and
+        // the set_derived() behind the fill forms the row pointer of arena formats 7 and 9 from the index of the next step)
+        if constexpr (WFA_DUO_FILL != 0)
+            if (run && !fin) si += 1u;
+        // (WFA_DUO_FILL: the branch now holds the fill, and is marked as the cold side so that the step's own path keeps its layout and its
+        // registers -- 0.05 ms of a 14 ms step.  Not on the 32-bit rings: at their 124 .. 128 registers the hint costs wfa_duo32_kernel<false, 2, 4>
+        // eight spilled ones)
+        constexpr bool cold    = WFA_DUO_FILL != 0 && PK;
+        const bool     any_fin = __ballot(fin) != 0ull;
+        if (cold ? __builtin_expect(any_fin, 0) : any_fin) {
             const int ctot = (CENSUS && P.census) ? (int)cells : 0;
             int hf   = 0;  // extended offset of the end cell M[s][Ak]: where the backtrace starts
 #pragma unroll
@@ -933,8 +954,19 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 st = 0, wide = false;
                 clear_rings();
             }
+            if constexpr (WFA_DUO_FILL != 0) {
+                // The freed half takes the next pair here and now -- a parked pair, else the staged one -- instead of asking for a
+                // restructuring round that would move nobody's rings (about 0.9 such rounds a pair at 1 kbp, each the price of a score
+                // step), and it runs in the very next step.  The rows go where the next step expects them: its phase.  Nothing to place
+                // (the queue is dry, the next pair not staged yet): the half waits for a round, as before.
+                fill(std::integral_constant<int, (ph + 1) % R>{}, __ballot(st == 0));
+                set_derived();
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
         }
-        if (run && !fin) si += 1u;
+        if constexpr (WFA_DUO_FILL == 0)
+            if (run && !fin) si += 1u;
         WFA_STAMP(5);  // ring + finish
     };
 

@@ -37,6 +37,12 @@ namespace wfa {
 #ifndef WFA_DUO_CLAIM
 #define WFA_DUO_CLAIM 4
 #endif
+// Where a freed half row takes its next pair (wfa_duo.hpp): 1 = in the finish branch of the score step that freed it (the default; a
+// restructuring round only places what that could not); 0 = always in a restructuring round, the form before, kept for A/B builds:
+// scripts/mkvariant.sh <name> -DWFA_DUO_FILL=0
+#ifndef WFA_DUO_FILL
+#define WFA_DUO_FILL 1
+#endif
 // Arena layout of wfa_duo_kernel (16-bit words; a lane's four diagonals of a score are one 8-byte store, and 8 scores of them
 // one 64-byte piece, in every one of the three):
 //   0  CompactView fmt 7 (round 3) -- tiles of 8 scores x 64 diagonals (1 KB), inside a tile [diagonal / 4][score & 7][diagonal & 3]:
