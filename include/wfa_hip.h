@@ -116,7 +116,7 @@ typedef struct {
                                   ran, else the first generic launch) */
     uint32_t n_main_launches;  /* launches of that kernel (one per chunk) */
     uint32_t n_packed_pairs;   /* pairs finished by the sub-wave forward + backtrace kernels */
-    uint32_t main_kernel_kind; /* 0 = wfa_generic_kernel, 1 = wfa_packed_kernel, 2 = wfa_reg_kernel, 3 = wfa_blk_kernel<16>, 4 = wfa_blk_kernel<8>,
+    uint32_t main_kernel_kind; /* (the library's names for these numbers: enum Kind, wfa_amd/csrc/wfa_kinds.hpp) 0 = wfa_generic_kernel, 1 = wfa_packed_kernel, 2 = wfa_reg_kernel, 3 = wfa_blk_kernel<16>, 4 = wfa_blk_kernel<8>,
                                   5 = wfa_blk_kernel<64>, 6 = wfa_blk_kernel<8, 8, false, 4> (short reads), 7 = wfa_team_kernel,
                                   8 = wfa_duo_kernel (8 or 16 lanes per pair), 9 = wfa_blk_kernel<32> (128 diagonals),
                                   10 = wfa_lane_kernel (a lane per pair, short reads), 11 / 12 / 13 = wfa_blk_kernel<16 / 32 / 64, .., LONG>

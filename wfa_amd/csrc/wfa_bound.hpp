@@ -9,22 +9,13 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include "wfa_kinds.hpp"
 
 namespace wfa {
 
-// 32-bit words per arena row of the sub-wave forward kernel `kind` (the host's numbering, wfa_fwd.hpp); 0: the kind's arena is
-// not fixed-pitch rows (kinds 1 and 2 keep a directory), the bound does not size it
-inline uint32_t bound_row_pitch(int kind) {
-    switch (kind) {
-    case 10: return 16;  // wfa_lane_kernel: 32 diagonals x 16 bit
-    case 6: return 32;   // wfa_blk_kernel<8, .., 4>: 32 diagonals
-    case 8: return 32;   // wfa_duo_kernel: 64 diagonals x 16 bit
-    case 3: case 4: case 11: case 14: return 64;
-    case 9: case 12: case 15: return 128;
-    case 5: case 13: return 256;
-    }
-    return 0;
-}
+// 32-bit words per arena row of the sub-wave forward kernel `kind` (wfa_kinds.hpp); 0: the kind's arena is not fixed-pitch rows
+// (K_PACKED and K_REG keep a directory), the bound does not size it
+inline uint32_t bound_row_pitch(int kind) { return kind_traits(kind).pitch; }
 
 // rows a slot gets under the bound: the score indices 0 .. max_score / g every score up to the bound needs, and one more when g
 // does not divide max_score -- (rows - 1) * g then reaches max_score itself, which is what bound_covers asks, and a slot that

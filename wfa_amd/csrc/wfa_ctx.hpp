@@ -10,6 +10,7 @@
 #pragma once
 #include "../../include/wfa_hip.h"
 #include "wfa_common.hpp"
+#include "wfa_kinds.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -64,7 +65,6 @@ struct DevBuf {
 
 // ctrl words (device): [0] queue_head [1] redo_count [2,3] ops_cursor (u64) [4,5] debug_info
 constexpr int CTRL_WORDS = 8;
-constexpr int BLK_BATCH  = 8;  // pairs a group of the blocked kernel stages at a time (short reads)
 // Pinned host block of a context (uint32 words).  Copies between pageable memory and the device are staged by the
 // runtime and cost 0.3-0.5 ms each even for a few bytes; the retry ladder sits on the critical path of a batch.
 constexpr size_t HPIN_CTRL = 0, HPIN_REDO = 16, HPIN_REDO_ENT = 4096, HPIN_WORK = HPIN_REDO + 2 * HPIN_REDO_ENT,

@@ -25,12 +25,10 @@ hipError_t go_duo(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t
 // shape: index of the penalty shape (wfa_fwd.hpp: fwd_shape()); pk: the packed rings (wfa_duo_kernel), else wfa_duo32_kernel
 hipError_t wfa_launch_duo(int shape, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st, bool census, bool pk) {
     switch (shape) {
-    case 0: return go_duo<2, 4>(P, grid, lds_bytes, st, census, pk);
-    case 1: return go_duo<1, 3>(P, grid, lds_bytes, st, census, pk);
-    case 2: return go_duo<1, 2>(P, grid, lds_bytes, st, census, pk);
-    case 3: return go_duo<2, 3>(P, grid, lds_bytes, st, census, pk);
-    case 4: return go_duo<2, 2>(P, grid, lds_bytes, st, census, pk);
-    case 5: return go_duo<3, 3>(P, grid, lds_bytes, st, census, pk);
+#define WFA_DUO_SHAPE(I, tag, DX_, DOE_) \
+    case I: return go_duo<DX_, DOE_>(P, grid, lds_bytes, st, census, pk);
+        WFA_FWD_SHAPES(WFA_DUO_SHAPE)
+#undef WFA_DUO_SHAPE
     }
     return hipErrorInvalidValue;
 }

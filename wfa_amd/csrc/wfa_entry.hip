@@ -928,7 +928,7 @@ static int align_pair_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_
             if (!(ctx->opt_pair_fast == 1 && ctx->one_ctl_clean)) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 1024, st));
             ctx->one_ctl_clean = false;
             if (ctx->opt_pair_fast == 2) {  // forward kernel, then the backtrace kernel (kept for comparison: 305 us per 1 kbp pair)
-                HIP_TRY(wfa_launch_fwd(0, 3, 0u, P, 1u, (size_t)seq_words * 2 * 4 * 4 + 16, st));
+                HIP_TRY(wfa_launch_fwd(0, K_BLK16, 0u, P, 1u, (size_t)seq_words * 2 * 4 * 4 + 16, st));
                 HIP_TRY(wfa_launch_backtrace_one(P, st));
                 launches += 2;
             } else if (ctx->opt_pair_fast == 1) {
@@ -966,7 +966,7 @@ static int align_pair_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_
             break;
         }
         ctx->timing = wfahip_timing{};
-        ctx->timing.n_launches = launches, ctx->timing.main_kernel_kind = ctx->opt_pair_fast == 1 ? 16 : 3;  // (the batch entry never makes fewer than two launches)
+        ctx->timing.n_launches = launches, ctx->timing.main_kernel_kind = ctx->opt_pair_fast == 1 ? K_PAIR : K_BLK16;  // (the batch entry never makes fewer than two launches)
         if (hrec[REC_STATUS] == ST_OK) {
             const uint64_t off = (uint64_t)hrec[REC_OPS_OFF_LO] | ((uint64_t)hrec[REC_OPS_OFF_HI] << 32);
             const uint32_t len = hrec[REC_OPS_LEN];

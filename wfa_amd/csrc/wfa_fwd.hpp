@@ -15,49 +15,55 @@
 // Shapes without an instance (e/g != 1, a ring deeper than four rows) keep the LDS-ring kernel.
 #pragma once
 #include "wfa_common.hpp"
+#include "wfa_kinds.hpp"
 
 namespace wfa {
+
+// the shapes with instances: X(index, tag, DX, DOE).  fwd_shape(), the per-shape entry points below and every switch over a
+// shape index (wfa_host.hip, wfa_duo.hip, wfa_score.hip, wfa_wide_pk.hip) are generated from this list, in this order
+#define WFA_FWD_SHAPES(X) X(0, s24, 2, 4) X(1, s13, 1, 3) X(2, s12, 1, 2) X(3, s23, 2, 3) X(4, s22, 2, 2) X(5, s33, 3, 3)
 
 constexpr int FWD_N_SHAPES = 6;
 // index of the shape's instances, -1: none
 inline int fwd_shape(uint32_t dx, uint32_t doe, uint32_t de) {
     if (de != 1u) return -1;
-    if (dx == 2u && doe == 4u) return 0;
-    if (dx == 1u && doe == 3u) return 1;
-    if (dx == 1u && doe == 2u) return 2;
-    if (dx == 2u && doe == 3u) return 3;
-    if (dx == 2u && doe == 2u) return 4;
-    if (dx == 3u && doe == 3u) return 5;
+#define WFA_FWD_SHAPE_IS(I, tag, DX_, DOE_) \
+    if (dx == DX_##u && doe == DOE_##u) return I;
+    WFA_FWD_SHAPES(WFA_FWD_SHAPE_IS)
+#undef WFA_FWD_SHAPE_IS
     return -1;
 }
 
 // flags of wfa_launch_fwd
 enum : uint32_t {
     FWD_CENSUS   = 1u,  // count the stored wavefront words (REC_CELLS)
-    FWD_STREAM   = 2u,  // kind 3 only, shape 2 : 4 only: the launch also walks the backtrace of finished pairs
-    FWD_BATCH    = 4u,  // kinds 3 / 6: a group stages BLK_BATCH queue entries per refill (short reads)
-    FWD_ADAPTIVE = 8u   // kind 10: the instance that tracks wf-adaptive's distances
+    FWD_STREAM   = 2u,  // K_BLK16 only, shape 2 : 4 only: the launch also walks the backtrace of finished pairs
+    FWD_BATCH    = 4u,  // K_BLK16 / K_NARROW: a group stages BLK_BATCH queue entries per refill (short reads)
+    FWD_ADAPTIVE = 8u   // K_LANE: the instance that tracks wf-adaptive's distances
 };
 
-// Forward kernel of `kind` (the host's numbering: 3 = wfa_blk_kernel<16>, 4 = <8>, 5 = <64> (256 diagonals), 6 = <8, .., 4> (32
-// diagonals), 8 = wfa_duo_kernel, 9 = <32> (128 diagonals), 10 = wfa_lane_kernel, 11 / 12 / 13 = 3 / 9 / 5 with sliding sequence
-// windows, 14 / 15 = a wave per pair with one / two diagonals per lane) for penalty shape `shape`.  hipErrorInvalidValue: no
-// such instance.
+// Forward kernel of `kind` (wfa_kinds.hpp: K_BLK16 .. K_LONE128 without K_TEAM and K_DUO) for penalty shape `shape`.
+// hipErrorInvalidValue: no such instance.
 hipError_t wfa_launch_fwd(int shape, int kind, uint32_t flags, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 
 // wfahip_align_pair's lone-pair instance (a lane per diagonal, the wave walks its own backtrace): lds_arena = the rows in LDS
 hipError_t wfa_launch_pair(int shape, bool lds_arena, const KParams &P, size_t lds_bytes, hipStream_t st);
 
+// one wfa_wide_kernel instance with `waves` waves per pair; rings above 64 KB need the opt-in (per device: the attribute belongs
+// to the kernel as loaded there)
+template <class K>
+hipError_t wfa_launch_wide_instance(K kern, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    if (lds_bytes > 64 * 1024)
+        if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), lds_bytes, st, P);
+    return hipGetLastError();
+}
+
 // per-shape entry points (wfa_fwd_s*.hip)
-#define WFA_FWD_DECL(tag)                                                                                                   \
+#define WFA_FWD_DECL(I, tag, DX_, DOE_)                                                                                     \
     hipError_t wfa_launch_fwd_##tag(int kind, uint32_t flags, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st); \
     hipError_t wfa_launch_pair_##tag(bool lds_arena, const KParams &P, size_t lds_bytes, hipStream_t st);
-WFA_FWD_DECL(s24)
-WFA_FWD_DECL(s13)
-WFA_FWD_DECL(s12)
-WFA_FWD_DECL(s23)
-WFA_FWD_DECL(s22)
-WFA_FWD_DECL(s33)
+WFA_FWD_SHAPES(WFA_FWD_DECL)
 #undef WFA_FWD_DECL
 
 }  // namespace wfa

@@ -15,7 +15,6 @@ namespace wfa {
 namespace {
 constexpr int  SDX = WFA_SHAPE_DX, SDOE = WFA_SHAPE_DOE;
 constexpr bool DEFAULT_SHAPE = SDX == 2 && SDOE == 4;
-constexpr int  FWD_BLK_BATCH = 8;  // = BLK_BATCH of wfa_host.hip
 
 template <int G, int BATCH, bool STREAM, int PPT, bool CENSUS, bool LONG, bool LDSA = false>
 hipError_t go(const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
@@ -37,34 +36,34 @@ hipError_t WFA_CAT(wfa_launch_fwd_, WFA_SHAPE_TAG)(int kind, uint32_t flags, con
     const bool census = (flags & FWD_CENSUS) != 0u, stream = (flags & FWD_STREAM) != 0u, batch = (flags & FWD_BATCH) != 0u;
     const bool adaptive = (flags & FWD_ADAPTIVE) != 0u;
     switch (kind) {
-    case 3:  // four pairs per wave, 64 diagonals
-        if (batch) return go<16, FWD_BLK_BATCH, false, 0, true, false>(P, grid, lds_bytes, st);
+    case K_BLK16:  // four pairs per wave, 64 diagonals
+        if (batch) return go<16, BLK_BATCH, false, 0, true, false>(P, grid, lds_bytes, st);
         if constexpr (DEFAULT_SHAPE) {
             if (stream) return census ? go<16, 1, true, 0, true, false>(P, grid, lds_bytes, st) : go<16, 1, true, 0, false, false>(P, grid, lds_bytes, st);
         } else if (stream) {
             return hipErrorInvalidValue;
         }
         return census ? go<16, 1, false, 0, true, false>(P, grid, lds_bytes, st) : go<16, 1, false, 0, false, false>(P, grid, lds_bytes, st);
-    case 4:  // eight pairs per wave, eight diagonals per lane (option blk = 8)
+    case K_BLK8:  // eight pairs per wave, eight diagonals per lane (option blk = 8)
         if constexpr (DEFAULT_SHAPE) return go<8, 1, false, 0, true, false>(P, grid, lds_bytes, st);
         return hipErrorInvalidValue;
-    case 5:  // a wave per pair, 256 diagonals
+    case K_BLK64:  // a wave per pair, 256 diagonals
         return go<64, 1, false, 0, true, false>(P, grid, lds_bytes, st);
-    case 6:  // eight pairs per wave, 32 diagonals (short reads)
-        if (batch) return census ? go<8, FWD_BLK_BATCH, false, 4, true, false>(P, grid, lds_bytes, st) : go<8, FWD_BLK_BATCH, false, 4, false, false>(P, grid, lds_bytes, st);
+    case K_NARROW:  // eight pairs per wave, 32 diagonals (short reads)
+        if (batch) return census ? go<8, BLK_BATCH, false, 4, true, false>(P, grid, lds_bytes, st) : go<8, BLK_BATCH, false, 4, false, false>(P, grid, lds_bytes, st);
         if constexpr (DEFAULT_SHAPE) return go<8, 1, false, 4, true, false>(P, grid, lds_bytes, st);
         return hipErrorInvalidValue;
-    case 9:  // two pairs per wave, 128 diagonals
+    case K_BLK32:  // two pairs per wave, 128 diagonals
         return go<32, 1, false, 0, true, false>(P, grid, lds_bytes, st);
-    case 10:  // a lane per pair (short reads)
+    case K_LANE:  // a lane per pair (short reads)
         if (census) return adaptive ? go_lane<true, true>(P, grid, lds_bytes, st) : go_lane<true, false>(P, grid, lds_bytes, st);
         return adaptive ? go_lane<false, true>(P, grid, lds_bytes, st) : go_lane<false, false>(P, grid, lds_bytes, st);
     // long reads: the same groups with sliding sequence windows
-    case 11: return census ? go<16, 1, false, 0, true, true>(P, grid, lds_bytes, st) : go<16, 1, false, 0, false, true>(P, grid, lds_bytes, st);
-    case 12: return go<32, 1, false, 0, true, true>(P, grid, lds_bytes, st);
-    case 13: return census ? go<64, 1, false, 0, true, true>(P, grid, lds_bytes, st) : go<64, 1, false, 0, false, true>(P, grid, lds_bytes, st);
-    case 14: return census ? go<64, 1, false, 1, true, true>(P, grid, lds_bytes, st) : go<64, 1, false, 1, false, true>(P, grid, lds_bytes, st);
-    case 15: return census ? go<64, 1, false, 2, true, true>(P, grid, lds_bytes, st) : go<64, 1, false, 2, false, true>(P, grid, lds_bytes, st);
+    case K_LONG16: return census ? go<16, 1, false, 0, true, true>(P, grid, lds_bytes, st) : go<16, 1, false, 0, false, true>(P, grid, lds_bytes, st);
+    case K_LONG32: return go<32, 1, false, 0, true, true>(P, grid, lds_bytes, st);
+    case K_LONG64: return census ? go<64, 1, false, 0, true, true>(P, grid, lds_bytes, st) : go<64, 1, false, 0, false, true>(P, grid, lds_bytes, st);
+    case K_LONE64: return census ? go<64, 1, false, 1, true, true>(P, grid, lds_bytes, st) : go<64, 1, false, 1, false, true>(P, grid, lds_bytes, st);
+    case K_LONE128: return census ? go<64, 1, false, 2, true, true>(P, grid, lds_bytes, st) : go<64, 1, false, 2, false, true>(P, grid, lds_bytes, st);
     }
     return hipErrorInvalidValue;
 }

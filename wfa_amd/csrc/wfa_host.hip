@@ -30,23 +30,19 @@ static_assert(TEAM_SOLO_MAX == 4096, "wfa_ctx.hpp: default of opt_team_solo_max"
 namespace wfa {
 hipError_t wfa_launch_fwd(int shape, int kind, uint32_t flags, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     switch (shape) {
-    case 0: return wfa_launch_fwd_s24(kind, flags, P, grid, lds_bytes, st);
-    case 1: return wfa_launch_fwd_s13(kind, flags, P, grid, lds_bytes, st);
-    case 2: return wfa_launch_fwd_s12(kind, flags, P, grid, lds_bytes, st);
-    case 3: return wfa_launch_fwd_s23(kind, flags, P, grid, lds_bytes, st);
-    case 4: return wfa_launch_fwd_s22(kind, flags, P, grid, lds_bytes, st);
-    case 5: return wfa_launch_fwd_s33(kind, flags, P, grid, lds_bytes, st);
+#define WFA_FWD_CASE(I, tag, DX_, DOE_) \
+    case I: return wfa_launch_fwd_##tag(kind, flags, P, grid, lds_bytes, st);
+        WFA_FWD_SHAPES(WFA_FWD_CASE)
+#undef WFA_FWD_CASE
     }
     return hipErrorInvalidValue;
 }
 hipError_t wfa_launch_pair(int shape, bool lds_arena, const KParams &P, size_t lds_bytes, hipStream_t st) {
     switch (shape) {
-    case 0: return wfa_launch_pair_s24(lds_arena, P, lds_bytes, st);
-    case 1: return wfa_launch_pair_s13(lds_arena, P, lds_bytes, st);
-    case 2: return wfa_launch_pair_s12(lds_arena, P, lds_bytes, st);
-    case 3: return wfa_launch_pair_s23(lds_arena, P, lds_bytes, st);
-    case 4: return wfa_launch_pair_s22(lds_arena, P, lds_bytes, st);
-    case 5: return wfa_launch_pair_s33(lds_arena, P, lds_bytes, st);
+#define WFA_PAIR_CASE(I, tag, DX_, DOE_) \
+    case I: return wfa_launch_pair_##tag(lds_arena, P, lds_bytes, st);
+        WFA_FWD_SHAPES(WFA_PAIR_CASE)
+#undef WFA_PAIR_CASE
     }
     return hipErrorInvalidValue;
 }
@@ -55,25 +51,13 @@ hipError_t wfa_launch_pair(int shape, bool lds_arena, const KParams &P, size_t l
 hipError_t wfa_launch_wide(int stage, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     if (stage == STAGE_PACKED) return wfa_launch_wide_packed(shape, phase, waves, P, grid, lds_bytes, st);
     if (stage != STAGE_BYTES) return hipErrorInvalidValue;
-    const auto go = [&](auto kern, int nw) -> hipError_t {
-        if (lds_bytes > 64 * 1024) {  // (per device: the attribute belongs to the kernel as loaded there)
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds_bytes, st, P);
-        return hipGetLastError();
-    };
-#define WFA_WIDE_SHAPE(I, DX_, DOE_)                                                                            \
+    const auto go = [&](auto kern, int nw) { return wfa_launch_wide_instance(kern, nw, P, grid, lds_bytes, st); };
+#define WFA_WIDE_SHAPE(I, tag, DX_, DOE_)                                                                       \
     case 3 * I: return go(wfa_wide_kernel<DX_, DOE_, 0, 1>, 1);                                                 \
     case 3 * I + 1: return go(wfa_wide_kernel<DX_, DOE_, 0, 4>, 4);                                             \
     case 3 * I + 2: return go(wfa_wide_kernel<DX_, DOE_, 1, 1>, 1);
     switch (shape * 3 + (phase ? 2 : (waves > 1 ? 1 : 0))) {
-        WFA_WIDE_SHAPE(0, 2, 4)
-        WFA_WIDE_SHAPE(1, 1, 3)
-        WFA_WIDE_SHAPE(2, 1, 2)
-        WFA_WIDE_SHAPE(3, 2, 3)
-        WFA_WIDE_SHAPE(4, 2, 2)
-        WFA_WIDE_SHAPE(5, 3, 3)
+        WFA_FWD_SHAPES(WFA_WIDE_SHAPE)
     }
 #undef WFA_WIDE_SHAPE
     return hipErrorInvalidValue;
@@ -130,9 +114,9 @@ struct LaunchCfg {
 hipError_t launch_generic(const KParams &P, const LaunchCfg &c, hipStream_t st) { return wfa_launch_generic(P, c.waves, c.mode, c.slots, c.lds_bytes, st); }
 
 struct Job {
-    int                   mode;
-    int                   level;  // arena size: make_cfg's ladder (x8, x8, x2 .., then one slot fewer per level)
-    bool                  all;    // identity work list over all pairs
+    int                   mode  = 0;
+    int                   level = 0;      // arena size: make_cfg's ladder (x8, x8, x2 .., then one slot fewer per level)
+    bool                  all   = false;  // identity work list over all pairs
     std::vector<uint32_t> pairs;
     uint32_t              max_len = 0;  // length bound of these pairs (0 = the batch's)
     bool                  hint    = false;  // `level` came from an earlier call of the class (learn), not from a failed level below it
@@ -191,6 +175,32 @@ int make_cfg(wfahip_ctx *ctx, uint32_t max_len, int mode, int level, uint64_t n_
     slots   = std::min<uint64_t>(slots, std::max<uint64_t>(n_work, 1));
     c.slots = (uint32_t)slots;
     return 0;
+}
+
+// What of a sub-wave forward kind depends on how the kernels were built (the rest is KIND_TRAITS, wfa_kinds.hpp).
+// KParams::compact_fmt of the arena the kind `base` writes (KindTraits::base)
+uint32_t compact_fmt_of(Kind base) {
+    switch (base) {
+    case K_BLK16: case K_BLK8: return WFA_BLK_TILED ? 3u : 1u;
+    case K_BLK64: return 4u;
+    case K_NARROW: return 5u;
+    case K_BLK32: return 6u;
+    case K_DUO: return DUO_ARENA_FMT;
+    case K_LANE: return 8u;
+    default: return 0u;  // K_PACKED, K_REG: the directory
+    }
+}
+// waves a CU is given at most, before what their LDS allows (at most 32)
+uint32_t waves_cap(Kind kind, bool census, bool overlap) {
+    switch (kind) {
+    case K_PACKED: return overlap ? 24 : 32;
+    case K_BLK8: return 12;
+    case K_DUO: return 4 * WFA_DUO_WAVES;
+    case K_LANE: return 8;
+    case K_LONG16: return census ? 16 : 4 * WFA_BLK_WAVES;
+    case K_LONG32: case K_LONG64: case K_LONE64: case K_LONE128: return 16;
+    default: return 20;
+    }
 }
 
 }  // namespace
@@ -630,11 +640,27 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
     HIP_TRY(hipSetDevice(ctx->device));
     if (!st) st = ctx->stream;
 
-    if (max_len == 0) {  // compute the bound from the device-resident length arrays
-        std::vector<uint32_t> ql(n_pairs), tl(n_pairs);
+    // the batch's length arrays on the host: the call's read-only inputs, fetched by the first of the places that read them
+    std::vector<uint32_t> ql, tl;
+    const auto host_lens = [&]() -> int {
+        if (!ql.empty()) return WFAHIP_OK;
+        ql.resize(n_pairs), tl.resize(n_pairs);
         HIP_TRY(hipMemcpyAsync(ql.data(), d_q_len, n_pairs * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(tl.data(), d_t_len, n_pairs * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        return WFAHIP_OK;
+    };
+    // n events in the context's pool
+    const auto grow_evpool = [&](uint64_t n) -> int {
+        while (ctx->evpool.size() < n) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            ctx->evpool.push_back(e);
+        }
+        return WFAHIP_OK;
+    };
+    if (max_len == 0) {  // compute the bound from the device-resident length arrays
+        if ((rc = host_lens())) return rc;
         for (uint64_t i = 0; i < n_pairs; i++) {
             if (ql[i] <= WFAHIP_MAX_SEQ_LEN) max_len = std::max(max_len, ql[i]);
             if (tl[i] <= WFAHIP_MAX_SEQ_LEN) max_len = std::max(max_len, tl[i]);
@@ -721,9 +747,13 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
     }
     HIP_TRY(hipEventRecord(ctx->ev0, st));
 
+    // workload class of what a context learns from call to call: length bucket, penalties, wf-adaptive
+    uint32_t len_bucket = 0;
+    while ((2u << len_bucket) <= max_len) len_bucket++;
+    const uint64_t class_key = 1ull | ((uint64_t)len_bucket << 1) | ((uint64_t)P.adaptive << 9) | ((uint64_t)(P.x & 0xFFF) << 12) | ((uint64_t)(P.oe & 0xFFF) << 24) |
+                               ((uint64_t)(P.e & 0xFFF) << 36) | ((uint64_t)(P.max_dist_diff & 0xFFFF) << 48);
     std::deque<Job> jobs;
     std::vector<uint32_t> no_memory;
-    std::vector<uint32_t> h_len;   // max(q_len, t_len) per pair, only when the batch mixes short and long pairs
     uint32_t              sub_len_used = 0;
     const int             max_level = 12;
     bool                  first     = true, after_scout = false;
@@ -842,11 +872,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             P.min_xe = std::min(P.x, P.e), P.compact_fmt = WIDE_FMT;
             P.prepack = nullptr, P.prepack_words = 0, P.done_q = nullptr, P.done_ctl = nullptr, P.n_stream_wgs = 0;
             P.mx_words = ctx->pk_words;
-            while (ctx->evpool.size() < ev_need) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                ctx->evpool.push_back(e);
-            }
+            if ((rc = grow_evpool(ev_need))) return rc;
             ctrl_zeroed = false;
             uint64_t ev_i = 0, last_cn = 0;
             for (const WideRun &r : runs) {
@@ -895,7 +921,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                     }
                 for (const auto &kv : tally) std::fprintf(stderr, "[wfahip] wide: status %u reason %u: %u pairs of %llu\n", (uint32_t)(kv.first >> 32), (uint32_t)kv.first, kv.second, (unsigned long long)cn);
             }
-            ctx->timing.main_kernel_kind = 18;
+            ctx->timing.main_kernel_kind = K_WIDE;
             ctx->timing.n_packed_pairs   = (uint32_t)(n_pairs - redo.size() - n_ladder);
             ctx->timing.n_retried_pairs += (uint32_t)(redo.size() + n_ladder);
             // what the kernel hands back for its bytes or its arena is within the kernel's lengths: jobs sized by the longest classed read;
@@ -904,9 +930,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             uint32_t wide_longest = 0;
             for (const WideRun &r : runs) wide_longest = std::max(wide_longest, r.longest);
             Job jb, ja, jl;
-            jb.mode = 1, jb.level = 0, jb.all = false;
-            ja.mode = 0, ja.level = 0, ja.all = false;
-            jl.mode = 0, jl.level = 0, jl.all = false;
+            jb.mode = 1;
             if (max_len > WIDE_MAX_LEN) jb.max_len = ja.max_len = wide_longest;
             for (uint64_t e : redo) {
                 const uint32_t stw = (uint32_t)(e >> 32);
@@ -919,14 +943,11 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             // starts, as pass 1 splits its leftovers
             if (n_ladder) {
                 Job js, jt;
-                js.mode = 0, js.level = 0, js.all = false, js.max_len = ladder_longest;
-                jt.mode = 0, jt.level = 0, jt.all = false, jt.max_len = ladder_longest;
+                js.max_len = jt.max_len = ladder_longest;
                 std::vector<uint32_t> ids(n_ladder);
                 HIP_TRY(hipMemcpy(ids.data(), static_cast<const uint32_t *>(ctx->wide_ids.p) + (n_pairs - n_ladder), n_ladder * 4, hipMemcpyDeviceToHost));
                 if (ctx->opt_team_min_len > 0 && (int64_t)ladder_longest >= ctx->opt_team_min_len) {
-                    std::vector<uint32_t> ql(n_pairs), tl(n_pairs);
-                    HIP_TRY(hipMemcpy(ql.data(), d_q_len, n_pairs * 4, hipMemcpyDeviceToHost));
-                    HIP_TRY(hipMemcpy(tl.data(), d_t_len, n_pairs * 4, hipMemcpyDeviceToHost));
+                    if ((rc = host_lens())) return rc;
                     js.max_len = 0;
                     for (uint32_t pid : ids) {
                         const uint32_t l = std::max(ql[pid], tl[pid]);
@@ -943,7 +964,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         }
     }
     // ---- pass 1: sub-wave forward kernels + lane-per-pair backtrace kernel, chunk by chunk.
-    //      kind 2 = register-window kernel (4 pairs per wave), kind 1 = LDS-ring packed kernel (2 pairs per wave).
+    //      (The kinds: wfa_kinds.hpp.)
     if (!packed_done && ctx->opt_packed && !debug_single && ctx->force_mode < 0 && P.global_alignment && P.e != 0u) {
         const uint32_t dx = P.x / P.g, doe = P.oe / P.g, de = P.e / P.g;
         const uint32_t dm = std::max(dx, doe) + 1, di = de + 1;
@@ -952,35 +973,25 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         // the kernels hand the longer ones on themselves (ST_REDO_LDS) and the generic / team kernels take them.
         constexpr uint32_t SUB_LEN_LIMIT = 10200;
         uint32_t           sub_len       = max_len;
-        // long reads: the blocked kernels with sliding sequence windows (kinds 11 / 12 / 13 = 64 / 128 / 256 diagonals)
+        // long reads: the blocked kernels with sliding sequence windows (K_LONG16 / K_LONG32 / K_LONG64 = 64 / 128 / 256 diagonals)
         // the penalty shape the register-ring kernels are instantiated for (wfa_fwd.hpp); -1: none, the LDS-ring kernel takes the batch
         const int  shape    = fwd_shape(dx, doe, de);
         const bool can_long = ctx->opt_long != 0 && ctx->opt_blk == 16 && shape >= 0 && (int64_t)max_len > ctx->opt_long_min_len;
         // (a batch of mostly short pairs with a few long ones keeps the short pairs' pipeline -- slots, arenas and windows of the
         // long instances are sized by the longest pair -- and the long ones get a pass of their own behind it: long_first below)
         if (max_len > SUB_LEN_LIMIT && n_pairs >= 256) {
-            std::vector<uint32_t> ql(n_pairs), tl(n_pairs);
-            HIP_TRY(hipMemcpyAsync(ql.data(), d_q_len, n_pairs * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(tl.data(), d_t_len, n_pairs * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
+            if ((rc = host_lens())) return rc;
             uint64_t n_fit = 0;
             uint32_t best  = 0;
-            h_len.resize(n_pairs);
             for (uint64_t i = 0; i < n_pairs; i++) {
                 const uint32_t l = std::max(ql[i], tl[i]);
-                h_len[i]         = l;
                 if (l <= SUB_LEN_LIMIT) n_fit++, best = std::max(best, l);
             }
-            if (n_fit * 10 >= n_pairs * 9 && best > 0)
-                sub_len = best, sub_len_used = best;  // at least 90 % of the pairs fit
-            else
-                h_len.clear();
+            if (n_fit * 10 >= n_pairs * 9 && best > 0) sub_len = best, sub_len_used = best;  // at least 90 % of the pairs fit
         }
         const bool     long_first = can_long && sub_len_used == 0;  // the whole batch starts on the sliding-window instances
         const uint32_t seq_words = (sub_len + 15) / 16 + 1;
         const uint64_t sub_words = packed_sub_lds_words(seq_words, dm, di);
-        // what forward_pass sizes slots and arenas by: the class of pairs it is given (the batch's; the long pairs' in their own pass)
-        uint32_t fp_seq_words = seq_words;
         const size_t   lds_b     = (size_t)sub_words * 2 * 4;       // packed kernel: two halves
         const size_t   lds_c     = (size_t)seq_words * 2 * 4 * 4;   // register kernel: four rows, sequences only
         const size_t   lds_d     = (size_t)seq_words * 2 * 4 * (ctx->opt_blk == 8 ? 8 : 4) + 16;  // blocked kernel
@@ -993,8 +1004,13 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             if (ctx->opt_packed_arena_bytes > 0) wd = std::max<uint64_t>(1024, ctx->opt_packed_arena_bytes / 4);
             return (wd + 7) & ~7ull;
         };
-        uint64_t fp_words_dir = words_dir_of(sub_len);
-        P.arena_words   = fp_words_dir;
+        // what a pass sizes slots and arenas by: the class of pairs it is given (the batch's; the long pairs' in their own pass)
+        struct PassClass {
+            uint32_t seq_words;
+            uint64_t words_dir;
+        };
+        const PassClass batch_class{seq_words, words_dir_of(sub_len)};
+        P.arena_words   = batch_class.words_dir;
         P.dx = dx, P.doe = doe, P.de = de, P.dm = dm, P.di = di;
         P.lds_seq_words = seq_words;
         P.sub_lds_words = (uint32_t)sub_words;
@@ -1008,81 +1024,60 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         // one pass over `count` pairs (identity range when list == nullptr); returns the {pair,status} redo entries
         // detach_bt: (first pass, one chunk) the backtrace kernel goes to stream2 and is only waited for at the very
         // end of the call, so the retry passes -- which use the second arena -- run beside it.
-        // (workload class of the learned row count: length bucket, penalties, wf-adaptive)
-        uint64_t rkey = 0;
-        {
-            uint32_t lb = 0;
-            while ((2u << lb) <= max_len) lb++;
-            rkey = 1ull | ((uint64_t)lb << 1) | ((uint64_t)P.adaptive << 9) | ((uint64_t)(P.x & 0xFFF) << 12) | ((uint64_t)(P.oe & 0xFFF) << 24) |
-                   ((uint64_t)(P.e & 0xFFF) << 36) | ((uint64_t)(P.max_dist_diff & 0xFFFF) << 48);
-        }
-        uint64_t arena_mult = (ctx->rows_key == rkey && ctx->opt_packed_arena_bytes <= 0) ? ctx->rows_scale : 1;  // rows per pair, in units of the default
-        auto forward_pass = [&](int kind, const std::vector<uint32_t> *list, uint64_t first_pair, uint64_t count,
-                                std::vector<uint64_t> &redo_out, bool detach_bt) -> int {
+        const uint64_t rkey = class_key;  // (workload class of the learned row count)
+        const uint64_t arena_mult = (ctx->rows_key == rkey && ctx->opt_packed_arena_bytes <= 0) ? ctx->rows_scale : 1;  // rows per pair, in units of the default
+        // (cls: the class of pairs the pass is sized by -- nullptr: the batch's; rows_mult: the row multiplier -- 0: arena_mult)
+        auto forward_pass = [&](Kind kind, const std::vector<uint32_t> *list, uint64_t first_pair, uint64_t count, std::vector<uint64_t> &redo_out,
+                                bool detach_bt, const PassClass *cls = nullptr, uint64_t rows_mult = 0) -> int {
+            const uint32_t seq_words = (cls ? cls : &batch_class)->seq_words;  // (shadows the batch's)
+            const uint64_t words_dir = (cls ? cls : &batch_class)->words_dir;
+            if (rows_mult == 0) rows_mult = arena_mult;
+            const KindTraits &T = kind_traits(kind);
             // (retry passes take the second pair of buffers: the first pass's backtrace may still be reading the first -- and
             // wfahip_debug_compact_arena shows what the first pass left.  Unless the first pair is large and free: two large
             // arenas side by side are for overlap, not for a snapshot)
-            const uint32_t seq_words = fp_seq_words;  // (shadow the batch's: this pass's class of pairs)
-            const uint64_t words_dir = fp_words_dir;
             const bool second = ctx->bt_pending || (list && ctx->arena.bytes <= ctx->total_mem / 10);
             DevBuf &arena_buf = second ? ctx->arena2 : ctx->arena;
             DevBuf &meta_buf  = second ? ctx->meta2 : ctx->meta;
             // short reads: the blocked kernel stages BLK_BATCH pairs per group at a time
-            // (kind 6: eight pairs per wave, 32-diagonal window; only with the batched refill)
-            const bool     blk_batch    = (kind == 3 || kind == 6) && seq_words <= 16 && ctx->opt_blk_batch != 0;
-            if (kind == 6 && !blk_batch && ctx->opt_narrow_long == 0) return WFAHIP_ERR_INTERNAL;
+            // (K_NARROW: only with the batched refill)
+            const bool     blk_batch    = (kind == K_BLK16 || kind == K_NARROW) && seq_words <= 16 && ctx->opt_blk_batch != 0;
+            if (kind == K_NARROW && !blk_batch && ctx->opt_narrow_long == 0) return WFAHIP_ERR_INTERNAL;
             if (ctx->opt_fail_pass == kind) return WFAHIP_ERR_OOM;  // (fault injection, tests only)
-            // kind 8 (wfa_duo_kernel): sequences come pre-packed, slot = 4 header words + 2 x (even) words per sequence
-            const uint32_t duo_sw       = (seq_words + 1u) & ~1u, duo_pw = 4u + 2u * duo_sw;
-            if (kind == 8 && (duo_pw > 256u || blk_batch)) return WFAHIP_ERR_INTERNAL;
-            if (kind == 10 && (seq_words > (uint32_t)LN_SEQ_WORDS || list)) return WFAHIP_ERR_INTERNAL;
-            const uint32_t lane_sw      = (seq_words + 1u) & ~1u;  // kind 10 (wfa_lane_kernel): words per sequence in its slots and in LDS
-            // kinds 11 / 12 / 13: kinds 3 / 9 / 5 with sliding sequence windows (long reads): pre-packed slots of long_sw words per
-            // sequence in HBM, long_cw words of each in LDS
-            // kinds 14 / 15: the whole wave on ONE pair with one / two diagonals per lane (64 / 128 diagonals): batches too small to fill the GPU
-            const bool     is_long      = kind >= 11 && kind <= 15;
+            // wfa_duo_kernel: sequences come pre-packed, slot = 4 header words + 2 x (even) words per sequence
+            const uint32_t even_sw      = (seq_words + 1u) & ~1u, duo_pw = 4u + 2u * even_sw;  // (wfa_lane_kernel too: even words per sequence in its slots and in LDS)
+            if (kind == K_DUO && (duo_pw > 256u || blk_batch)) return WFAHIP_ERR_INTERNAL;
+            if (kind == K_LANE && (seq_words > (uint32_t)LN_SEQ_WORDS || list)) return WFAHIP_ERR_INTERNAL;
+            // the sliding-window kinds (long reads): pre-packed slots of long_sw words per sequence in HBM, long_cw words of each in LDS
+            const bool     is_long      = T.windows != 0;
             const uint32_t long_sw      = (seq_words + 3u) & ~3u, long_cw = (uint32_t)ctx->opt_long_window_words;
             if (is_long && !can_long) return WFAHIP_ERR_INTERNAL;
             if (is_long && (uint64_t)seq_words * 16u < (uint64_t)max_len && !list) return WFAHIP_ERR_INTERNAL;  // (slots sized for the short class)
-            const int      bkind        = (kind == 11 || kind == 14) ? 3 : (kind == 12 || kind == 15) ? 9 : kind == 13 ? 5 : kind;  // (arena format)
-            const size_t   lds_bytes    = is_long ? (size_t)(kind == 11 ? 4 : kind == 12 ? 2 : 1) * 2 * long_cw * 4
-                                          : kind == 10 ? (size_t)64 * lane_stride_words(lane_sw) * 4
-                                          : kind == 8 ? (size_t)duo_lds_words(duo_pw) * 4
-                                          : kind == 9 ? (size_t)seq_words * 2 * 4 * 2 + 16
-                                          : blk_batch ? (size_t)(kind == 6 ? 8 : 4) * BLK_BATCH * (2 * seq_words + 8) * 4 + 16
-                                          : kind == 6 ? (size_t)seq_words * 2 * 4 * 8 + 16
-                                          : kind == 5 ? (size_t)seq_words * 2 * 4 + 16
-                                                      : (kind >= 3 ? lds_d : (kind == 2 ? lds_c : lds_b));
-            const uint32_t pairs_wave   = kind >= 13 ? 1 : kind == 10 ? 64 : bkind == 5 ? 1 : bkind == 9 ? 2 : (kind == 4 || kind == 6 || kind == 8 ? 8 : (kind >= 2 ? 4 : 2));
+            size_t lds_bytes = (size_t)seq_words * 2 * 4 * T.pairs_wave + 16;  // the sequences of a wave's pairs (K_BLK32, K_BLK64, K_NARROW)
+            if (is_long) lds_bytes = (size_t)T.windows * 2 * long_cw * 4;
+            else if (blk_batch) lds_bytes = (size_t)T.pairs_wave * BLK_BATCH * (2 * seq_words + 8) * 4 + 16;
+            else if (kind == K_PACKED) lds_bytes = lds_b;
+            else if (kind == K_REG) lds_bytes = lds_c;
+            else if (kind == K_BLK16 || kind == K_BLK8) lds_bytes = lds_d;
+            else if (kind == K_DUO) lds_bytes = (size_t)duo_lds_words(duo_pw) * 4;
+            else if (kind == K_LANE) lds_bytes = (size_t)64 * lane_stride_words(even_sw) * 4;
             // blocked kernels: fixed-pitch arena, no directory.  64-diagonal window: 16 words per base = 250 scores at
-            // 1 kbp; 256-diagonal window (kind 5, the retry rung): 128 words per base = 500 scores at 1 kbp
-            const uint64_t words_min    = bkind == 5 ? 8192 : bkind == 9 ? 4096 : (kind == 8 || kind == 10) ? 1024 : 2048;
-            const uint64_t words_free   = bkind == 5   ? std::max<uint64_t>((words_dir * 16 * arena_mult + 511) & ~511ull, words_min)
-                                          : bkind == 9 ? std::max<uint64_t>((words_dir * 4 * arena_mult + 511) & ~511ull, words_min)
-                                          : kind == 8 ? std::max<uint64_t>((words_dir * arena_mult + 511) & ~511ull, words_min)  // 16-bit words
-                                          : kind == 10 ? std::max<uint64_t>((words_dir * arena_mult + 511) & ~511ull, words_min)  // rows of 32 x 16 bit
-                                          : kind >= 3 ? std::max<uint64_t>((words_dir * 2 * arena_mult + 511) & ~511ull, words_min)
-                                                      : words_dir;
+            // 1 kbp; 256-diagonal window (K_BLK64, the retry rung): 128 words per base = 500 scores at 1 kbp
+            const uint64_t words_free   = T.pitch ? std::max<uint64_t>((words_dir * T.rows_mult * rows_mult + 511) & ~511ull, T.words_min) : words_dir;
             // a score bound sizes the fixed-pitch rows: no more of them than the bound can reach.  When the rows reach it, a pair
             // that runs out of them is above the bound and final (wfa_bound.hpp)
-            const uint32_t pitch        = bound_row_pitch(kind);
-            const uint64_t words        = bound_cap_words(words_free, pitch, words_min, P.max_score, P.g);
-            const bool     bound_final  = bound_covers(words, pitch, P.max_score, P.g);
-            P.arena_words = words, P.compact_fmt = kind == 10 ? 8u : kind == 8 ? DUO_ARENA_FMT : kind == 6 ? 5u : bkind == 5 ? 4u : bkind == 9 ? 6u : (kind >= 3 ? (WFA_BLK_TILED ? 3u : 1u) : 0u);
+            const uint64_t words        = bound_cap_words(words_free, T.pitch, T.words_min, P.max_score, P.g);
+            const bool     bound_final  = bound_covers(words, T.pitch, P.max_score, P.g);
+            P.arena_words = words, P.compact_fmt = compact_fmt_of((Kind)T.base);
             const uint32_t waves_lds    = (uint32_t)std::min<size_t>(32, LDS_MAX_BYTES / lds_bytes);
             const bool     overlap      = ctx->opt_overlap != 0;
-            uint32_t       waves_per_cu = is_long ? std::min<uint32_t>(waves_lds, (kind == 11 && !P.census) ? 4 * WFA_BLK_WAVES : 16)
-                                          : kind == 10 ? std::min<uint32_t>(waves_lds, 8)
-                                          : kind == 8 ? std::min<uint32_t>(waves_lds, 4 * WFA_DUO_WAVES)
-                                          : kind == 4 ? std::min<uint32_t>(waves_lds, 12)
-                                          : kind >= 2 ? std::min<uint32_t>(waves_lds, 20)
-                                                      : (overlap ? std::min<uint32_t>(waves_lds, 24) : waves_lds);
+            uint32_t       waves_per_cu = std::min<uint32_t>(waves_lds, waves_cap(kind, P.census != 0, overlap));
             if (ctx->opt_packed_waves_per_cu > 0)
                 waves_per_cu = std::min<uint32_t>(waves_lds, (uint32_t)ctx->opt_packed_waves_per_cu);
             // Chunking: every pair of a chunk owns an arena until its backtrace has run.  Two chunk buffers
             // alternate so the (latency-bound) backtrace kernel of chunk c runs on a second stream beside the
             // (issue-bound) forward kernel of chunk c+1.
-            const uint64_t resident = (uint64_t)pairs_wave * ctx->num_cus * waves_per_cu;  // pairs in flight
+            const uint64_t resident = (uint64_t)T.pairs_wave * ctx->num_cus * waves_per_cu;  // pairs in flight
             uint64_t budget = (uint64_t)((double)ctx->total_mem * 0.35) / (overlap ? 2 : 1);
             uint64_t chunk  = std::max<uint64_t>(1, std::min<uint64_t>(count, budget / (words * 4ull)));
             if (overlap && count >= 8 * resident) chunk = std::min<uint64_t>(chunk, (count + 7) / 8);
@@ -1109,7 +1104,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             // (off unless asked for since round 2: with the forward pass at 20 ms per 1e6 pairs the write-through row
             // stores of the streaming instance cost more than the backtrace kernel they save -- 3e6 x 1 kbp pairs in two
             // chunks: 65.2 ms with a backtrace kernel per chunk, 70.5 ms streamed)
-            const bool stream_bt = kind == 3 && shape == 0 && !blk_batch && n_buf == 1 && ctx->opt_bt_stream > 0 && (int64_t)chunk >= ctx->opt_bt_stream_min &&
+            const bool stream_bt = kind == K_BLK16 && shape == 0 && !blk_batch && n_buf == 1 && ctx->opt_bt_stream > 0 && (int64_t)chunk >= ctx->opt_bt_stream_min &&
                                    ctx->opt_bt_stream_single != 0;
             P.done_q = nullptr, P.done_ctl = nullptr, P.n_stream_wgs = 0;
             if (stream_bt) {
@@ -1119,11 +1114,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             }
             ctx->timing.arena_bytes = std::max<uint64_t>(ctx->timing.arena_bytes, words * 4ull * chunk * n_buf);
             if (list && (rc2 = upload_work(list->data(), count))) return rc2;
-            while (ctx->evpool.size() < 4 * n_chunks) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                ctx->evpool.push_back(e);
-            }
+            if ((rc2 = grow_evpool(4 * n_chunks))) return rc2;
             if (!ctrl_zeroed) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 8, st));  // queue_head, redo_count
             ctrl_zeroed = false;
             hipStream_t st_bt = (n_buf == 2 || detach_bt) ? ctx->stream2 : st;
@@ -1141,7 +1132,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                     ctx->dbg_arena = P.arena, ctx->dbg_meta = P.pair_meta, ctx->dbg_words = words, ctx->dbg_first = first_pair,
                     ctx->dbg_n = cn, ctx->dbg_fmt = P.compact_fmt, ctx->dbg_g = P.g;
                 uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)ctx->num_cus * waves_per_cu,
-                                                            (cn + pairs_wave - 1) / pairs_wave);
+                                                            (cn + T.pairs_wave - 1) / T.pairs_wave);
                 const uint32_t n_bt = stream_bt ? (uint32_t)std::min<int64_t>(ctx->opt_bt_stream, grid / 4) : 0u;
                 if (stream_bt) {
                     // the first n_bt workgroups of the launch only backtrace; they take the place of forward waves when
@@ -1154,9 +1145,9 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 }
                 // the chunk's sequences 2-bit packed up front (unbatched 16-lane first pass over a range of pairs)
                 P.prepack = nullptr, P.prepack_words = 0;
-                P.lds_seq_words = is_long ? long_sw : kind == 10 ? lane_sw : kind == 8 ? duo_sw : seq_words;
-                if (kind == 10) P.sub_lds_words = lane_stride_words(lane_sw);
-                if ((kind == 3 && !blk_batch && !list && ctx->opt_prepack != 0) || kind == 8 || (kind == 10 && ctx->opt_lane_pack == 0) || is_long) {
+                P.lds_seq_words = is_long ? long_sw : (kind == K_LANE || kind == K_DUO) ? even_sw : seq_words;
+                if (kind == K_LANE) P.sub_lds_words = lane_stride_words(even_sw);
+                if ((kind == K_BLK16 && !blk_batch && !list && ctx->opt_prepack != 0) || kind == K_DUO || (kind == K_LANE && ctx->opt_lane_pack == 0) || is_long) {
                     const uint32_t pw = 4u + 2u * P.lds_seq_words;
                     if ((rc2 = ensure(ctx, ctx->prepack, (size_t)chunk * pw * 4))) return rc2;
                     if (ctx->pk_words)  // (packed input: the slots are copied from the uploaded words, no bytes in between)
@@ -1182,18 +1173,18 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 // (tests: the sub-wave kernels zero nothing -- no word the backtrace reads may be one they did not write)
                 if (ctx->opt_arena_poison) HIP_TRY(hipMemsetAsync(P.arena, 0xA5, (size_t)(words * 4ull * cn), st));
                 HIP_TRY(hipEventRecord(evFa, st));
-                if (kind == 8) {
+                if (kind == K_DUO) {
                     // (the first blocks of the kernel's queue claims rest on this launch's grid: at most ceil(cn / 8) waves, and the
                     // kernel keeps the grid in 16 bits of its flags word)
-                    if (grid > 0xFFFFu || pairs_wave != 8) return WFAHIP_ERR_INTERNAL;
+                    if (grid > 0xFFFFu || T.pairs_wave != 8) return WFAHIP_ERR_INTERNAL;
                     P.duo_claim = ctx->opt_duo_claim > 0 ? (uint32_t)ctx->opt_duo_claim : (uint32_t)DUO_CLAIM;
                     HIP_TRY(wfa_launch_duo(shape, P, grid, lds_bytes, st, P.census != 0, ctx->opt_duo_pk));
-                } else if (kind >= 3) {
+                } else if (kind != K_REG && kind != K_PACKED) {
                     uint32_t fl = (P.census ? (uint32_t)FWD_CENSUS : 0u) | (P.adaptive ? (uint32_t)FWD_ADAPTIVE : 0u);
-                    if (kind == 3 && stream_bt) fl |= FWD_STREAM;
+                    if (stream_bt) fl |= FWD_STREAM;
                     if (blk_batch) {
                         // entries per grab: the chunk's share of one resident group, cut into the fewest rounds of <= 8
-                        const uint64_t groups = (uint64_t)ctx->num_cus * 16 * pairs_wave;  // 4 waves per SIMD x 4 (8) pairs
+                        const uint64_t groups = (uint64_t)ctx->num_cus * 16 * T.pairs_wave;  // 4 waves per SIMD x 4 (8) pairs
                         const uint64_t share  = (cn + groups - 1) / groups;
                         const uint64_t rounds = (share + BLK_BATCH - 1) / BLK_BATCH;
                         P.blk_batch_n = (uint32_t)std::min<uint64_t>(BLK_BATCH, std::max<uint64_t>(1, (share + rounds - 1) / std::max<uint64_t>(1, rounds)));
@@ -1202,7 +1193,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                     }
                     // (instances without the census of stored words exist where a first pass runs them: the others count always)
                     HIP_TRY(wfa_launch_fwd(shape, kind, fl, P, grid, lds_bytes, st));
-                } else if (kind == 2)
+                } else if (kind == K_REG)
                     hipLaunchKernelGGL((wfa_reg_kernel<2, 4, 1>), dim3(grid), dim3(64), lds_bytes, st, P);
                 else
                     hipLaunchKernelGGL(wfa_packed_kernel, dim3(grid), dim3(64), lds_bytes, st, P);
@@ -1264,53 +1255,60 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             // short reads (at most 240 bases): a lane per pair
             const bool lane1   = can_d && ctx->opt_blk == 16 && seq_words <= (uint32_t)LN_SEQ_WORDS &&
                                  (ctx->opt_lane >= 2 || (ctx->opt_lane == 1 && (int64_t)n_pairs >= ctx->opt_lane_min_pairs));
-            const int  kind1   = long_first ? 11 : (duo1 && duo_short) ? 8 : lane1 ? 10 : duo1 ? 8 : narrow1 ? 6 : (can_d ? (ctx->opt_blk == 8 ? 4 : 3) : (can_c ? 2 : 1));
+            const Kind kind1   = long_first ? K_LONG16 : (duo1 && duo_short) ? K_DUO : lane1 ? K_LANE : duo1 ? K_DUO : narrow1 ? K_NARROW : (can_d ? (ctx->opt_blk == 8 ? K_BLK8 : K_BLK16) : (can_c ? K_REG : K_PACKED));
             // the rungs above the 64-diagonal first pass: 128 and 256 diagonals (long reads: the same with sliding sequence windows)
-            const int  kind_mid = long_first ? 12 : 9, kind_wide = long_first ? 13 : 5, kind_64 = long_first ? 11 : 3;
+            const Kind kind_mid = long_first ? K_LONG32 : K_BLK32, kind_wide = long_first ? K_LONG64 : K_BLK64, kind_64 = long_first ? K_LONG16 : K_BLK16;
             // Pilot: on a large batch with wf-adaptive off the first 4 096 pairs go first.  When most of them leave the
             // 64-diagonal window the rest does not start there only to be handed on: it goes straight to the
             // wave-per-pair kernel (256 diagonals) if that one takes most of the pilot's leftovers, else to the
             // generic ladder.  (wf-adaptive or short reads: narrow bands, no pilot.)
             uint64_t done_pairs = 0;
             bool     skip_rest  = false;
-            int      kind_rest  = kind1;
-            const bool wide_ok  = kind1 >= 3 && ctx->opt_blk_wide != 0;
+            Kind     kind_rest  = kind1;
+            const bool rows1    = kind_traits(kind1).pitch != 0;  // the first pass is one of the fixed-pitch kinds: the rungs below are its kernels
+            const bool wide_ok  = rows1 && ctx->opt_blk_wide != 0;
             std::vector<uint64_t> redo_w;  // handed on by the 256-diagonal kernel, or not eligible for it
-            // band failures of `from` -> kind 9 (128 diagonals, two pairs per wave; unless `from` comes from there), its band
-            // failures -> kind 5 (256 diagonals, a wave per pair); everything else -> redo_w
-            uint64_t mid_in = 0, mid_fail = 0;  // what the 128-diagonal instance was given / handed on (learned routing below)
-            const auto wide_pass = [&](std::vector<uint64_t> &from, bool from_mid = false) -> int {
+            const auto is_band = [](uint32_t s) { return s == ST_REDO_BAND; };
+            const auto n_taken = [](const std::vector<uint64_t> &from, auto take) {
+                return (size_t)std::count_if(from.begin(), from.end(), [&](uint64_t e) { return take((uint32_t)(e >> 32)); });
+            };
+            // One retry rung: the entries of `from` whose status `take` accepts run on `kind` as a pass of their own (in the order of
+            // `from`; by_pair: sorted by pair) and count as packed pairs, except those the pass hands on again: `out`.  The other entries
+            // of `from` go to the end of `rest`, in order.  Nothing taken: no pass, `out` empty.  (cls, rows_mult: forward_pass's.)
+            const auto rung = [&](Kind kind, const std::vector<uint64_t> &from, auto take, std::vector<uint64_t> &rest, std::vector<uint64_t> &out,
+                                  const PassClass *cls = nullptr, uint64_t rows_mult = 0, bool by_pair = false) -> int {
                 std::vector<uint32_t> lst;
                 for (uint64_t e : from) {
-                    if ((uint32_t)(e >> 32) == ST_REDO_BAND) lst.push_back((uint32_t)e);
-                    else redo_w.push_back(e);
+                    if (take((uint32_t)(e >> 32))) lst.push_back((uint32_t)e);
+                    else rest.push_back(e);
                 }
-                from.clear();
-                if (lst.empty()) return 0;
-                const size_t n_in = lst.size();
-                std::vector<uint64_t> r2;
-                if (!from_mid && ctx->opt_blk_mid != 0) {
+                out.clear();
+                if (lst.empty()) return WFAHIP_OK;
+                if (by_pair) std::sort(lst.begin(), lst.end());
+                const int r = forward_pass(kind, &lst, 0, lst.size(), out, false, cls, rows_mult);
+                if (r == WFAHIP_OK) ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - out.size());
+                return r;  // WFAHIP_ERR_* (negative): the whole call fails, no pair is silently dropped
+            };
+            // band failures of `from` -> the 128-diagonal instance (two pairs per wave; unless `from` comes from there), its band
+            // failures -> the 256-diagonal one (a wave per pair); everything else -> redo_w.  0: no band failure among them, 2: the
+            // wide kernels do not take most of them either, else 1
+            uint64_t mid_in = 0, mid_fail = 0;  // what the 128-diagonal instance was given / handed on (learned routing below)
+            const auto wide_pass = [&](std::vector<uint64_t> &from, bool from_mid = false) -> int {
+                std::vector<uint64_t> src, r2;
+                src.swap(from);
+                const size_t n_in = n_taken(src, is_band);
+                int          r;
+                if (!from_mid && ctx->opt_blk_mid != 0 && n_in) {
                     // (long reads, leftovers that are a few waves per SIMD anyway: a wave per pair with two diagonals per lane steps
                     // in half the instructions of two pairs per wave with four -- 2e4 x 50 kbp: 53.1 -> 47.4 ms per step, the 4 186 leftovers' pass 20.6 -> ~15 ms)
-                    const int km = (long_first && ctx->opt_long_mid_lone != 0 && lst.size() <= 6ull * (uint64_t)ctx->num_cus * 4ull) ? 15 : kind_mid;
-                    const int rcm = forward_pass(km, &lst, 0, lst.size(), r2, false);
-                    if (rcm) return rcm;
-                    ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - r2.size());
-                    mid_in += lst.size();
-                    lst.clear();
-                    for (uint64_t e : r2) {
-                        if ((uint32_t)(e >> 32) == ST_REDO_BAND) lst.push_back((uint32_t)e);
-                        else redo_w.push_back(e);
-                    }
-                    mid_fail += lst.size();
-                    r2.clear();
-                    if (lst.empty()) return 1;
+                    const Kind km = (long_first && ctx->opt_long_mid_lone != 0 && n_in <= 6ull * (uint64_t)ctx->num_cus * 4ull) ? K_LONE128 : kind_mid;
+                    if ((r = rung(km, src, is_band, redo_w, r2))) return r;
+                    src.swap(r2);
+                    mid_in += n_in, mid_fail += n_taken(src, is_band);
                 }
-                const int rcw = forward_pass(kind_wide, &lst, 0, lst.size(), r2, false);
-                if (rcw) return rcw;  // WFAHIP_ERR_* (negative): the whole call fails, no pair is silently dropped
-                ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - r2.size());
+                if ((r = rung(kind_wide, src, is_band, redo_w, r2))) return r;
                 redo_w.insert(redo_w.end(), r2.begin(), r2.end());
-                return r2.size() * 2 > n_in ? 2 : 1;  // 2: the wide kernels do not take most of them either
+                return n_in == 0 ? 0 : r2.size() * 2 > n_in ? 2 : 1;
             };
             uint64_t n_first_fail = 0;  // pairs the first-pass kernel(s) handed on
             if (n_pairs >= 65536 && !P.adaptive && max_len >= 200 && ctx->opt_pilot != 0) {  // (the pilot costs one extra pass, ~0.1 ms)
@@ -1327,41 +1325,40 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             }
             // a class of batches whose pairs were mostly handed on for their band the last time starts on the window that
             // took them (1 kbp at 20 % error: every pair needs ~100 diagonals)
-            // (band_kind is kept in terms of the plain instances -- 3 / 9 / 5 -- and mapped to this call's rungs)
-            if (wide_ok && done_pairs == 0 && ctx->band_key == rkey && ctx->band_kind != 0 && (kind1 == 3 || kind1 == 8 || kind1 == 11) &&
-                (ctx->band_kind == 5 || ctx->band_kind == 3 || ctx->opt_blk_mid != 0) &&
-                !(ctx->band_kind == 3 && ctx->opt_duo >= 2) &&  // (option duo = 2: the variable-lanes kernel whatever was learned)
+            // (band_kind is kept in terms of the plain instances -- K_BLK16 / K_BLK32 / K_BLK64 -- and mapped to this call's rungs)
+            if (wide_ok && done_pairs == 0 && ctx->band_key == rkey && ctx->band_kind != 0 && (kind1 == K_BLK16 || kind1 == K_DUO || kind1 == K_LONG16) &&
+                (ctx->band_kind == K_BLK64 || ctx->band_kind == K_BLK16 || ctx->opt_blk_mid != 0) &&
+                !(ctx->band_kind == K_BLK16 && ctx->opt_duo >= 2) &&  // (option duo = 2: the variable-lanes kernel whatever was learned)
                 (++ctx->band_calls & 15u) != 0u)
-                kind_rest = ctx->band_kind == 5 ? kind_wide : ctx->band_kind == 9 ? kind_mid : kind_64;
+                kind_rest = ctx->band_kind == K_BLK64 ? kind_wide : ctx->band_kind == K_BLK32 ? kind_mid : kind_64;
             // Long reads in batches too small to fill the GPU start on the wider windows: 500 pairs are 500 waves of one pair each
             // (a wave alone on its SIMD steps in the same ~1.5 us whether it holds one pair or four), and nothing is handed on for
             // its band -- a fifth of 50 kbp pairs at 5 % error leave a 64-diagonal window at some score
-            if (long_first && done_pairs == 0 && kind_rest == 11 && wide_ok) {
+            if (long_first && done_pairs == 0 && kind_rest == K_LONG16 && wide_ok) {
                 const uint64_t simds = (uint64_t)ctx->num_cus * 4;
-                if (ctx->opt_long_first >= 11 && ctx->opt_long_first <= 15) kind_rest = (int)ctx->opt_long_first;
+                if (ctx->opt_long_first >= K_LONG16 && ctx->opt_long_first <= K_LONE128) kind_rest = (Kind)ctx->opt_long_first;
                 // (a wave per pair, two diagonals per lane: 128 diagonals at half the instructions of a step.  3 000 / 6 000 pairs of
                 // 50 kbp: 14.2 / 23.1 ms against 18.1 / 25.3 with two pairs per wave and 26.6 with four; 2e4 pairs are issue-bound and
                 // four pairs per wave share a step's instructions)
-                else if (n_pairs <= 6 * simds) kind_rest = 15;
+                else if (n_pairs <= 6 * simds) kind_rest = K_LONE128;
             }
             if (!skip_rest) {
                 std::vector<uint64_t> more;
                 if ((rc = forward_pass(kind_rest, nullptr, done_pairs, n_pairs - done_pairs, more, true))) return rc;
                 n_first_fail += more.size();
-                uint64_t n_band = 0;
-                for (uint64_t e : more) n_band += (uint32_t)(e >> 32) == ST_REDO_BAND;
-                if (kind_rest == kind_mid || kind_rest == 15) {
+                const uint64_t n_band = n_taken(more, is_band);
+                if (kind_rest == kind_mid || kind_rest == K_LONE128) {
                     mid_in += n_pairs - done_pairs, mid_fail += n_band;
                     if ((rc = wide_pass(more, true)) < 0) return rc;  // -> the 256-diagonal instance
                 } else {
                     (kind_rest == kind_wide ? redo_w : redo1).insert((kind_rest == kind_wide ? redo_w : redo1).end(), more.begin(), more.end());
                 }
-                if ((kind_rest == 3 || kind_rest == 8 || kind_rest == 11) && P.adaptive && n_band * 2 > n_pairs - done_pairs) ctx->band_key = rkey, ctx->band_kind = 9;
-                else if (kind_rest == 15 && P.adaptive && n_band * 2 > n_pairs - done_pairs) ctx->band_key = rkey, ctx->band_kind = 5;  // (128 diagonals were not enough)
+                if ((kind_rest == K_BLK16 || kind_rest == K_DUO || kind_rest == K_LONG16) && P.adaptive && n_band * 2 > n_pairs - done_pairs) ctx->band_key = rkey, ctx->band_kind = K_BLK32;
+                else if (kind_rest == K_LONE128 && P.adaptive && n_band * 2 > n_pairs - done_pairs) ctx->band_key = rkey, ctx->band_kind = K_BLK64;  // (128 diagonals were not enough)
                 // (bands mostly wider than 32 diagonals: the variable-lanes kernel then runs its pairs wide, parks and resumes for
                 // nothing and hands on more than the plain 64-diagonal kernel would -- 1e6 x 1 kbp @8 %: 53-71 ms against 46)
-                else if (kind_rest == 8 && n_band * 50 > n_pairs - done_pairs) ctx->band_key = rkey, ctx->band_kind = 3;
-                else if (kind_rest == 8 && ctx->band_key == rkey) ctx->band_kind = 0;
+                else if (kind_rest == K_DUO && n_band * 50 > n_pairs - done_pairs) ctx->band_key = rkey, ctx->band_kind = K_BLK16;
+                else if (kind_rest == K_DUO && ctx->band_key == rkey) ctx->band_kind = 0;
                 else if (kind_rest == kind_64 && kind1 == kind_64 && ctx->band_key == rkey) ctx->band_kind = 0;
                 done_pairs = n_pairs;
             }
@@ -1384,55 +1381,31 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             // Mixed lengths: the long pairs the short pairs' kernels handed on for their length (ST_REDO_LDS) take the
             // sliding-window instances now -- slots, windows and arenas sized for the batch's longest pair -- by their number:
             // a wave per pair up to one per SIMD; what leaves its band there tries 256 diagonals; the rest goes down the ladder
-            if (can_long && sub_len_used != 0) {
-                std::vector<uint32_t> lst;
-                std::vector<uint64_t> keep, r2;
-                for (uint64_t e : redo1) ((uint32_t)(e >> 32) == ST_REDO_LDS ? (void)lst.push_back((uint32_t)e) : (void)keep.push_back(e));
-                if (!lst.empty()) {
-                    std::sort(lst.begin(), lst.end());
-                    const uint32_t keep_sw = fp_seq_words;
-                    const uint64_t keep_wd = fp_words_dir, simds = (uint64_t)ctx->num_cus * 4;
-                    fp_seq_words = (max_len + 15) / 16 + 1, fp_words_dir = words_dir_of(max_len);
-                    const int kl = lst.size() <= simds ? 15 : lst.size() <= 4 * simds ? 12 : 11;
-                    rc = forward_pass(kl, &lst, 0, lst.size(), r2, false);
-                    if (rc == WFAHIP_OK) {
-                        ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - r2.size());
-                        lst.clear();
-                        for (uint64_t e : r2) ((uint32_t)(e >> 32) == ST_REDO_BAND ? (void)lst.push_back((uint32_t)e) : (void)keep.push_back(e));
-                        r2.clear();
-                        if (!lst.empty() && (rc = forward_pass(13, &lst, 0, lst.size(), r2, false)) == WFAHIP_OK) {
-                            ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - r2.size());
-                            keep.insert(keep.end(), r2.begin(), r2.end());
-                        }
-                    }
-                    fp_seq_words = keep_sw, fp_words_dir = keep_wd;
-                    if (rc) return rc;
-                    redo1.swap(keep);
-                }
+            const auto   is_lds = [](uint32_t s) { return s == ST_REDO_LDS; };
+            const size_t n_lds  = (can_long && sub_len_used != 0) ? n_taken(redo1, is_lds) : 0;
+            if (n_lds) {
+                const uint64_t  simds = (uint64_t)ctx->num_cus * 4;
+                const PassClass long_class{(max_len + 15) / 16 + 1, words_dir_of(max_len)};
+                const Kind      kl = n_lds <= simds ? K_LONE128 : n_lds <= 4 * simds ? K_LONG32 : K_LONG16;
+                std::vector<uint64_t> keep, r2, r3;
+                if ((rc = rung(kl, redo1, is_lds, keep, r2, &long_class, 0, true))) return rc;
+                if ((rc = rung(K_LONG64, r2, is_band, keep, r3, &long_class))) return rc;
+                keep.insert(keep.end(), r3.begin(), r3.end());
+                redo1.swap(keep);
             }
             Job jb, ja;
-            jb.mode = 1, jb.level = 0, jb.all = false;
-            ja.mode = 0, ja.level = 0, ja.all = false;
+            jb.mode = 1;
             // A few thousand leftovers finish sooner as one generic launch (one wave per pair, all of them resident at
             // once, backtrace included) than through another forward + backtrace pass; beyond that the LDS-ring
             // kernel's throughput wins.
             const uint64_t resident_generic = (uint64_t)ctx->num_cus * 32;
-            if (kind1 == 6 || kind1 == 10) {  // band / arena failures of the 32-diagonal instance -> the 64-diagonal one.  (What the variable-lanes
+            if (kind1 == K_NARROW || kind1 == K_LANE) {  // band / arena failures of the 32-diagonal instance -> the 64-diagonal one.  (What the variable-lanes
                                // kernel hands on -- a band wider than a row, rarely no park record free: 0.08 % of 1 kbp pairs --
                                // goes straight to the 128-diagonal instance below: one retry pass instead of two.)
-                std::vector<uint32_t> lst;
                 std::vector<uint64_t> keep, r2;
-                for (uint64_t e : redo1) {
-                    const uint32_t stw = (uint32_t)(e >> 32);
-                    if (stw == ST_REDO_BAND || stw == ST_REDO_ARENA) lst.push_back((uint32_t)e);
-                    else keep.push_back(e);
-                }
-                if (!lst.empty()) {
-                    if ((rc = forward_pass(3, &lst, 0, lst.size(), r2, false))) return rc;
-                    ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - r2.size());
-                    keep.insert(keep.end(), r2.begin(), r2.end());
-                    redo1.swap(keep);
-                }
+                if ((rc = rung(K_BLK16, redo1, [](uint32_t s) { return s == ST_REDO_BAND || s == ST_REDO_ARENA; }, keep, r2))) return rc;
+                keep.insert(keep.end(), r2.begin(), r2.end());
+                redo1.swap(keep);
             }
             if (wide_ok) {
                 // pairs whose band outgrew the 64-diagonal window: the same kernel with a wave per pair (256 diagonals)
@@ -1441,23 +1414,19 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             }
             redo1.insert(redo1.end(), redo_w.begin(), redo_w.end());
             redo_w.clear();
-            if (kind1 >= 3) {
+            if (rows1) {
                 // pairs that ran out of arena rows (a score above half the read length: error rates beyond ~8 %): the same
                 // 64-diagonal kernel with four times the rows; and the class starts with more rows next time
-                std::vector<uint32_t> lst;
-                std::vector<uint64_t> keep, r2;
-                for (uint64_t e : redo1) ((uint32_t)(e >> 32) == ST_REDO_ARENA ? (void)lst.push_back((uint32_t)e) : (void)keep.push_back(e));
-                if (lst.size() * 64 > n_pairs && ctx->opt_packed_arena_bytes <= 0) {
+                const auto   is_arena = [](uint32_t s) { return s == ST_REDO_ARENA; };
+                const size_t n_arena  = n_taken(redo1, is_arena);
+                if (n_arena * 64 > n_pairs && ctx->opt_packed_arena_bytes <= 0) {
                     const uint32_t nxt = (uint32_t)std::min<uint64_t>(8, arena_mult * 2);
                     if (ctx->rows_key != rkey || ctx->rows_scale < nxt) ctx->rows_key = rkey, ctx->rows_scale = nxt;
                 }
-                if (!lst.empty() && arena_mult <= 8 && ctx->opt_packed_arena_bytes <= 0) {
-                    const uint64_t keep_mult = arena_mult;
-                    arena_mult *= 4;
-                    rc = forward_pass((kind_rest == kind_wide || kind_rest == kind_mid || kind_rest >= 14) ? kind_rest : kind_64, &lst, 0, lst.size(), r2, false);
-                    arena_mult = keep_mult;
-                    if (rc) return rc;
-                    ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - r2.size());
+                if (n_arena && arena_mult <= 8 && ctx->opt_packed_arena_bytes <= 0) {
+                    const bool own = kind_rest == kind_wide || kind_rest == kind_mid || kind_rest == K_LONE64 || kind_rest == K_LONE128;
+                    std::vector<uint64_t> keep, r2;
+                    if ((rc = rung(own ? kind_rest : kind_64, redo1, is_arena, keep, r2, nullptr, arena_mult * 4))) return rc;
                     keep.insert(keep.end(), r2.begin(), r2.end());
                     redo1.swap(keep);
                     if (wide_ok) {  // (what outgrows the 64-diagonal window on the way)
@@ -1468,23 +1437,15 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             }
             redo1.insert(redo1.end(), redo_w.begin(), redo_w.end());
             redo_w.clear();
-            if (kind1 >= 2 && can_b && !wide_ok && redo1.size() > resident_generic) {
-                // second chance on the LDS-ring kernel (64-diagonal bands at any alignment) for band/arena misses
-                std::vector<uint32_t> lst;
-                for (uint64_t e : redo1) {
-                    const uint32_t stw = (uint32_t)(e >> 32);
-                    if (stw == ST_REDO_BYTES) jb.pairs.push_back((uint32_t)e);
-                    else if (stw == ST_REDO_BAND) lst.push_back((uint32_t)e);
-                    else ja.pairs.push_back((uint32_t)e);
-                }
-                if (!lst.empty()) {
-                    if ((rc = forward_pass(1, &lst, 0, lst.size(), redo2, false))) return rc;
-                    ctx->timing.n_packed_pairs += (uint32_t)(lst.size() - redo2.size());
-                    for (uint64_t e : redo2) ((uint32_t)(e >> 32) == ST_REDO_BYTES ? jb : ja).pairs.push_back((uint32_t)e);
-                }
+            std::vector<uint64_t> rest;
+            if (kind1 != K_PACKED && can_b && !wide_ok && redo1.size() > resident_generic) {
+                // second chance on the LDS-ring kernel (64-diagonal bands at any alignment) for band misses
+                if ((rc = rung(K_PACKED, redo1, is_band, rest, redo2))) return rc;
             } else {
-                for (uint64_t e : redo1) ((uint32_t)(e >> 32) == ST_REDO_BYTES ? jb : ja).pairs.push_back((uint32_t)e);
+                rest.swap(redo1);
             }
+            for (const std::vector<uint64_t> *v : {&rest, &redo2})
+                for (uint64_t e : *v) ((uint32_t)(e >> 32) == ST_REDO_BYTES ? jb : ja).pairs.push_back((uint32_t)e);
             if (skip_rest)
                 for (uint64_t i = done_pairs; i < n_pairs; i++) ja.pairs.push_back((uint32_t)i);
             std::sort(ja.pairs.begin(), ja.pairs.end());
@@ -1498,7 +1459,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 Job js = *jp, jl = *jp;
                 js.pairs.clear(), jl.pairs.clear();
                 js.max_len = sub_len_used;
-                for (uint32_t pid : jp->pairs) (h_len[pid] <= sub_len_used ? js : jl).pairs.push_back(pid);
+                for (uint32_t pid : jp->pairs) (std::max(ql[pid], tl[pid]) <= sub_len_used ? js : jl).pairs.push_back(pid);
                 if (!js.pairs.empty()) jobs.push_back(std::move(js));
                 if (!jl.pairs.empty()) jobs.push_back(std::move(jl));
             }
@@ -1521,7 +1482,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 P.debug_info = nullptr;
             }
 #endif
-            if (ctx->band_key == rkey && ctx->band_kind == 9 && mid_in > 0 && mid_fail * 2 > mid_in) ctx->band_kind = 5;
+            if (ctx->band_key == rkey && ctx->band_kind == K_BLK32 && mid_in > 0 && mid_fail * 2 > mid_in) ctx->band_kind = K_BLK64;
             first       = false;
             packed_done = true;
         }
@@ -1531,13 +1492,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
     // level.  A context remembers, per workload class (mode, wf-adaptive, penalties, length bucket), the lowest level by
     // which 90 % of the long pairs had finished, and starts the next call of that class there (the slots of the last
     // levels are tens of GB: a few outliers must not size everybody's arena).
-    uint64_t  lkey = 0;
-    {
-        uint32_t lb = 0;
-        while ((2u << lb) <= max_len) lb++;
-        lkey = 1ull | ((uint64_t)lb << 1) | ((uint64_t)(ctx->opt_team_compact != 0) << 7) | ((uint64_t)P.global_alignment << 8) | ((uint64_t)P.adaptive << 9) | ((uint64_t)(P.x & 0xFFF) << 12) |
-               ((uint64_t)(P.oe & 0xFFF) << 24) | ((uint64_t)(P.e & 0xFFF) << 36) | ((uint64_t)(P.max_dist_diff & 0xFFFF) << 48);
-    }
+    const uint64_t lkey = class_key | ((uint64_t)(ctx->opt_team_compact != 0) << 7) | ((uint64_t)P.global_alignment << 8);
     int      learned_now = -1;
     uint64_t team_total = 0, team_done = 0;
     // (tracked for every batch of long pairs that goes straight to this ladder -- team kernel or one workgroup per pair:
@@ -1736,10 +1691,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         std::vector<uint32_t> team_order;
         // (the hint reads the batch's length arrays: not for a handful of long pairs out of millions of short ones)
         if (team_T > 0 && ctx->opt_team_order != 0 && P.adaptive && n_work > team_n && n_work <= (1u << 24) && (n_pairs <= (1u << 20) || n_pairs <= 64 * n_work)) {
-            std::vector<uint32_t> ql(n_pairs), tl(n_pairs);
-            HIP_TRY(hipMemcpyAsync(ql.data(), d_q_len, n_pairs * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(tl.data(), d_t_len, n_pairs * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
+            if ((rc = host_lens())) return rc;
             team_order.resize(n_work);
             if (job.all) std::iota(team_order.begin(), team_order.end(), 0u);
             else std::copy(job.pairs.begin(), job.pairs.end(), team_order.begin());
@@ -1896,7 +1848,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         ctx->timing.kernel_ms += ms;
         if (first) {
             ctx->timing.main_kernel_ms = ms, ctx->timing.n_main_launches = 1, first = false;
-            if (team_T > 0) ctx->timing.main_kernel_kind = team_c ? 17 : 7;  // wfa_teamc_kernel / wfa_team_kernel (bench.py names the dominant kernel by this)
+            if (team_T > 0) ctx->timing.main_kernel_kind = team_c ? K_TEAMC : K_TEAM;  // wfa_teamc_kernel / wfa_team_kernel (bench.py names the dominant kernel by this)
             after_scout = scout_now;
         } else if (after_scout && team_T > 0 && team_c) {  // (the scout pass and the teams behind it are one kernel: its launches add up)
             ctx->timing.main_kernel_ms += ms, ctx->timing.n_main_launches++;
@@ -1919,7 +1871,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 (stw == ST_REDO_WIDE ? jw : (stw == ST_REDO_BYTES || stw == ST_REDO_LDS ? jb : ja)).pairs.push_back((uint32_t)ent[i]);
             }
             // (a pair the scouts hand on has not failed anything; behind wfa_wide_kernel every pair it did not finish has been counted already, once)
-            if (ctx->timing.main_kernel_kind != 18) ctx->timing.n_retried_pairs += n_redo - (uint32_t)jw.pairs.size();
+            if (ctx->timing.main_kernel_kind != K_WIDE) ctx->timing.n_retried_pairs += n_redo - (uint32_t)jw.pairs.size();
             if (!jw.pairs.empty()) jobs.push_front(std::move(jw));
             if (!jb.pairs.empty()) jobs.push_back(std::move(jb));
             if (!ja.pairs.empty()) jobs.push_back(std::move(ja));

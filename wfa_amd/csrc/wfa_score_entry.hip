@@ -309,7 +309,7 @@ static int score_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         tm.kernel_ms = tm.main_kernel_ms = ms;
-        tm.main_kernel_kind = R.glob ? (long_main ? 23u : 19u) : 20u;
+        tm.main_kernel_kind = R.glob ? (long_main ? K_SCORE_LONG : K_SCORE) : K_SCORE_WIDE;
         // (long pairs that were not listed: wfa_score_kernel said ST_REDO_LDS, or never saw them)
         for (const uint64_t i : lbytes) res[i] = make_uint2(ST_REDO_BYTES, 0u);
     } else {
@@ -432,7 +432,7 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         tm.kernel_ms = tm.main_kernel_ms = ms;
-        tm.main_kernel_kind = R.glob ? (long_main ? 23u : 19u) : 20u;
+        tm.main_kernel_kind = R.glob ? (long_main ? K_SCORE_LONG : K_SCORE) : K_SCORE_WIDE;
     } else {
         for (uint64_t i = 0; i < n_pairs; i++) res[i] = make_uint2(ST_REDO_BAND, 0u);
     }
@@ -585,7 +585,7 @@ static int score_batch_device_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
         P.score_out = S.score_out, P.max_score = max_score;
         bool long_main = false;
         if ((rc = score_launch(ctx, STAGE_BYTES, P, R, n_pairs, max_len, skip_short, n_listed, use_long ? n_long : 0, st, tm, long_main))) return rc;
-        tm.main_kernel_kind = R.glob ? (long_main ? 23u : 19u) : 20u;
+        tm.main_kernel_kind = R.glob ? (long_main ? K_SCORE_LONG : K_SCORE) : K_SCORE_WIDE;
     }
     // ---- what they handed back (every pair, for a shape without an instance): counted, then gathered in pair order
     S.all = R.on_kernel ? 0u : 1u;
@@ -833,7 +833,7 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         tm.kernel_ms = tm.main_kernel_ms = ms;
-        tm.main_kernel_kind = glob ? (long_main ? 24u : 21u) : 22u;
+        tm.main_kernel_kind = glob ? (long_main ? K_MATRIX_LONG : K_MATRIX) : K_MATRIX_WIDE;
     }
     // ---- the full path: what the kernels handed back -- or every cell, for a penalty shape without an instance -- a batch of at most
     // MX_FB_PAIRS cells at a time

@@ -6,30 +6,19 @@
 #define WFA_WIDE_PLAN_UNIT 1
 #include "wfa_wide.hpp"
 #include "wfa_wide_plan.hpp"
+#include "wfa_fwd.hpp"  // WFA_FWD_SHAPES
 
 namespace wfa {
 
 // wfa_wide_kernel<.., SCORE = false, STAGE_PACKED> of penalty shape `shape`: as wfa_launch_wide (wfa_host.hip) launches the byte instances
 hipError_t wfa_launch_wide_packed(int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st) {
-    const auto go = [&](auto kern, int nw) -> hipError_t {
-        if (lds_bytes > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds_bytes, st, P);
-        return hipGetLastError();
-    };
-#define WFA_WIDE_PK_SHAPE(I, DX_, DOE_)                                                                         \
+    const auto go = [&](auto kern, int nw) { return wfa_launch_wide_instance(kern, nw, P, grid, lds_bytes, st); };
+#define WFA_WIDE_PK_SHAPE(I, tag, DX_, DOE_)                                                                    \
     case 3 * I: return go(wfa_wide_kernel<DX_, DOE_, 0, 1, false, STAGE_PACKED>, 1);                           \
     case 3 * I + 1: return go(wfa_wide_kernel<DX_, DOE_, 0, 4, false, STAGE_PACKED>, 4);                       \
     case 3 * I + 2: return go(wfa_wide_kernel<DX_, DOE_, 1, 1, false, STAGE_PACKED>, 1);
     switch (shape * 3 + (phase ? 2 : (waves > 1 ? 1 : 0))) {
-        WFA_WIDE_PK_SHAPE(0, 2, 4)
-        WFA_WIDE_PK_SHAPE(1, 1, 3)
-        WFA_WIDE_PK_SHAPE(2, 1, 2)
-        WFA_WIDE_PK_SHAPE(3, 2, 3)
-        WFA_WIDE_PK_SHAPE(4, 2, 2)
-        WFA_WIDE_PK_SHAPE(5, 3, 3)
+        WFA_FWD_SHAPES(WFA_WIDE_PK_SHAPE)
     }
 #undef WFA_WIDE_PK_SHAPE
     return hipErrorInvalidValue;
