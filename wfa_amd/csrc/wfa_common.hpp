@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wfa_ladder.hpp"  // the constants the long-pair ladder's host-side plan shares with the kernels: DIR_WORDS, the LDS rings
 
 // Kernels that are not templates are defined in headers that more than one translation unit includes (wfa_host.hip and
 // wfa_duo.hip): the unit that does not launch them defines WFA_NO_AUX_KERNELS and gets the device functions only.
@@ -56,7 +57,7 @@ struct alignas(16) DirEnt {
     uint32_t stride;
     uint32_t pad[3];
 };
-constexpr int DIR_WORDS = 8;  // 32-byte entries
+static_assert(sizeof(DirEnt) == DIR_ENT_BYTES, "wfa_ladder.hpp: DIR_ENT_BYTES / DIR_WORDS");
 
 struct KParams {
     // input (device pointers)

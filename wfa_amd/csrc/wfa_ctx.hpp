@@ -1,12 +1,13 @@
 // wfa_ctx.hpp -- what the host-side translation units of libwfahip.so share: the context, its device buffers, the error
 // macros of the C-ABI, and the declarations of the functions one unit defines for the others.
 //   wfa_host.hip   the router: context life cycle, options, wfahip_align_batch_device -- the sub-wave passes and the
-//                  long-pair ladder behind it (align_device)
+//                  long-pair ladder behind it (align_device; the plan of a ladder job is host-only arithmetic: wfa_ladder.hpp)
 //   wfa_entry.hip  the host entries: wfahip_align_batch (sliced upload / alignment / download), packed input,
 //                  wfahip_align_pair, submit / collect, the results cache
 //   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_packed, wfahip_score_batch_device, wfahip_score_matrix -- a
 //                  router each over the launch section, the geometry and the full-path fallback they share
-//   wfa_debug.hip  parity and measurement aids: wavefront dumps, the compact arenas, the device-side generator, the clock probe
+//   wfa_debug.hip  parity and measurement aids: wavefront dumps, the compact arenas, the device-side generator, the clock probe,
+//                  the read-back behind a launch of the team kernels
 #pragma once
 #include "../../include/wfa_hip.h"
 #include "wfa_common.hpp"
@@ -233,7 +234,7 @@ struct wfahip_ctx {
     int64_t       opt_learn                = 1;   // 1: long pairs start on the arena level the previous call of the same kind ended on
     uint64_t      learn_key                = 0;   // workload class of the last call that used the team kernel
     int           learn_level              = 0;   // ... and the level by which 90 % of its long pairs had finished
-    uint32_t      learn_calls              = 0;
+    uint32_t      learn_calls              = 0;   // calls of that class since the level was learned (every sixteenth one probes one level lower)
     // rows per pair of the blocked kernels' arenas: the default holds scores up to half the read length (error rates up
     // to ~8 % at 4/6/2); a class of batches whose pairs ran out of rows gets twice / four times / eight times as many
     // from its next call on (the call that finds out re-runs those pairs on the same kernel with four times the rows)
@@ -244,7 +245,7 @@ struct wfahip_ctx {
     uint64_t      band_key                 = 0;
     int           band_kind                = 0;
     uint32_t      band_calls               = 0;   // (every sixteenth call of the class starts on its natural first pass again: data changes)
-    int64_t       opt_blk_mid              = 1;   // 1: band failures of the 64-diagonal kernels try the 128-diagonal instance before the 256-diagonal one   // calls of that class since the level was learned (every 4th one probes one level lower)
+    int64_t       opt_blk_mid              = 1;   // 1: band failures of the 64-diagonal kernels try the 128-diagonal instance before the 256-diagonal one
     int64_t       opt_mem_limit            = 0;   // tests: pretend the device has this many bytes (arena budgets follow)
     int           force_mode               = -1;  // debug: start the ladder in this mode
     // debug / parity aid (wfahip_debug_compact_arena): where the first chunk of the most recent first pass left its arena
@@ -337,8 +338,6 @@ inline int check_params(const wfahip_params *p) {
     return WFAHIP_OK;
 }
 
-constexpr size_t LDS_MAX_BYTES = 160 * 1024;
-
 // ---- defined in wfa_entry.hip
 void results_zero(wfahip_results *r);
 // records + ops of n pairs (as the kernels leave them) -> the malloc'd arrays of a wfahip_results
@@ -349,6 +348,11 @@ int align_batch_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *se
 // wfahip_align_batch_packed behind its guard: the same for wfahip_score_batch_packed, over a word buffer of that entry's own
 int align_batch_packed_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
                              const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
+
+// ---- defined in wfa_debug.hip
+// behind a launch of the team kernels (team_c: wfa_teamc_kernel) and its synchronisation: prints the reports of their control words and
+// returns the team whose barrier timed out (last_error set) or -1; rc: the error of a copy that failed
+int team_read_back(wfahip_ctx *ctx, bool team_c, uint32_t team_n, uint32_t team_T, int &rc);
 
 // ---- defined in wfa_host.hip
 // the device-resident core behind every entry (exception-safe: the host entry calls it while its upload / download threads are joinable)

@@ -19,9 +19,7 @@
 
 namespace wfa {
 
-// LDS words used besides the two packed sequences
-constexpr int GEN_LDS_EXTRA_WORDS = 16;
-
+// (GEN_LDS_EXTRA_WORDS, the LDS words used besides the two packed sequences: wfa_ladder.hpp)
 template <int WAVES, int MODE>
 __global__ __launch_bounds__(64 * WAVES) void wfa_generic_kernel(const KParams P) {
     constexpr int G = 64 * WAVES;

@@ -1,11 +1,12 @@
 // wfa_host.hip -- the C-ABI of libwfahip.so (include/wfa_hip.h): context, workspaces, launch
-// configuration, retry ladder (bigger arena / byte-compare path) and result unpacking.
+// configuration, retry ladder (bigger arena / byte-compare path; the plan of a job: wfa_ladder.hpp) and result unpacking.
 //
 // There is NO CPU fallback here: every alignment is produced by the HIP kernels.  Without a GPU the
 // entry points return WFAHIP_ERR_NO_DEVICE.
 #include <map>
 #include "wfa_ctx.hpp"
 #include "wfa_bound.hpp"
+#include "wfa_ladder.hpp"
 // (the kernels' headers for their constants and device functions; the forward kernels are instantiated per penalty shape in
 // wfa_fwd_s*.hip, wfa_duo_kernel in wfa_duo.hip, the long-pair kernels in wfa_long.hip: this unit keeps the router, the
 // non-template kernels of the pipeline -- packing, backtrace, result assembly, the generator -- and the two first-generation
@@ -66,11 +67,6 @@ hipError_t wfa_launch_wide(int stage, int shape, int phase, int waves, const KPa
 
 namespace {
 
-// Share of device memory the arenas of the long-pair ladder may take: 0.6 -> four 43 GiB slots for the hard 100 kbp
-// semi-global pairs (a team of workgroups each).  Option arena_budget_pct; more slots were measured and lose to the
-// re-runs of the pairs that outgrow them (see the option).
-inline double ladder_budget(const wfahip_ctx *ctx) { return std::min(0.9, std::max(0.1, (double)ctx->opt_arena_budget_pct / 100.0)); }
-
 // wfa_team_kernel / wfa_teamc_kernel synchronise their workgroups with barriers they spin on: every workgroup of a launch
 // must be resident, which holds for ONE such launch on a GPU (the grid is sized by its CUs) and not for two -- two contexts
 // on one device (wfahip_create_multi with repeated ids, bench.py --share-gpus, two processes of one job) would each hold part
@@ -102,80 +98,22 @@ struct TeamLaunchLock {
     TeamLaunchLock &operator=(const TeamLaunchLock &) = delete;
 };
 
-struct LaunchCfg {
-    int      waves;        // 1, 4 or 16 waves per pair
-    int      mode;         // 0 = 2-bit LDS, 1 = bytes in global memory
-    uint32_t lds_seq_words;
-    size_t   lds_bytes;
-    uint64_t arena_words;  // per slot
-    uint32_t slots;
-};
-
-hipError_t launch_generic(const KParams &P, const LaunchCfg &c, hipStream_t st) { return wfa_launch_generic(P, c.waves, c.mode, c.slots, c.lds_bytes, st); }
+// what the plan of a ladder job reads (wfa_ladder.hpp)
+LadderEnv ladder_env(const wfahip_ctx *ctx, const KParams &P, bool debug_single) {
+    return {ctx->total_mem, ctx->num_cus, ctx->opt_arena_budget_pct, ctx->opt_arena_bytes_per_slot, ctx->opt_slots, ctx->opt_threads_per_pair,
+            ctx->opt_team_min_len, ctx->opt_team_wgs, ctx->opt_team_wave, ctx->opt_team_compact, ctx->opt_team_paged, ctx->opt_team_scout, ctx->opt_team_xcd,
+            debug_single, ctx->dbg_teamc, P.x, P.oe, P.e, P.g, P.global_alignment != 0u, P.adaptive != 0u};
+}
 
 struct Job {
     int                   mode  = 0;
-    int                   level = 0;      // arena size: make_cfg's ladder (x8, x8, x2 .., then one slot fewer per level)
+    int                   level = 0;      // arena size: ladder_slot_words' ladder (x8, x8, x2 .., then one slot fewer per level)
     bool                  all   = false;  // identity work list over all pairs
     std::vector<uint32_t> pairs;
     uint32_t              max_len = 0;  // length bound of these pairs (0 = the batch's)
     bool                  hint    = false;  // `level` came from an earlier call of the class (learn), not from a failed level below it
     bool                  scout   = false;  // long pairs, first launch: may run as the team kernel's scout pass (one workgroup per pair; wide pairs are handed on)
 };
-
-
-// Launch configuration for one job.
-int make_cfg(wfahip_ctx *ctx, uint32_t max_len, int mode, int level, uint64_t n_work, bool semi_global, LaunchCfg &c) {
-    int waves = max_len <= 4096 ? 1 : (max_len <= 65536 ? 4 : 16);
-    if (ctx->opt_threads_per_pair > 0) {
-        int64_t t = ctx->opt_threads_per_pair;
-        waves     = t <= 64 ? 1 : (t <= 256 ? 4 : 16);
-    }
-    c.waves         = waves;
-    c.mode          = mode;
-    c.lds_seq_words = (mode == 0) ? ((max_len + 15) / 16 + 1) : 0;
-    c.lds_bytes     = (2ull * c.lds_seq_words + GEN_LDS_EXTRA_WORDS) * 4ull;
-    if (c.lds_bytes > LDS_MAX_BYTES) return 1;  // caller must use mode 1
-
-    // semi-global rows are n+m-1 wide until wf-adaptive collapses the band (a few dozen scores): ~4x the words
-    uint64_t base_words = std::max<uint64_t>(64 * 1024, (semi_global ? 384ull : 96ull) * max_len);
-    if (ctx->opt_arena_bytes_per_slot > 0) base_words = std::max<uint64_t>(4096, ctx->opt_arena_bytes_per_slot / 4);
-    // the ladder: x8, x8, then x2 per level -- a slot of a long pair is tens of GB by then, and every doubling
-    // halves the number of pairs that can be in flight (level 3 of a 100 kbp semi-global pair: 21.6 GB)
-    // Once at most six slots fit the budget (tens of GB per pair), a level is "one slot fewer", and a slot takes
-    // its whole share of the budget: 5 x 46 GB, 4 x 57, 3 x 76, 2 x 115, 1 x 230 on a 288 GB device with the budget at
-    // 80 % (round 2, 60 %: 4 x 43, 3 x 57, 2 x 86, 1 x 172) -- every slot dropped is a team of workgroups less in flight.
-    const uint64_t budget_words = (uint64_t)((double)ctx->total_mem * ladder_budget(ctx)) / 4ull;
-    uint64_t       words        = base_words;
-    auto snap = [&](uint64_t w) {
-        const uint64_t fit = w ? budget_words / w : 0;
-        return (fit >= 1 && fit <= 6 && ctx->opt_arena_bytes_per_slot <= 0) ? budget_words / fit : w;  // (not an explicit size)
-    };
-    for (int i = 0; i < level; i++) {
-        const uint64_t fit = budget_words / words;
-        if (fit >= 2 && fit <= 6)
-            words = budget_words / (fit - 1);
-        else
-            words *= (i < 2 ? 8 : 2);
-    }
-    words         = snap(words) & ~7ull;  // directory entries are 32-byte aligned from the slot end
-    c.arena_words = words;
-
-    // resident workgroups per CU: 32 wave slots, LDS, and keep <= 8 blocks of >=256 threads
-    uint32_t per_cu = 32 / waves;
-    per_cu          = std::min<uint32_t>(per_cu, (uint32_t)(LDS_MAX_BYTES / std::max<size_t>(c.lds_bytes, 1)));
-    per_cu          = std::max<uint32_t>(per_cu, 1);
-    uint64_t slots  = (uint64_t)ctx->num_cus * per_cu;
-    if (ctx->opt_slots > 0) slots = (uint64_t)ctx->opt_slots;
-    // arena budget: at most ~60 % of device memory
-    uint64_t budget = budget_words * 4ull;
-    uint64_t fit    = budget / (words * 4ull);
-    if (fit == 0) return 2;  // even one slot does not fit
-    slots   = std::min<uint64_t>(slots, fit);
-    slots   = std::min<uint64_t>(slots, std::max<uint64_t>(n_work, 1));
-    c.slots = (uint32_t)slots;
-    return 0;
-}
 
 // What of a sub-wave forward kind depends on how the kernels were built (the rest is KIND_TRAITS, wfa_kinds.hpp).
 // KParams::compact_fmt of the arena the kind `base` writes (KindTraits::base)
@@ -1515,6 +1453,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         jobs.push_back(std::move(j));
     }
 
+    const LadderEnv lenv = ladder_env(ctx, P, debug_single);
     while (!jobs.empty()) {
         ctrl_fresh = false, ctrl_zeroed = false;
         Job job = std::move(jobs.front());
@@ -1523,123 +1462,14 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         if (n_work == 0) continue;
         const uint32_t max_len_all = max_len;
         const uint32_t max_len     = job.max_len ? job.max_len : max_len_all;  // (shadows the batch's bound for this job)
-        LaunchCfg cfg;
-        int       cr = make_cfg(ctx, max_len, job.mode, job.level, n_work, !P.global_alignment, cfg);
-        if (cr == 1) {  // sequences do not fit LDS: byte path for the whole job
-            job.mode = 1;
-            cr       = make_cfg(ctx, max_len, 1, job.level, n_work, !P.global_alignment, cfg);
-        }
-        // a learned start level whose slot does not fit (the class buckets lengths by powers of two, slots scale with the
-        // length): climb down to the largest level that does, never straight to "no memory"
-        while (cr == 2 && job.hint && job.level > 0) {
-            job.level -= 1;
-            cr = make_cfg(ctx, max_len, job.mode, job.level, n_work, !P.global_alignment, cfg);
-        }
-        // (the paged team kernel has levels beyond "one slot of this level fits": the pool is the whole budget there and a level
-        // halves the teams that share it -- the launch configuration is then that of the last level whose slot fitted)
-        const bool paged_capable = ctx->opt_team_paged != 0 && !debug_single && ctx->opt_team_wgs == 0 && ctx->opt_arena_bytes_per_slot <= 0 &&
-                                   ctx->opt_team_min_len > 0 && max_len >= (uint64_t)ctx->opt_team_min_len && P.e != 0u;
-        const bool no_slot_fits = cr == 2;  // (if the paged launch does not happen after all, the job ends as "no memory" as it used to)
-        for (int lv = job.level; cr == 2 && paged_capable && lv > 0;) cr = make_cfg(ctx, max_len, job.mode, --lv, n_work, !P.global_alignment, cfg);
-        if (debug_single) cfg.slots = 1;
-        // Wide wavefronts: a team of workgroups per pair (wfa_team_kernel) instead of one workgroup per pair.
-        uint32_t team_T = 0, team_n = 0, team_wave_rows = 0;
-        // It pays when one workgroup per pair cannot fill the GPU: few pairs, or arenas so large that only a few
-        // fit (cfg.slots is the number of pairs the generic kernel could run at once).
-        if (cr == 0 && (!debug_single || ctx->opt_team_wgs > 0) && ctx->opt_team_min_len > 0 && max_len >= (uint64_t)ctx->opt_team_min_len &&
-            (cfg.slots < (uint32_t)std::max(1, ctx->num_cus / 2) || ctx->opt_team_wgs > 0) && P.e != 0u &&
-            std::max(P.x, std::max(P.oe, P.e)) / P.g < (uint32_t)TEAM_RING) {
-            const uint32_t cus = (uint32_t)std::max(1, ctx->num_cus);
-            uint32_t t0 = (uint32_t)std::min<uint64_t>(cus, std::max<uint64_t>(2, (2ull * max_len + 8191) / 8192));
-            if (ctx->opt_team_wgs > 0) t0 = (uint32_t)std::min<int64_t>(cus, ctx->opt_team_wgs);
-            team_n = (uint32_t)std::min<uint64_t>(n_work, std::max<uint32_t>(1, cus / t0));
-            team_T = ctx->opt_team_wgs > 0 ? t0 : cus / team_n;
-            // one arena per team
-            const uint64_t budget = (uint64_t)((double)ctx->total_mem * ladder_budget(ctx));
-            while (team_n > 1 && (uint64_t)team_n * cfg.arena_words * 4ull > budget) team_n--;
-            if ((uint64_t)team_n * cfg.arena_words * 4ull > budget) cr = 2;
-            if (ctx->opt_team_wgs == 0) team_T = std::min<uint32_t>(cus / team_n, 2 * t0);  // ~2 cells per thread and stripe
-            cfg.slots         = team_n;
-            cfg.lds_seq_words = (cfg.lds_seq_words + 1u) & ~1u;
-            cfg.lds_bytes     = (2ull * cfg.lds_seq_words + 16 + TEAM_RING * (sizeof(DirEnt) / 4)) * 4ull;
-            if (cfg.lds_bytes > LDS_MAX_BYTES) team_T = 0;  // (cannot happen: make_cfg already bounded the sequences)
-            // wave mode: an LDS ring of the last rows (a power of two above the farthest source), if it fits
-            team_wave_rows = 0;
-            if (ctx->opt_team_wave) {
-                uint32_t rows = 2;
-                while (rows <= std::max(P.x, std::max(P.oe, P.e)) / P.g) rows *= 2;
-                const size_t ring_bytes = (size_t)rows * 3 * 64 * 4;
-                if (rows <= (uint32_t)TEAM_RING && cfg.lds_bytes + ring_bytes <= LDS_MAX_BYTES) {
-                    team_wave_rows = rows;
-                    cfg.lds_bytes += ring_bytes;
-                }
-            }
-        }
-        // wfa_teamc_kernel (round 5) instead of wfa_team_kernel when its LDS rings fit beside the sequences: rows of max(x, o+e)/g +
-        // 2 e/g x 4 098 words (the default penalties: six rows, 96 KB; a 100 kbp pair's packed sequences: 50 KB)
-        bool   team_c = false;
-        size_t lds_c  = 0;
-        if (team_T > 0 && ctx->opt_team_compact != 0 && (!debug_single || ctx->dbg_teamc) && max_len < (1u << 27)) {
-            const uint32_t rm = std::max(P.x, P.oe) / P.g, re = P.e / P.g;
-            lds_c = (2ull * cfg.lds_seq_words + TC_RED + TEAM_RING * (sizeof(DirEnt) / 4)) * 4ull + (size_t)team_wave_rows * 3 * 64 * 4 +
-                    (size_t)64 * TC_U * 4 + (size_t)(rm + 2 * re) * TC_ROWW * 4;
-            team_c = lds_c <= LDS_MAX_BYTES;
-        }
-        if (debug_single && ctx->dbg_teamc && !team_c) return WFAHIP_ERR_UNSUPPORTED;
-        // Paged arena of the team kernel: ONE pool for all teams, a pair takes pages as its rows grow.  The ladder level sizes the
-        // pool (as many slot sizes as there are teams) until that reaches the budget; from there a level halves the number of
-        // teams that share it -- down to one team with the whole pool.
-        bool     paged = false, scout_now = false;
-        uint64_t pool_words = 0, dir_words = 0;
-        uint32_t page_log = 0, n_pages = 0;
-        if (team_T > 0 && paged_capable) {
-            const uint32_t cus = (uint32_t)std::max(1, ctx->num_cus);
-            const uint32_t t0  = (uint32_t)std::min<uint64_t>(cus, std::max<uint64_t>(2, (2ull * max_len + 8191) / 8192));
-            uint32_t teams = (uint32_t)std::min<uint64_t>(n_work, std::max<uint32_t>(1, std::min<uint32_t>(8u, cus / t0)));
-            // scout pass (wfa_teamc_kernel only): a team is ONE workgroup, as many teams as CUs; it finishes the pairs whose band collapses and hands the
-            // others on.  Worth a launch of its own when the teams would otherwise take several pairs each.
-            scout_now = job.scout && team_c && ctx->opt_team_scout != 0 && P.adaptive && (ctx->opt_team_scout >= 2 || n_work > 2ull * teams);
-            const uint32_t teams_full = teams;
-            if (scout_now) teams = (uint32_t)std::min<uint64_t>(n_work, cus);
-            const uint64_t budget_w = (uint64_t)((double)ctx->total_mem * ladder_budget(ctx)) / 4ull;
-            // the first level at which `teams` slots no longer fit the budget, and how far this job is beyond it
-            int over = 0;
-            for (int lv = 0; lv <= job.level; lv++) {
-                LaunchCfg c2;
-                const int r2 = make_cfg(ctx, max_len, job.mode, lv, n_work, !P.global_alignment, c2);
-                if (r2 == 2 || (uint64_t)teams * c2.arena_words > budget_w) over++;
-            }
-            // (over = 1: the first level whose slots no longer fit -- all teams, the whole budget; every further level halves the teams)
-            const bool spent = over > 1 && (teams >> (over - 2)) <= 1u;  // the level before already ran ONE team with the whole pool
-            if (over > 1) teams = std::max<uint32_t>(1, teams >> (over - 1));
-            LaunchCfg c0;
-            const int r0 = make_cfg(ctx, max_len, job.mode, job.level, n_work, !P.global_alignment, c0);
-            // a directory entry per score index up to the worst score two sequences of this length can reach (every base a
-            // mismatch or part of one long gap), per team, behind the pages
-            const uint64_t worst_idx = ((uint64_t)(P.x + P.e) * max_len + 2ull * P.oe) / P.g + 64;
-            dir_words = ((uint64_t)DIR_WORDS * worst_idx + 4095) & ~4095ull;
-            const uint64_t dirs = (uint64_t)teams * dir_words;
-            uint64_t rows_words = (r0 == 2 || over > 0) ? (budget_w > dirs ? budget_w - dirs : 0) : std::min<uint64_t>(budget_w, (uint64_t)teams * c0.arena_words);
-            // pages of 1/64 of the rows' share, between "a row and then some" and 256 MB
-            uint64_t pw = 1ull << 20;
-            while (pw < 8ull * max_len) pw <<= 1;
-            while (pw < (64ull << 20) && pw * 64 < rows_words) pw <<= 1;
-            while ((1ull << page_log) < pw) page_log++;
-            n_pages    = (uint32_t)std::min<uint64_t>(rows_words >> page_log, 1u << 20);
-            pool_words = ((uint64_t)n_pages << page_log) + dirs;
-            if (spent) {
-                cr = 2;
-            } else if (n_pages >= teams) {
-                paged = true, team_n = teams, cr = 0;
-                if (ctx->opt_team_wgs == 0) team_T = scout_now ? 1u : std::min<uint32_t>(cus / team_n, 2 * t0);
-            } else if (scout_now && n_pages >= teams_full) {  // (too few pages for a team per CU: as many scouts as there are pages)
-                paged = true, team_n = std::min<uint32_t>(teams, n_pages), cr = 0;
-                team_T = 1u;
-            }
-            if (!paged) scout_now = false;
-        }
-        if (no_slot_fits && !paged) cr = 2;  // (the configuration of a lower level was only borrowed for the paged launch)
-        if (cr == 2 || job.level > max_level) {
+        // the plan (wfa_ladder.hpp): kernel, slots or paged pool, team geometry, LDS
+        const LadderPlan pl = plan_ladder_job(lenv, job.mode, job.level, job.hint, job.scout, n_work, max_len);
+        job.mode = pl.mode, job.level = pl.level;
+        if (debug_single && ctx->dbg_teamc && !pl.team_c) return WFAHIP_ERR_UNSUPPORTED;
+        LaunchCfg      cfg  = pl.cfg;
+        const bool     team = pl.kind != K_GENERIC, teamc = pl.kind == K_TEAMC, paged = pl.paged;
+        const uint32_t team_n = pl.team_n, team_T = pl.team_T, n_pages = pl.n_pages;
+        if (!pl.launch || job.level > max_level) {
             if (job.all) {
                 no_memory.resize(n_pairs);
                 std::iota(no_memory.begin(), no_memory.end(), 0u);
@@ -1653,11 +1483,9 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         DevBuf &jarena = (ctx->bt_pending || (packed_done && ctx->arena.bytes <= ctx->total_mem / 10)) ? ctx->arena2 : ctx->arena;
         // Long pairs climbing the ladder: take the whole arena budget once instead of freeing and re-allocating a
         // bigger buffer at every level (hipMalloc / hipFree of tens of GB cost more than the alignments).
-        if (team_T > 0 && job.level >= 2 && jarena.bytes < (size_t)((double)ctx->total_mem * ladder_budget(ctx)))
-            (void)ensure(ctx, jarena, (size_t)((double)ctx->total_mem * ladder_budget(ctx)));
+        if (team && job.level >= 2 && jarena.bytes < (size_t)lenv.budget_bytes()) (void)ensure(ctx, jarena, (size_t)lenv.budget_bytes());
         if (paged) {
-            cfg.slots = team_n, cfg.arena_words = pool_words;
-            rc = ensure(ctx, jarena, (size_t)pool_words * 4ull);
+            rc = ensure(ctx, jarena, (size_t)pl.pool_words * 4ull);
         } else {
             rc = ensure(ctx, jarena, (size_t)cfg.arena_words * 4ull * cfg.slots);
             if (rc == WFAHIP_ERR_OOM && cfg.slots > 1) {  // shrink once
@@ -1666,7 +1494,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             }
         }
         if (rc) return rc;
-        ctx->timing.arena_bytes = std::max<uint64_t>(ctx->timing.arena_bytes, paged ? pool_words * 4ull : (uint64_t)cfg.arena_words * 4ull * cfg.slots);
+        ctx->timing.arena_bytes = std::max<uint64_t>(ctx->timing.arena_bytes, paged ? pl.pool_words * 4ull : (uint64_t)cfg.arena_words * 4ull * cfg.slots);
 
         P.arena = static_cast<uint32_t *>(jarena.p), P.arena_words = cfg.arena_words;
         P.page_ctl = nullptr, P.page_words_log2 = 0, P.n_pages = 0, P.dir_region_words = 0;
@@ -1678,7 +1506,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
             for (uint32_t i = 0; i < n_pages; i++) init[4u + i] = n_pages - 1u - i;  // (page 0 on top of the stack)
             HIP_TRY(hipMemcpyAsync(ctx->page_ctl.p, init.data(), init.size() * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));  // (`init` is a pageable temporary)
-            P.page_ctl = static_cast<uint32_t *>(ctx->page_ctl.p), P.page_words_log2 = page_log, P.n_pages = n_pages, P.dir_region_words = dir_words;
+            P.page_ctl = static_cast<uint32_t *>(ctx->page_ctl.p), P.page_words_log2 = pl.page_log, P.n_pages = n_pages, P.dir_region_words = pl.dir_words;
         }
         P.lds_seq_words = cfg.lds_seq_words;
         P.n_work        = (uint32_t)n_work;
@@ -1687,10 +1515,10 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         // more than MaxDistDiff keeps a wide band for most of its scores (the first reduce cuts the final diagonal off; KERNELS.md
         // 4d) -- a scheduling hint only, results do not depend on the order.
         std::optional<TeamLaunchLock> team_lock;  // (released at the end of this job, behind the synchronisation that follows its launch)
-        if (team_T > 0) team_lock.emplace(ctx->device);
+        if (team) team_lock.emplace(ctx->device);
         std::vector<uint32_t> team_order;
         // (the hint reads the batch's length arrays: not for a handful of long pairs out of millions of short ones)
-        if (team_T > 0 && ctx->opt_team_order != 0 && P.adaptive && n_work > team_n && n_work <= (1u << 24) && (n_pairs <= (1u << 20) || n_pairs <= 64 * n_work)) {
+        if (team && ctx->opt_team_order != 0 && P.adaptive && n_work > team_n && n_work <= (1u << 24) && (n_pairs <= (1u << 20) || n_pairs <= 64 * n_work)) {
             if ((rc = host_lens())) return rc;
             team_order.resize(n_work);
             if (job.all) std::iota(team_order.begin(), team_order.end(), 0u);
@@ -1722,17 +1550,14 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
         // (tests: what an earlier launch left in the arena must never be read -- with the same batch run twice a stale
         // read returns the right value and hides itself)
         if (ctx->opt_arena_poison)
-            HIP_TRY(hipMemsetAsync(jarena.p, 0xA5, paged ? (size_t)pool_words * 4ull : (size_t)cfg.arena_words * 4ull * cfg.slots, st));
+            HIP_TRY(hipMemsetAsync(jarena.p, 0xA5, paged ? (size_t)pl.pool_words * 4ull : (size_t)cfg.arena_words * 4ull * cfg.slots, st));
         HIP_TRY(hipEventRecord(ctx->evA, st));
-        if (team_T > 0) {
-            const size_t ctl_words = team_c ? (size_t)TC_CTL_WORDS : (size_t)TEAM_CTL_WORDS;
+        if (team) {
+            const size_t ctl_words = pl.team_c ? (size_t)TC_CTL_WORDS : (size_t)TEAM_CTL_WORDS;
             if ((rc = ensure(ctx, ctx->team_ctl, (size_t)team_n * ctl_words * 4))) return rc;
             HIP_TRY(hipMemsetAsync(ctx->team_ctl.p, 0, (size_t)team_n * ctl_words * 4, st));
-            // teams of one XCD's CUs (team = blockIdx % 8) when at most eight teams run and the CUs divide by eight
-            const bool     xmap   = ctx->opt_team_xcd != 0 && ctx->opt_team_wgs == 0 && team_n <= 8 && ctx->num_cus % 8 == 0 && ctx->num_cus >= 16;
-            const uint32_t grid_t = xmap ? (uint32_t)ctx->num_cus : team_n * team_T;
-            if (xmap) team_T = (uint32_t)ctx->num_cus / 8u;
-            if (team_c && team_T <= (uint32_t)TC_MAX_T) {
+            const bool xmap = pl.xmap;
+            if (teamc) {
                 TcArgs X{};
                 const uint32_t rm = std::max(P.x, P.oe) / P.g, re = P.e / P.g;
                 X.xw         = (2u * max_len + 64u + 63u) & ~63u;
@@ -1741,116 +1566,39 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                 if (ctx->opt_arena_poison) HIP_TRY(hipMemsetAsync(ctx->xbuf.p, 0xA5, (size_t)team_n * X.xbuf_words * 4, st));
                 X.team_ctl = static_cast<uint32_t *>(ctx->team_ctl.p), X.xbuf = static_cast<uint32_t *>(ctx->xbuf.p);
                 X.T = team_T, X.n_teams = team_n, X.tpx = xmap ? 1u : 0u;
-                X.solo_max = (uint32_t)std::max<int64_t>(0, ctx->opt_team_solo_max_set ? ctx->opt_team_solo_max : std::min<int64_t>(ctx->opt_team_solo_max, 512)), X.wave_rows = team_wave_rows;
+                X.solo_max = (uint32_t)std::max<int64_t>(0, ctx->opt_team_solo_max_set ? ctx->opt_team_solo_max : std::min<int64_t>(ctx->opt_team_solo_max, 512)), X.wave_rows = pl.team_wave_rows;
                 X.strict = (uint32_t)(ctx->opt_team_strict != 0) | (xmap && ctx->opt_team_xcd >= 2 ? 4u : 0u);
                 X.slack  = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, ctx->opt_team_slack), 1 << 20);
                 X.fast   = ctx->opt_team_fast != 0 ? 1u : 0u;
-                X.scout  = scout_now ? 1u : 0u;
+                X.scout  = pl.scout_now ? 1u : 0u;
                 X.pipe   = ctx->opt_team_pipe != 0 ? 1u : 0u;
                 X.dbg    = debug_single ? d_ctrl + 4 : nullptr;
-                HIP_TRY(wfa_launch_teamc(P, X, job.mode, grid_t, lds_c, st));
+                HIP_TRY(wfa_launch_teamc(P, X, job.mode, pl.grid, pl.lds_c, st));
             } else {
-                team_c = false;
-                HIP_TRY(wfa_launch_team(P, job.mode, grid_t, cfg.lds_bytes, st, static_cast<uint32_t *>(ctx->team_ctl.p), team_T,
-                                        (uint32_t)std::max<int64_t>(0, ctx->opt_team_solo_max), team_wave_rows,
+                HIP_TRY(wfa_launch_team(P, job.mode, pl.grid, cfg.lds_bytes, st, static_cast<uint32_t *>(ctx->team_ctl.p), team_T,
+                                        (uint32_t)std::max<int64_t>(0, ctx->opt_team_solo_max), pl.team_wave_rows,
                                         (uint32_t)(ctx->opt_team_strict != 0) | (xmap ? 2u : 0u) | (xmap && ctx->opt_team_xcd >= 2 ? 4u : 0u) | (team_n << 16)));
             }
         } else {
-            // wave mode of the generic kernel: directory ring + ring of the last rows in LDS, if they fit
-            P.wave_rows = 0, P.wave_bt = 0;
-            if (ctx->opt_team_wave && std::max(P.x, std::max(P.oe, P.e)) / P.g < (uint32_t)WAVE_DIR_RING) {
-                const size_t dir_bytes = 16 + (size_t)WAVE_DIR_RING * sizeof(DirEnt);
-                if (cfg.lds_bytes + dir_bytes <= LDS_MAX_BYTES) {
-                    P.wave_bt = 1, cfg.lds_bytes += dir_bytes;
-                    uint32_t rows = 2;
-                    while (rows <= std::max(P.x, std::max(P.oe, P.e)) / P.g) rows *= 2;
-                    const size_t ring_bytes = (size_t)rows * 3 * 64 * 4;
-                    if (P.e != 0u && cfg.lds_bytes + ring_bytes <= LDS_MAX_BYTES) P.wave_rows = rows, cfg.lds_bytes += ring_bytes;
-                }
-            }
-            HIP_TRY(launch_generic(P, cfg, st));
+            P.wave_rows = pl.wave_rows, P.wave_bt = pl.wave_bt;  // wave mode of the generic kernel: directory ring + ring of the last rows in LDS
+            HIP_TRY(wfa_launch_generic(P, cfg.waves, cfg.mode, cfg.slots, cfg.lds_bytes, st));
         }
         HIP_TRY(hipEventRecord(ctx->evB, st));
         uint32_t              hctrl[CTRL_WORDS];
         std::vector<uint64_t> ent;  // {pair, status}, sorted by pair
         if ((rc = fetch_ctrl(hctrl, &ent))) return rc;
-        if (team_T > 0) {  // a team barrier that ran into its spin bound
-            const size_t TEAM_CTL_STRIDE = team_c ? (size_t)TC_CTL_WORDS : (size_t)TEAM_CTL_WORDS;
-            std::vector<uint32_t> tc((size_t)team_n * TEAM_CTL_STRIDE);
-            HIP_TRY(hipMemcpy(tc.data(), ctx->team_ctl.p, tc.size() * 4, hipMemcpyDeviceToHost));
-#ifdef WFA_TEAM_STAMPS
-            for (uint32_t t = 0; team_c && t < team_n; t++) {  // wfa_teamc_kernel's phases (its own numbering, wfa_teamc.hpp)
-                const unsigned long long *a = reinterpret_cast<const unsigned long long *>(&tc[(size_t)t * TEAM_CTL_STRIDE + 64]);
-                const double steps = (double)std::max<unsigned long long>(1, a[16] + a[17] + a[18]);
-                std::fprintf(stderr, "[teamc %u] steps: stripe(team) %llu xbuf %llu stripe(solo) %llu, ring loads %llu | us: head %.0f cells %.0f wave-red %.0f wait-wg %.0f rings+edges %.0f "
-                             "exchange1 %.0f band-ends %.0f exchange2 %.0f tail %.0f | wave mode %.0f backtrace %.0f | per wide step %.2f us\n", t, a[16], a[17], a[18], a[19],
-                             a[0] / 100.0, a[1] / 100.0, a[2] / 100.0, a[3] / 100.0, a[4] / 100.0, a[5] / 100.0, a[6] / 100.0, a[7] / 100.0, a[8] / 100.0, a[9] / 100.0, a[10] / 100.0,
-                             (a[0] + a[1] + a[2] + a[3] + a[4] + a[5] + a[6] + a[7] + a[8] + a[11] + a[12] + a[13] + a[14]) / 100.0 / steps);
-                {
-                    const unsigned long long *m = reinterpret_cast<const unsigned long long *>(&tc[(size_t)t * TEAM_CTL_STRIDE + TC_TRACE_OFF]);
-                    std::fprintf(stderr, "[teamc %u] the workgroup in the middle of the team, us: head %.0f cells %.0f wave-red %.0f wait-wg %.0f rings+edges %.0f exchange1 %.0f band-ends %.0f exchange2 %.0f tail %.0f\n",
-                                 t, m[0] / 100.0, m[1] / 100.0, m[2] / 100.0, m[3] / 100.0, m[4] / 100.0, m[5] / 100.0, m[6] / 100.0, m[7] / 100.0, m[8] / 100.0);
-                }
-                {
-                    const unsigned long long *x = reinterpret_cast<const unsigned long long *>(&tc[(size_t)t * TEAM_CTL_STRIDE + TC_TRACE_OFF + 64]) - 24;
-                    std::fprintf(stderr, "[teamc %u] exchange 1 in detail (inside the figure above), us: rows into the rings + slot stored %.0f, polled %.0f (%llu polls), reduced %.0f\n", t,
-                                 x[24] / 100.0, x[25] / 100.0, x[27], x[26] / 100.0);
-                }
-                {
-                    const unsigned long long *x = reinterpret_cast<const unsigned long long *>(&tc[(size_t)t * TEAM_CTL_STRIDE + TC_TRACE_OFF + 64]) - 24;
-                    std::fprintf(stderr, "[teamc %u] pipelined steps: committed %llu, left (row not eligible) %llu, deep %llu, complex %llu, not entered %llu | us of wave 0: head %.0f, row S + late cells %.0f, "
-                                 "wait for the cell waves %.0f, commit %.0f\n", t, a[20], a[21], a[22], a[23], x[28], a[0] / 100.0, x[29] / 100.0, x[30] / 100.0, x[31] / 100.0);
-                }
-                std::fprintf(stderr, "[teamc %u] head in detail, us: ring entries + ranges %.0f, room %.0f, first barrier %.0f, mode + scratch %.0f, second barrier %.0f\n", t, a[11] / 100.0,
-                             a[12] / 100.0, a[13] / 100.0, a[14] / 100.0, a[0] / 100.0);
-            }
-            for (uint32_t t = 0; !team_c && t < team_n; t++) {
-                const unsigned long long *a = reinterpret_cast<const unsigned long long *>(&tc[(size_t)t * TEAM_CTL_STRIDE + 64]);
-                std::fprintf(stderr, "[team %u] us: P1 %.0f  barriers %.0f  P2 %.0f  P3 %.0f  tail(team) %.0f  solo steps %.0f  end search %.0f  backtrace %.0f  wave mode %.0f | steps: wave %llu solo %llu team %llu\n", t,
-                             a[0] / 100.0, a[1] / 100.0, a[2] / 100.0, a[3] / 100.0, a[4] / 100.0, a[5] / 100.0, a[6] / 100.0, a[7] / 100.0,
-                             a[8] / 100.0, a[9], a[10], a[11]);
-                std::fprintf(stderr, "[team %u] band ends: nothing fails %llu, both within 64 cells %llu, within the 512-cell windows %llu, full passes %llu; mean trim low %.1f high %.1f\n",
-                             t, a[12], a[13], a[14], a[15], (double)a[16] / (double)std::max<unsigned long long>(1, a[13] + a[14]),
-                             (double)a[17] / (double)std::max<unsigned long long>(1, a[13] + a[14]));
-                std::fprintf(stderr, "[team %u] inside P1 (wave 0 of workgroup 0), us: cells %.0f  wave reductions %.0f  wait for the other waves %.0f  (rest = team atomics); stripe-mode ring loads %llu\n",
-                             t, a[18] / 100.0, a[19] / 100.0, a[20] / 100.0, a[21]);
-            }
-#endif
-            if (std::getenv("WFAHIP_DEBUG_TIMING")) {
-                uint32_t n_xl = 0;
-                for (uint32_t t = 0; t < team_n; t++) n_xl += tc[(size_t)t * TEAM_CTL_STRIDE + 11];
-                for (uint32_t t = 0; t < team_n; t++) std::fprintf(stderr, "[wfahip]   team %u: XCC ids seen, as a mask: 0x%x\n", t, tc[(size_t)t * TEAM_CTL_STRIDE + 3]);
-                std::fprintf(stderr, "[wfahip] team kernel: %u teams of %u workgroups, %u of them on one XCD each\n", team_n, team_T, n_xl);
-            }
-            for (uint32_t t = 0; t < team_n; t++)
-                if (tc[(size_t)t * TEAM_CTL_STRIDE + 1] != 0u) {
-                    if (team_c && std::getenv("WFAHIP_DEBUG_TIMING")) {  // (wfa_teamc_kernel: where every workgroup of the team was)
-                        const uint32_t *tr = &tc[(size_t)t * TEAM_CTL_STRIDE + TC_TRACE_OFF];
-                        for (uint32_t w = 0; w < team_T && w < (uint32_t)TC_MAX_T; w++) {
-                            std::fprintf(stderr, "[wfahip]   team %u workgroup %u: last mode change at score %u (%u -> %u), last park wake at %u (cmd %u), last wave exit at %u (flags %u), "
-                                         "pair left at %u (mode %u done %u overflow %u alone %u); ctl: cmd %u score %u flags %u\n", t, w, tr[2 * TC_MAX_T + w] >> 8, tr[2 * TC_MAX_T + w] & 15u,
-                                         (tr[2 * TC_MAX_T + w] >> 4) & 15u, tr[3 * TC_MAX_T + w] >> 8, tr[3 * TC_MAX_T + w] & 255u, tr[4 * TC_MAX_T + w] >> 8, tr[4 * TC_MAX_T + w] & 255u,
-                                         tr[5 * TC_MAX_T + w] >> 8, tr[5 * TC_MAX_T + w] & 15u, (tr[5 * TC_MAX_T + w] >> 4) & 1u, (tr[5 * TC_MAX_T + w] >> 5) & 1u, (tr[5 * TC_MAX_T + w] >> 6) & 1u,
-                                         tc[(size_t)t * TEAM_CTL_STRIDE + 4], tc[(size_t)t * TEAM_CTL_STRIDE + 5], tc[(size_t)t * TEAM_CTL_STRIDE + 10]);
-                            if ((tr[w] >> 24) == 0xABu)
-                                std::fprintf(stderr, "[wfahip]   team %u workgroup %u: left after an aborted barrier at wfa_teamc.hpp:%u, exchanges %u\n", t, w, tr[w] & 0xFFFFFFu, tr[TC_MAX_T + w]);
-                            else
-                                std::fprintf(stderr, "[wfahip]   team %u workgroup %u: score %u phase %u mode %u, exchanges %u, barrier count %u\n", t, w, tr[w] >> 8,
-                                             tr[w] & 15u, (tr[w] >> 4) & 15u, tr[TC_MAX_T + w], tc[(size_t)t * TEAM_CTL_STRIDE]);
-                        }
-                    }
-                    std::snprintf(ctx->last_error, sizeof ctx->last_error, "team kernel: barrier timeout in team %u", t);
-                    return WFAHIP_ERR_INTERNAL;
-                }
+        if (team) {  // a team barrier that ran into its spin bound
+            if (team_read_back(ctx, teamc, team_n, team_T, rc) >= 0) return WFAHIP_ERR_INTERNAL;
+            if (rc) return rc;
         }
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
         ctx->timing.kernel_ms += ms;
         if (first) {
             ctx->timing.main_kernel_ms = ms, ctx->timing.n_main_launches = 1, first = false;
-            if (team_T > 0) ctx->timing.main_kernel_kind = team_c ? K_TEAMC : K_TEAM;  // wfa_teamc_kernel / wfa_team_kernel (bench.py names the dominant kernel by this)
-            after_scout = scout_now;
-        } else if (after_scout && team_T > 0 && team_c) {  // (the scout pass and the teams behind it are one kernel: its launches add up)
+            if (team) ctx->timing.main_kernel_kind = pl.kind;  // wfa_teamc_kernel / wfa_team_kernel (bench.py names the dominant kernel by this)
+            after_scout = pl.scout_now;
+        } else if (after_scout && teamc) {  // (the scout pass and the teams behind it are one kernel: its launches add up)
             ctx->timing.main_kernel_ms += ms, ctx->timing.n_main_launches++;
         }
         ctx->timing.n_launches++;

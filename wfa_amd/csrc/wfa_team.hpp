@@ -47,12 +47,11 @@
 namespace wfa {
 
 constexpr int TEAM_THREADS   = 1024;
-constexpr int TEAM_RING      = WAVE_DIR_RING;  // directory entries every workgroup keeps in LDS (sources reach back < 64 scores)
+// (TEAM_RING, the directory entries every workgroup keeps in LDS, and TEAM_MAX_PAGES, the pages one pair can hold: wfa_ladder.hpp)
 constexpr int TEAM_CTL_WORDS = 128;  // per team, in global memory: [0] barrier count [1] abort [2] work index
                                      // [3] XCC ids of the team (mask) [4] command [5] score [6..7] arena top [8..9] end-cell key (u64) [10] end flags [11] team on one XCD [12..13] stored cells (u64)
                                      // [16 + 16*set ..] three reduction sets [64..] diagnostic stamps
 constexpr uint32_t TEAM_SPIN_LIMIT = 1u << 24;
-constexpr int      TEAM_MAX_PAGES  = 1024;  // pages one pair can hold (its list in page_ctl)
 #ifndef WFA_TEAM_U
 #define WFA_TEAM_U 2
 #endif

@@ -35,16 +35,16 @@
 
 namespace wfa {
 
-#ifndef WFA_TC_THREADS
-#define WFA_TC_THREADS 1024
-#endif
-constexpr int      TC_THREADS  = WFA_TC_THREADS;
-constexpr int      TC_STRIPE   = 4096;             // diagonals of a workgroup's stripe
-constexpr int      TC_U        = TC_STRIPE / TC_THREADS;
-constexpr int      TC_ROWW     = TC_STRIPE + 2;    // LDS words of a ring row: the stripe and a halo cell at either end
+// The workgroup's shape is what the host-side plan of a ladder job sizes this kernel's LDS and teams from: its one definition is in
+// wfa_ladder.hpp.
+//   TC_THREADS  threads of a workgroup (WFA_TC_THREADS: 1 024)
+//   TC_STRIPE   diagonals of a workgroup's stripe (4 096)
+//   TC_U        diagonals of a thread: TC_STRIPE / TC_THREADS
+//   TC_ROWW     LDS words of a ring row: the stripe and a halo cell at either end
+//   TC_RED      ints of the workgroup's scratch in LDS (red[])
+//   TC_MAX_T    workgroups per team (one lane of the polling wave each)
+// (the trace word of an aborted barrier carries its line in this file: TC_ABORT_RET)
 constexpr int      TC_SLOT_U64 = 16;               // a workgroup's exchange slot: (sequence number, value) words -- eight values to reduce, six edge cells
-constexpr int      TC_RED      = 80;               // ints of the workgroup's scratch in LDS (red[])
-constexpr int      TC_MAX_T    = 64;               // workgroups per team (one lane of the polling wave each)
 // per team in global memory: the control words of wfa_team_kernel (TEAM_CTL_WORDS: [0] barrier count [1] abort [2] work index
 // [3] XCC mask [4] command [5] score [6..7] arena top [8..9] - [10] end flags [11] on one XCD [12..13] stored cells
 // [112..114] page hand-over [115] KB [116] mode) followed by two sets of exchange slots

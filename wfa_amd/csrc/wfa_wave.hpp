@@ -14,7 +14,7 @@
 
 namespace wfa {
 
-constexpr int WAVE_DIR_RING = 64;  // directory entries in LDS (sources reach back < 64 scores)
+// (WAVE_DIR_RING, the directory entries in LDS: wfa_ladder.hpp)
 enum : uint32_t { WAVE_DONE = 1u, WAVE_OVERFLOW = 2u, WAVE_WIDE = 4u, WAVE_OVER_MAX = 8u };
 
 // Runs score steps from score s (whose row is known to be at most 64 diagonals wide) until the alignment ends
