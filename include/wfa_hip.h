@@ -217,6 +217,16 @@ int  wfahip_score_matrix(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t 
                          const uint64_t *q_off, const uint32_t *q_len, uint64_t n_q,
                          const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t,
                          uint32_t max_score, int32_t *status, uint32_t *score, uint64_t out_stride);
+/* ... with a flag per query ROW (q_rc: n_q flags, NULL = none set): every cell of a flagged row scores the reverse complement of its
+ * query, and equals what wfahip_score_batch returns for the bytes (revcomp(query i), target j); the other rows, and every call with
+ * q_rc = NULL, are wfahip_score_matrix, which is this entry without flags.  The complement of a byte: A <-> T, C <-> G, a <-> t,
+ * c <-> g, every other byte itself.  The table still holds each sequence once, forward (with the same arrays on both sides a flagged
+ * query is still a forward target): the kernels reverse-complement a flagged row's words as they stage them.  A flagged query with a
+ * byte outside ACGT takes the full path like any such cell, on bytes reverse-complemented on the host. */
+int  wfahip_score_matrix_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
+                            const uint64_t *q_off, const uint32_t *q_len, uint64_t n_q, const uint8_t *q_rc,
+                            const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t,
+                            uint32_t max_score, int32_t *status, uint32_t *score, uint64_t out_stride);
 
 /* Device-resident variant: every pointer is a device address on the context's GPU (caller-owned).
  * d_rec receives n_pairs records of WFAHIP_REC_WORDS u32; d_ops receives the CIGAR ops
@@ -330,6 +340,28 @@ int  wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const ui
 int  wfahip_score_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
                                const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                                uint64_t n_pairs, uint32_t max_score, wfahip_scores *out);
+
+/* The reverse strand of packed queries.  A read's orientation is unknown when a set is screened: the query and its reverse complement
+ * are both candidates.  In the packed code the complement of a base is code ^ 2, so the kernels make a query's reverse complement from
+ * the words they copy into LDS anyway -- nothing is reverse-complemented on the host, packed twice or uploaded twice.
+ * q_rc: n_pairs flags (NULL = none set).  q_rc[i] != 0: pair i scores the reverse complement of its query against its target; its
+ * status and score equal what wfahip_score_batch returns for the bytes (revcomp(query), target) under the same p and max_score.  A
+ * pair whose flag is clear is a pair of wfahip_score_batch_packed, which IS this entry with q_rc = NULL: everything said there holds,
+ * errors, empty and too long pairs (whose offsets are never looked at, whatever their flag) and timing included.  Offsets may
+ * repeat, so both strands of a pair are the pair listed twice, once flagged.
+ * Flagged global pairs of reads beyond 2 047 bases: wfa_rc_words_kernel writes their queries' reverse complements once, behind the
+ * uploaded words on the device, and wfa_score_long_kernel reads them there -- once per distinct {offset, length}, however many
+ * targets such a query is listed against: device memory of a quarter of a byte per base of those queries, nothing on the host or
+ * the bus.  Flagged pairs the kernels hand back are gathered with the same word function on the host. */
+int  wfahip_score_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                  const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                  const uint8_t *q_rc, uint64_t n_pairs, uint32_t max_score, wfahip_scores *out);
+/* Host only, no device: dst[0 .. wfahip_packed_words(len)) = the reverse complement of the len bases packed at src, as
+ * wfahip_pack_pairs would write it (the bits of the last word beyond the last base and the pad word zero) -- for the reverse-strand
+ * survivors a caller hands to wfahip_align_batch_packed.  Reads src[0 .. (len + 15) / 16) only: the pad word and the bits beyond
+ * the last base may hold anything.  src and dst must not overlap.  WFAHIP_ERR_BAD_ARG: dst null, src null with len > 0, len over
+ * WFAHIP_MAX_SEQ_LEN. */
+int  wfahip_revcomp_packed(const uint32_t *src, uint32_t len, uint32_t *dst);
 
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns

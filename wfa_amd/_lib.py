@@ -30,6 +30,7 @@ EXPORTS = [
     "wfahip_debug_score_long_list", "wfahip_score_batch_device", "wfahip_debug_score_device_list",
     "wfahip_align_batch_bounded", "wfahip_align_batch_bounded_device", "wfahip_score_batch_packed",
     "wfahip_wide_class_bounds", "wfahip_debug_wide_plan",
+    "wfahip_score_batch_packed_rc", "wfahip_score_matrix_rc", "wfahip_revcomp_packed",
 ]
 
 
@@ -92,6 +93,12 @@ def lib():
         L.wfahip_scores_free.argtypes = [C.POINTER(Scores)]
         L.wfahip_score_batch_packed.restype = C.c_int
         L.wfahip_score_batch_packed.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, C.POINTER(Scores)]
+        L.wfahip_score_batch_packed_rc.restype = C.c_int
+        L.wfahip_score_batch_packed_rc.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, vp, u64, u32, C.POINTER(Scores)]
+        L.wfahip_score_matrix_rc.restype = C.c_int
+        L.wfahip_score_matrix_rc.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, u64, vp, vp, vp, u64, u32, vp, vp, u64]
+        L.wfahip_revcomp_packed.restype = C.c_int
+        L.wfahip_revcomp_packed.argtypes = [vp, u32, vp]
         L.wfahip_score_matrix.restype = C.c_int
         L.wfahip_score_matrix.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, u64, vp, vp, u64, u32, vp, vp, u64]
         L.wfahip_debug_score_long_list.restype = C.c_int

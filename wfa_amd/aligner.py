@@ -315,6 +315,12 @@ class Aligner:
         """score_arrays on pre-packed 2-bit input (include/wfa_hip.h: wfahip_score_batch_packed): takes what pack_pairs() returns,
         and the same buffer then serves align_arrays_packed for the pairs worth aligning.  Offsets may repeat and come in any order;
         a quarter of the bytes cross PCIe.  (status, score) equal score_arrays' on the unpacked bytes."""
+        return self.score_arrays_packed_rc(packed, q_woff, q_len, t_woff, t_len, None, max_score=max_score)
+
+    def score_arrays_packed_rc(self, packed, q_woff, q_len, t_woff, t_len, q_rc, max_score: int = 0):
+        """score_arrays_packed with a flag per pair (include/wfa_hip.h: wfahip_score_batch_packed_rc): a pair whose flag is non-zero
+        scores the reverse complement of its query, made on the GPU from the same words -- (status, score) equal score_arrays' on the
+        bytes (revcomp(query), target).  Both strands of a pair: list it twice, once flagged.  q_rc=None: no flag set."""
         n = int(len(q_len))
         packed = np.ascontiguousarray(packed, dtype=np.uint32)
         q_woff = np.ascontiguousarray(q_woff, dtype=np.uint64)
@@ -325,12 +331,22 @@ class Aligner:
             raise ValueError("offset and length arrays differ in length")
         if not 0 <= int(max_score) < 1 << 32:
             raise ValueError("max_score must fit in 32 bits")
+        if q_rc is not None:
+            q_rc = np.ascontiguousarray(np.asarray(q_rc) != 0, dtype=np.uint8)
+            if q_rc.shape != (n,):
+                raise ValueError("q_rc must hold one flag per pair")
         res = L.Scores()
         prm = self._params()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = L.lib().wfahip_score_batch_packed(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff),
-                                               vp(t_len), n, int(max_score), C.byref(res))
-        L.check(rc, "wfahip_score_batch_packed" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        if q_rc is None:
+            name = "wfahip_score_batch_packed"
+            rc = L.lib().wfahip_score_batch_packed(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff),
+                                                   vp(t_len), n, int(max_score), C.byref(res))
+        else:
+            name = "wfahip_score_batch_packed_rc"
+            rc = L.lib().wfahip_score_batch_packed_rc(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff),
+                                                      vp(t_len), vp(q_rc), n, int(max_score), C.byref(res))
+        L.check(rc, name + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         try:
             if n == 0:
                 return np.zeros(0, np.int32), np.zeros(0, np.uint32)
@@ -426,11 +442,13 @@ class Aligner:
         return status, score
 
     # -- new: score matrix (include/wfa_hip.h: wfahip_score_matrix) ------------------------------------
-    def score_matrix_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, out=None):
+    def score_matrix_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, out=None, q_rc=None):
         """(status: np.int32[n_q, n_t], score: np.uint32[n_q, n_t]) of every query against every target: cell (i, j) is what
         score_arrays gives for the pair (query i, target j).  Pass the same arrays as queries and targets for all against all.
         out: an optional pair of preallocated C-contiguous arrays of shape (n_q, n_t) -- or row-strided views of that shape into
-        larger ones (one row stride for both); nothing outside the window is written.  Returns the arrays written."""
+        larger ones (one row stride for both); nothing outside the window is written.  Returns the arrays written.
+        q_rc: optional flags, one per QUERY (wfahip_score_matrix_rc): the cells of a flagged row score the reverse complement of that
+        query (A <-> T, C <-> G in either case, other bytes themselves); as a target the same sequence stays forward."""
         same = q_off is t_off and q_len is t_len  # (all against all: the entry packs and uploads each sequence once)
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
@@ -444,6 +462,10 @@ class Aligner:
             raise ValueError("offset and length arrays differ in length")
         if not 0 <= int(max_score) < 1 << 32:
             raise ValueError("max_score must fit in 32 bits")
+        if q_rc is not None:
+            q_rc = np.ascontiguousarray(np.asarray(q_rc) != 0, dtype=np.uint8)
+            if q_rc.shape != (n_q,):
+                raise ValueError("q_rc must hold one flag per query")
         if out is None:
             status, score = np.zeros((n_q, n_t), np.int32), np.zeros((n_q, n_t), np.uint32)
             stride = n_t
@@ -470,20 +492,41 @@ class Aligner:
             return status, score
         prm = self._params()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = L.lib().wfahip_score_matrix(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), n_q, vp(t_off), vp(t_len), n_t,
-                                         int(max_score), vp(status), vp(score), stride)
-        L.check(rc, "wfahip_score_matrix" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        if q_rc is None:
+            name = "wfahip_score_matrix"
+            rc = L.lib().wfahip_score_matrix(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), n_q, vp(t_off), vp(t_len), n_t,
+                                             int(max_score), vp(status), vp(score), stride)
+        else:
+            name = "wfahip_score_matrix_rc"
+            rc = L.lib().wfahip_score_matrix_rc(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), n_q, vp(q_rc), vp(t_off),
+                                                vp(t_len), n_t, int(max_score), vp(status), vp(score), stride)
+        L.check(rc, name + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return status, score
 
-    def ScoreMatrix(self, qs: Sequence[bytes], ts: Optional[Sequence[bytes]] = None, max_score: int = 0):
+    def ScoreMatrix(self, qs: Sequence[bytes], ts: Optional[Sequence[bytes]] = None, max_score: int = 0, strands: str = "+"):
         """(status, score) arrays of shape (len(qs), len(ts)): every query against every target (see score_matrix_arrays).
-        ts=None: all against all (qs against qs; each sequence is uploaded once)."""
-        seqs = list(qs) if ts is None else list(qs) + list(ts)
-        blob, off, ln, _, _ = make_blob(seqs, [b""] * len(seqs))
+        ts=None: all against all (qs against qs; each sequence is uploaded once).
+        strands="both": every query runs in both orientations -- each is listed twice, once flagged (score_matrix_arrays' q_rc), in ONE
+        call over ONE blob; the entry's table then holds a query's words twice, once per row (and with ts=None a third time as a target:
+        the row list is no longer the target list) -- and (status, score, strand) come back, the better strand per cell: strand 0 forward, 1 reverse complement.  An OK strand
+        beats one that is not; of two OK strands the lower score wins and a tie goes to the forward one; when neither is OK the status
+        is OVER_MAX if both are OVER_MAX and the forward strand's otherwise (strand 0)."""
+        if strands not in ("+", "both"):
+            raise ValueError('strands must be "+" or "both"')
+        both = strands == "both"
         n_q = len(qs)
-        if ts is None:
-            return self.score_matrix_arrays(blob, off, ln, off, ln, max_score=max_score)
-        return self.score_matrix_arrays(blob, off[:n_q], ln[:n_q], off[n_q:], ln[n_q:], max_score=max_score)
+        seqs = list(qs) + ([] if ts is None else list(ts))
+        blob, off, ln, _, _ = make_blob(seqs, [b""] * len(seqs))
+        if not both:
+            if ts is None:
+                return self.score_matrix_arrays(blob, off, ln, off, ln, max_score=max_score)
+            return self.score_matrix_arrays(blob, off[:n_q], ln[:n_q], off[n_q:], ln[n_q:], max_score=max_score)
+        # rows 0 .. n_q - 1 forward, rows n_q .. 2 n_q - 1 the same queries flagged (the blob holds a sequence once: offsets repeat)
+        q_off, q_len = np.concatenate([off[:n_q], off[:n_q]]), np.concatenate([ln[:n_q], ln[:n_q]])
+        t_off, t_len = (off[:n_q], ln[:n_q]) if ts is None else (off[n_q:], ln[n_q:])
+        q_rc = np.repeat(np.array([0, 1], np.uint8), n_q)
+        st, sc = self.score_matrix_arrays(blob, q_off, q_len, t_off, t_len, max_score=max_score, q_rc=q_rc)
+        return best_strand(st[:n_q], sc[:n_q], st[n_q:], sc[n_q:])
 
     # -- new: one pair at a time behind the batch ----------------------------------------------------
     def Submit(self, q: bytes, t: bytes) -> int:
@@ -657,6 +700,32 @@ def wide_class_bounds() -> List[int]:
     b = (C.c_uint32 * n)()
     L.lib().wfahip_wide_class_bounds(b, n)
     return [int(x) for x in b]
+
+
+def best_strand(st_f, sc_f, st_r, sc_r):
+    """The better of a forward and a reverse-strand result per element -> (status, score, strand): OK beats any other status, of two
+    OK results the lower score wins and a tie goes to the forward strand (0); when neither is OK the status is OVER_MAX if both are
+    OVER_MAX and the forward strand's otherwise, with strand 0."""
+    st_f, st_r = np.asarray(st_f, np.int32), np.asarray(st_r, np.int32)
+    sc_f, sc_r = np.asarray(sc_f, np.uint32), np.asarray(sc_r, np.uint32)
+    ok_f, ok_r = st_f == L.PAIR_OK, st_r == L.PAIR_OK
+    rev = ok_r & (~ok_f | (sc_r < sc_f))
+    status = np.where(rev, st_r, st_f)
+    score = np.where(rev, sc_r, sc_f)
+    return status.astype(np.int32), score.astype(np.uint32), rev.astype(np.uint8)
+
+
+def revcomp_packed(words, length: int):
+    """The reverse complement of one 2-bit packed sequence of `length` bases (include/wfa_hip.h: wfahip_revcomp_packed) as
+    pack_pairs() would have written it: (length + 15) // 16 + 1 words, tail bits and pad word zero.  Host only."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    length = int(length)
+    if length < 0 or words.size < (length + 15) // 16:
+        raise ValueError("words does not hold `length` bases")
+    dst = np.zeros((length + 15) // 16 + 1, dtype=np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    L.check(L.lib().wfahip_revcomp_packed(vp(words), length, vp(dst)), "wfahip_revcomp_packed")
+    return dst
 
 
 def pack_pairs(blob, q_off, q_len, t_off, t_len, n_threads: int = 8):

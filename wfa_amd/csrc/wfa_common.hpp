@@ -143,6 +143,11 @@ struct KParams {
     uint32_t        mx_cols;         // targets of the tile
     // ---- wfa_duo_kernel's queue claims (wfa_duo.hpp; appended last for the same reason)
     uint32_t        duo_claim;       // most fetches a wave claims with one atomic on queue_head, 1 .. 8; 1: one fetch per atomic and no first block
+    // ---- reverse-strand scoring (wfahip_score_batch_packed_rc, wfahip_score_matrix_rc; wfa_rc.hpp; appended last for the same reason)
+    const uint8_t  *q_rc;            // one flag per pair of the packed list / per query ROW of the matrix: != 0, the pair or the row's cells score the reverse
+                                     // complement of the query, made as its words are staged (mx_stage); nullptr: none set
+    uint64_t        mx_rc_shift;     // wfa_score_long_kernel<MATRIX>: the reverse-complemented words of a flagged long query (wfa_rc_words_kernel) lie this
+                                     // many words behind its table entry's
 };
 
 }  // namespace wfa

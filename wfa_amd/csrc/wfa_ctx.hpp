@@ -177,6 +177,8 @@ struct wfahip_ctx {
     DevBuf        score_out;                      // wfahip_score_batch: {status, score} per pair
     DevBuf        wide_ckpt;                      // wfa_wide_kernel: what its first launch hands its second, per pair of the chunk
     DevBuf        mx_seq, mx_words;               // wfahip_score_matrix: the call's sequence table (wfa_matrix.hpp)
+    DevBuf        in_rc, rc_jobs;                 // the _rc score entries: the call's flags (per pair / per query row), the jobs of wfa_rc_words_kernel (whose
+                                                  // words lie in mx_words, behind the uploaded ones)
     DevBuf        sd_ctl, sd_blk, sd_list, sd_redo;  // wfahip_score_batch_device (wfa_score_dev.hpp): control words, tile sums, the long pairs, the pairs of the full path
     uint64_t      sd_n_words = 0, sd_n_listed = 0;   // ... what its last call left in mx_words / mx_seq (wfahip_debug_score_device_list)
     DevBuf        mx_out;                         // ... {status, score} of two tiles (double-buffered: tile c downloads while tile c + 1 runs)
@@ -369,6 +371,7 @@ struct SDParams;
 hipError_t wfa_launch_score(int stage, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_wide_score(int stage, int shape, int phase, int waves, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
 hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, size_t lds_bytes, hipStream_t st);
+hipError_t wfa_launch_rc_words(const uint4 *jobs, uint32_t *words, uint32_t n_jobs, hipStream_t st);
 hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st);
 // ---- defined in wfa_wide_pk.hip: wfa_wide_kernel's full-alignment instances with the packed prologue, and the three launches of the
 // length-class plan (wfa_wide_plan.hpp)

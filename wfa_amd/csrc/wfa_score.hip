@@ -36,6 +36,12 @@ hipError_t wfa_launch_score_long(bool matrix, const KParams &P, uint32_t grid, s
     return hipGetLastError();
 }
 
+// wfa_rc_words_kernel (wfa_score_long.hpp): the reverse complements of `n_jobs` flagged long queries, from and into `words`
+hipError_t wfa_launch_rc_words(const uint4 *jobs, uint32_t *words, uint32_t n_jobs, hipStream_t st) {
+    hipLaunchKernelGGL(wfa_rc_words_kernel, dim3(n_jobs), dim3(256), 0, st, jobs, words, n_jobs);
+    return hipGetLastError();
+}
+
 // wfa_wide_kernel<.., SCORE = true> of penalty shape `shape` (wfa_fwd.hpp: fwd_shape()): phase 0 with `waves` waves per pair (1 or 4),
 // phase 1 with one -- as wfa_launch_wide (wfa_host.hip) launches the full-path instances
 template <int STAGE>

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(64) void wfa_score_kernel(const KParams P) {
     const uint32_t ml = nq > mt ? nq : mt;
     if (ml > SCORE_MAX_LEN || (ml + 15u) / 16u + 1u > SW) return emit(ST_REDO_LDS, 0u);
     if constexpr (STAGE == STAGE_PACKED) {
-        mx_stage<64>(P.mx_words, pk_entry(P.q_off, pair, nq), lq, lane);
+        mx_stage<64>(P.mx_words, pk_entry(P.q_off, pair, nq, 0u, P.q_rc), lq, lane);
         mx_stage<64>(P.mx_words, pk_entry(P.t_off, pair, mt), lt, lane);
     } else {
         bool bad = stage_pack<64>(P.blob, P.q_off[pair], nq, lq, lane);

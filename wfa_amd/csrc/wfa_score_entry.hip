@@ -1,11 +1,13 @@
 // wfa_score_entry.hip -- the score-only entries of the C-ABI (include/wfa_hip.h): wfahip_score_batch (host arrays),
 // wfahip_score_batch_packed (host arrays over caller-packed 2-bit words), wfahip_score_batch_device (device-resident input) and
-// wfahip_score_matrix (every query against every target).  The forward pass
+// wfahip_score_matrix (every query against every target); wfahip_score_batch_packed_rc and wfahip_score_matrix_rc, which are the packed and
+// the matrix entry with a reverse-complement flag per pair / per query row (wfa_rc.hpp), and wfahip_revcomp_packed.  The forward pass
 // without arena or backtrace: wfa_score_kernel for global pairs, wfa_score_long_kernel for global reads beyond its length, the score
 // instances of wfa_wide_kernel for semi-global ones (all launched by wfa_score.hip); whatever they hand back goes through the
 // full path of wfahip_align_batch (wfa_entry.hip).  One router per entry over what they share: the route a call's penalties
 // take, the launch geometry of a chunk or tile, its launch, and the full-path fallback.  No kernel is defined here.
 #define WFA_NO_AUX_KERNELS 1  // (device functions and constants of the kernels' headers only)
+#include <map>
 #include "wfa_ctx.hpp"
 #include "wfa_hostpack.hpp"
 #include "wfa_fwd.hpp"
@@ -203,8 +205,9 @@ int score_fallback(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_b
 // kernel's checkpoints take WIDE_CKPT_WORDS words per pair of a chunk) pairs, the wide kernel's two phases under wf-adaptive, and
 // the n_listed pairs of ctx->mx_seq / mx_words on wfa_score_long_kernel behind the short launch.  Records ctx->ev0 before the
 // first launch and ctx->ev1 behind the last; synchronises nothing.  n_long: the long pairs of the batch (listed or not).
+// n_rc_jobs: the listed pairs whose query is flagged -- wfa_rc_words_kernel writes the words their entries name (ctx->rc_jobs) first.
 static int score_launch(wfahip_ctx *ctx, int stage, KParams &P, const ScoreRoute &R, uint64_t n_pairs, uint32_t max_len, bool skip_short, uint64_t n_listed,
-                        uint64_t n_long, hipStream_t st, wfahip_timing &tm, bool &long_main) {
+                        uint64_t n_long, hipStream_t st, wfahip_timing &tm, bool &long_main, uint64_t n_rc_jobs = 0) {
     int            rc;
     const uint32_t L     = std::min<uint32_t>(max_len, R.glob ? SCORE_MAX_LEN : WIDE_MAX_LEN);  // (longer pairs come back ST_REDO_LDS)
     const uint64_t chunk = R.glob ? (1ull << 24) : (1ull << 18);
@@ -213,6 +216,10 @@ static int score_launch(wfahip_ctx *ctx, int stage, KParams &P, const ScoreRoute
     if (!ctx->ev0) HIP_TRY(hipEventCreate(&ctx->ev0));
     if (!ctx->ev1) HIP_TRY(hipEventCreate(&ctx->ev1));
     HIP_TRY(hipEventRecord(ctx->ev0, st));
+    if (n_rc_jobs) {
+        HIP_TRY(wfa_launch_rc_words(static_cast<const uint4 *>(ctx->rc_jobs.p), static_cast<uint32_t *>(ctx->mx_words.p), (uint32_t)n_rc_jobs, st));
+        tm.n_launches++;
+    }
     for (uint64_t c0 = 0; c0 < n_pairs && !skip_short; c0 += chunk) {
         P.chunk_first = (uint32_t)c0, P.chunk_n = (uint32_t)std::min<uint64_t>(chunk, n_pairs - c0);
         if ((rc = score_launch_short(ctx, stage, R, G, P, st, tm))) return rc;
@@ -347,6 +354,10 @@ extern "C" int wfahip_score_batch(wfahip_ctx *ctx, const wfahip_params *p, const
 // pair's words into LDS from there (q_woff / t_woff are their P.q_off / P.t_off), and wfa_score_long_kernel's table points INTO the
 // same words -- eight words per long pair built here, no sequence packed or uploaded a second time.  What the kernels hand back is
 // gathered, those pairs' words only, into a buffer of this entry's own and aligned through the packed full path.
+// wfahip_score_batch_packed_rc is the same entry with a flag per pair: a flagged pair scores the REVERSE COMPLEMENT of its query.  The
+// kernels make its words as they stage them (mx_stage, wfa_rc.hpp) -- nothing is stored or sent twice; the flagged long queries are
+// written once behind the uploaded words (wfa_rc_words_kernel) and the long table names them there; the gather below makes the words of the
+// flagged pairs the kernels hand back with the same rc_word.
 namespace {
 // words of one sequence as wfahip_pack_pairs writes them: the bits of the last word beyond the last base and the pad word zero
 void copy_packed_seq(const uint32_t *src, uint32_t len, uint32_t *dst) {
@@ -355,11 +366,35 @@ void copy_packed_seq(const uint32_t *src, uint32_t len, uint32_t *dst) {
     if (tail) dst[nw - 1] &= (1u << (2u * tail)) - 1u;
     dst[nw] = 0u;
 }
+// ... and those of its reverse complement
+void revcomp_packed_seq(const uint32_t *src, uint32_t len, uint32_t *dst) {
+    const uint32_t nw = (len + 15u) >> 4;
+    for (uint32_t j = 0; j < nw; j++) dst[j] = rc_word(src, len, j);
+    dst[nw] = 0u;
+}
+// the flags of a call as the kernels take them: nullptr when none of the n is set (they then run as without flags)
+const uint8_t *any_flag(const uint8_t *f, uint64_t n) {
+    if (f)
+        for (uint64_t i = 0; i < n; i++)
+            if (f[i]) return f;
+    return nullptr;
+}
 }  // namespace
 
+// Host only: the reverse complement of one packed sequence, as wfahip_pack_pairs would have written it (include/wfa_hip.h)
+extern "C" int wfahip_revcomp_packed(const uint32_t *src, uint32_t len, uint32_t *dst) {
+    if (!dst || (!src && len) || len > WFAHIP_MAX_SEQ_LEN) return WFAHIP_ERR_BAD_ARG;
+    if (len == 0) {
+        for (uint64_t j = 0; j < wfahip_packed_words(0); j++) dst[j] = 0u;
+        return WFAHIP_OK;
+    }
+    revcomp_packed_seq(src, len, dst);
+    return WFAHIP_OK;
+}
+
 static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
-                                   const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, uint32_t max_score,
-                                   wfahip_scores *out) {
+                                   const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc, uint64_t n_pairs,
+                                   uint32_t max_score, wfahip_scores *out) {
     // (every check before any device work, and none dereferences ctx)
     if (!ctx || !p || !out) return WFAHIP_ERR_BAD_ARG;
     std::memset(out, 0, sizeof *out);
@@ -382,6 +417,7 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
     if (n_pairs == 0) return WFAHIP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const auto t_start = std::chrono::steady_clock::now();
+    q_rc = any_flag(q_rc, n_pairs);
     std::vector<uint2> res(n_pairs);
     wfahip_timing      tm{};
     KParams            P{};
@@ -391,12 +427,29 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
         // wfa_score_long_kernel where they lie in the caller's words
         const bool         use_long = R.glob && n_pairs <= UINT32_MAX && n_long != 0 && (int64_t)n_long >= ctx->opt_score_long_min;
         std::vector<uint4> ltab;  // two entries per long pair
+        // a flagged long pair's query entry names words behind the uploaded ones (from word n_words + 4 on, each query with its pad word),
+        // which wfa_rc_words_kernel writes: a job per distinct {the caller's words, length} among such pairs, {those words} -- one query
+        // flagged against fifty long targets is written once.  (Keyed by offset AND length: the reverse complement of a prefix is no prefix
+        // of the reverse complement.)  Device memory only: a quarter of a byte per base of those queries
+        std::vector<uint4>                                    jobs;
+        std::map<std::pair<uint64_t, uint32_t>, uint64_t>     rc_at;
+        uint64_t                                              rc_end = n_words + 4;
         if (use_long) {
             ltab.reserve(2 * n_long);
             for (uint64_t i = 0; i < n_pairs; i++) {
                 if (!(q_len[i] && t_len[i] && q_len[i] <= WFAHIP_MAX_SEQ_LEN && t_len[i] <= WFAHIP_MAX_SEQ_LEN)) continue;
                 if (std::max(q_len[i], t_len[i]) <= SCORE_MAX_LEN) continue;
-                ltab.push_back(make_uint4((uint32_t)q_woff[i], (uint32_t)(q_woff[i] >> 32), q_len[i], (uint32_t)i));
+                uint64_t qw = q_woff[i];
+                if (q_rc && q_rc[i]) {
+                    const auto at = rc_at.emplace(std::make_pair(qw, q_len[i]), rc_end);
+                    if (at.second) {
+                        jobs.push_back(make_uint4((uint32_t)qw, (uint32_t)(qw >> 32), q_len[i], 0u));
+                        jobs.push_back(make_uint4((uint32_t)rc_end, (uint32_t)(rc_end >> 32), 0u, 0u));
+                        rc_end += wfahip_packed_words(q_len[i]);
+                    }
+                    qw = at.first->second;
+                }
+                ltab.push_back(make_uint4((uint32_t)qw, (uint32_t)(qw >> 32), q_len[i], (uint32_t)i));
                 ltab.push_back(make_uint4((uint32_t)t_woff[i], (uint32_t)(t_woff[i] >> 32), t_len[i], 0u));
             }
         }
@@ -404,7 +457,7 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
         const bool     skip_short = use_long && n_long == n_pairs;  // every pair is long: nothing for wfa_score_kernel
         hipStream_t    st         = ctx->stream;
         if ((rc = ensure(ctx, ctx->score_out, n_pairs * 8))) return rc;
-        if ((rc = ensure(ctx, ctx->mx_words, (size_t)(n_words + 4) * 4))) return rc;  // (+16 bytes, as in_packed has)
+        if ((rc = ensure(ctx, ctx->mx_words, (size_t)(rc_end + 4) * 4))) return rc;  // (+16 bytes, as in_packed has)
         ctx->sd_n_words = ctx->sd_n_listed = 0;  // (what wfahip_score_batch_device left there is gone)
         if (n_words) HIP_TRY(hipMemcpyAsync(ctx->mx_words.p, packed, (size_t)n_words * 4, hipMemcpyHostToDevice, st));
         if (!skip_short) {
@@ -416,17 +469,26 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
             HIP_TRY(hipMemcpyAsync(ctx->in_toff.p, t_woff, n_pairs * 8, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+            if (q_rc) {
+                if ((rc = ensure(ctx, ctx->in_rc, n_pairs))) return rc;
+                HIP_TRY(hipMemcpyAsync(ctx->in_rc.p, q_rc, n_pairs, hipMemcpyHostToDevice, st));
+                P.q_rc = static_cast<const uint8_t *>(ctx->in_rc.p);
+            }
         }
         if (n_listed) {
             if ((rc = ensure(ctx, ctx->mx_seq, ltab.size() * 16))) return rc;
             HIP_TRY(hipMemcpyAsync(ctx->mx_seq.p, ltab.data(), ltab.size() * 16, hipMemcpyHostToDevice, st));
+        }
+        if (!jobs.empty()) {
+            if ((rc = ensure(ctx, ctx->rc_jobs, jobs.size() * 16))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->rc_jobs.p, jobs.data(), jobs.size() * 16, hipMemcpyHostToDevice, st));
         }
         P.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
         P.q_off = static_cast<const uint64_t *>(ctx->in_qoff.p), P.t_off = static_cast<const uint64_t *>(ctx->in_toff.p);  // (in words)
         P.q_len = static_cast<const uint32_t *>(ctx->in_qlen.p), P.t_len = static_cast<const uint32_t *>(ctx->in_tlen.p);
         P.score_out = static_cast<uint2 *>(ctx->score_out.p), P.max_score = max_score;
         bool long_main = false;
-        if ((rc = score_launch(ctx, STAGE_PACKED, P, R, n_pairs, max_len, skip_short, n_listed, n_long, st, tm, long_main))) return rc;
+        if ((rc = score_launch(ctx, STAGE_PACKED, P, R, n_pairs, max_len, skip_short, n_listed, n_long, st, tm, long_main, jobs.size() / 2))) return rc;
         HIP_TRY(hipMemcpyAsync(res.data(), ctx->score_out.p, n_pairs * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         float ms = 0;
@@ -461,7 +523,7 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
         parallel_ranges(0, n, (unsigned)std::min<uint64_t>(host_pack_threads(16, true), pos / 65536 + 1), [&](uint64_t a, uint64_t b) {
             for (uint64_t k = a; k < b; k++) {
                 if (!valid[k]) continue;  // (the vector's zeros are its two pad words)
-                copy_packed_seq(packed + q_woff[fb[k]], ql[k], words.data() + qo[k]);
+                (q_rc && q_rc[fb[k]] ? revcomp_packed_seq : copy_packed_seq)(packed + q_woff[fb[k]], ql[k], words.data() + qo[k]);
                 copy_packed_seq(packed + t_woff[fb[k]], tl[k], words.data() + to[k]);
             }
         });
@@ -488,7 +550,12 @@ static int score_batch_packed_impl(wfahip_ctx *ctx, const wfahip_params *p, cons
 extern "C" int wfahip_score_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
                                          const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                                          uint64_t n_pairs, uint32_t max_score, wfahip_scores *out) {
-    WFAHIP_GUARD(score_batch_packed_impl(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, n_pairs, max_score, out))
+    WFAHIP_GUARD(score_batch_packed_impl(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, nullptr, n_pairs, max_score, out))
+}
+extern "C" int wfahip_score_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                            const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                            const uint8_t *q_rc, uint64_t n_pairs, uint32_t max_score, wfahip_scores *out) {
+    WFAHIP_GUARD(score_batch_packed_impl(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, n_pairs, max_score, out))
 }
 
 // ---- score only on device-resident input (wfahip_score_batch_device): score_batch_impl with everything it does on the host done by
@@ -672,9 +739,31 @@ extern "C" int wfahip_debug_score_device_list(wfahip_ctx *ctx, uint32_t **words,
 // take the cells of a rectangular tile, a workgroup per cell, and stage the cell's two sequences from the table.  Tiles are
 // double-buffered: tile c downloads on stream2 while tile c + 1 runs, and the host scatters it into the caller's arrays.  What the
 // kernels hand back goes through the full path of wfahip_align_batch, in batches of MX_FB_PAIRS cells.
+// wfahip_score_matrix_rc is the same entry with a flag per query ROW: every cell of a flagged row scores the reverse complement of its query.
+// The table still holds every sequence once, forward (with the same arrays on both sides a sequence is a target too): the kernels read the
+// row's flag with the cell (mx_cell) and reverse-complement the query's words as they stage them; flagged long rows are written once
+// behind the table's words, P.mx_rc_shift words behind their forward form (wfa_rc_words_kernel); the cells the kernels hand back take the
+// full path on bytes reverse-complemented here (rc_byte).
+namespace {
+// the complement of a byte: A <-> T, C <-> G in either case, every other byte itself
+inline uint8_t rc_byte(uint8_t c) {
+    switch (c) {
+    case 'A': return 'T';
+    case 'T': return 'A';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'a': return 't';
+    case 't': return 'a';
+    case 'c': return 'g';
+    case 'g': return 'c';
+    }
+    return c;
+}
+}  // namespace
+
 static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
-                             const uint32_t *q_len, uint64_t n_q, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t, uint32_t max_score,
-                             int32_t *status, uint32_t *score, uint64_t out_stride) {
+                             const uint32_t *q_len, uint64_t n_q, const uint8_t *q_rc, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t,
+                             uint32_t max_score, int32_t *status, uint32_t *score, uint64_t out_stride) {
     // (every check before any device work, and none dereferences ctx)
     if (!ctx || !p || !status || !score) return WFAHIP_ERR_BAD_ARG;
     if ((n_q && (!q_off || !q_len)) || (n_t && (!t_off || !t_len)) || (!seq_blob && blob_bytes)) return WFAHIP_ERR_BAD_ARG;
@@ -693,6 +782,7 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
 
     HIP_TRY(hipSetDevice(ctx->device));
     const auto    t_start = std::chrono::steady_clock::now();
+    q_rc = any_flag(q_rc, n_q);
     wfahip_timing tm{};
     const auto    put = [&](uint64_t i, uint64_t j, uint32_t st, uint32_t sc) {
         status[i * stride + j] = (int32_t)st, score[i * stride + j] = st == ST_OK ? sc : 0u;
@@ -758,10 +848,42 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
         std::vector<uint64_t> n_lng(use_long ? n_seq + 1 : 0, 0);
         for (uint64_t s = 0; s < n_seq && use_long; s++) n_lng[s + 1] = n_lng[s] + ((seq[s].w & MXF_LONG) ? 1u : 0u);
         const bool long_main = use_long && n_long_cells > n_q * n_t - n_long_cells;
+        // the flagged rows with a cell for the long kernel -- a long row, or a row of any length when a column is long: the kernel takes every
+        // cell with a long side -- : their reverse complements go behind the table's words, each as far behind its forward form as the first
+        // of them (words [lo, hi) of the table -> [words.size(), ..)); a job of wfa_rc_words_kernel per row.  (Rows with a byte outside
+        // ACGT have no such cell.)  The span costs at most the table's words again on the device, nothing on the host or the bus
+        std::vector<uint4> jobs;
+        uint64_t           rc_lo = UINT64_MAX, rc_hi = 0;
+        bool               long_col = false;
+        for (uint64_t s = same ? 0 : n_q; s < n_seq && use_long && q_rc; s++) long_col |= seq[s].w == MXF_LONG;
+        const auto wants_rc = [&](uint64_t s) { return q_rc[s] && (seq[s].w == MXF_LONG || (seq[s].w == 0u && long_col)); };
+        for (uint64_t s = 0; s < n_q && use_long && q_rc; s++) {
+            if (!wants_rc(s)) continue;
+            const uint64_t w = (uint64_t)seq[s].y << 32 | seq[s].x;
+            rc_lo = std::min(rc_lo, w), rc_hi = std::max(rc_hi, w + wfahip_packed_words(seq[s].z));
+        }
+        if (rc_hi) {
+            P.mx_rc_shift = words.size() - rc_lo;
+            for (uint64_t s = 0; s < n_q; s++) {
+                if (!wants_rc(s)) continue;
+                const uint64_t d = ((uint64_t)seq[s].y << 32 | seq[s].x) + P.mx_rc_shift;
+                jobs.push_back(make_uint4(seq[s].x, seq[s].y, seq[s].z, 0u));
+                jobs.push_back(make_uint4((uint32_t)d, (uint32_t)(d >> 32), 0u, 0u));
+            }
+        }
         if ((rc = ensure(ctx, ctx->mx_seq, n_seq * 16))) return rc;
-        if ((rc = ensure(ctx, ctx->mx_words, words.size() * 4))) return rc;
+        if ((rc = ensure(ctx, ctx->mx_words, (words.size() + (rc_hi ? rc_hi - rc_lo + 4 : 0)) * 4))) return rc;
         HIP_TRY(hipMemcpyAsync(ctx->mx_seq.p, seq.data(), n_seq * 16, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ctx->mx_words.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+        if (q_rc) {
+            if ((rc = ensure(ctx, ctx->in_rc, n_q))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->in_rc.p, q_rc, n_q, hipMemcpyHostToDevice, st));
+            P.q_rc = static_cast<const uint8_t *>(ctx->in_rc.p);
+        }
+        if (!jobs.empty()) {
+            if ((rc = ensure(ctx, ctx->rc_jobs, jobs.size() * 16))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->rc_jobs.p, jobs.data(), jobs.size() * 16, hipMemcpyHostToDevice, st));
+        }
         P.mx_seq = static_cast<const uint4 *>(ctx->mx_seq.p), P.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
         P.mx_tbase = same ? 0u : n_q;
         P.max_score = max_score;
@@ -791,6 +913,10 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
                 }
         };
         HIP_TRY(hipEventRecord(ctx->ev0, st));
+        if (!jobs.empty()) {
+            HIP_TRY(wfa_launch_rc_words(static_cast<const uint4 *>(ctx->rc_jobs.p), static_cast<uint32_t *>(ctx->mx_words.p), (uint32_t)(jobs.size() / 2), st));
+            tm.n_launches++;
+        }
         Tile     prev{};
         uint64_t c = 0;
         for (uint64_t r0 = 0; r0 < n_q; r0 += Rq)
@@ -838,6 +964,25 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
     // ---- the full path: what the kernels handed back -- or every cell, for a penalty shape without an instance -- a batch of at most
     // MX_FB_PAIRS cells at a time
     const uint64_t n_fb = R.on_kernel ? (uint64_t)fb.size() : n_q * n_t;
+    // (the flagged rows among them: the full path reads their queries from a copy of the blob with their reverse complements appended --
+    // align_batch_entry takes ONE blob, so while such cells are aligned the host holds the blob a second time, plus those rows)
+    std::vector<uint8_t>  rblob;
+    std::vector<uint64_t> rq_off;
+    if (q_rc && n_fb) {
+        std::vector<uint8_t> need(n_q, 0);
+        for (uint64_t k = 0; k < n_fb; k++) {
+            const uint64_t i = (R.on_kernel ? fb[k] : k) / n_t;
+            need[i] = q_rc[i] && q_len[i] && q_len[i] <= WFAHIP_MAX_SEQ_LEN;
+        }
+        rblob.assign(seq_blob, seq_blob + blob_bytes), rq_off.assign(q_off, q_off + n_q);
+        for (uint64_t i = 0; i < n_q; i++) {
+            if (!need[i]) continue;
+            rq_off[i] = rblob.size();
+            const uint8_t *const src = seq_blob + q_off[i];
+            for (uint32_t b = q_len[i]; b-- > 0;) rblob.push_back(rc_byte(src[b]));
+        }
+        seq_blob = rblob.data(), blob_bytes = rblob.size(), q_off = rq_off.data();
+    }
     for (uint64_t a = 0; a < n_fb; a += MX_FB_PAIRS) {
         const auto cell = [&](uint64_t k) {
             const uint64_t x = R.on_kernel ? fb[a + k] : a + k;
@@ -859,5 +1004,10 @@ static int score_matrix_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint
 extern "C" int wfahip_score_matrix(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
                                    const uint32_t *q_len, uint64_t n_q, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t, uint32_t max_score,
                                    int32_t *status, uint32_t *score, uint64_t out_stride) {
-    WFAHIP_GUARD(score_matrix_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, n_q, t_off, t_len, n_t, max_score, status, score, out_stride))
+    WFAHIP_GUARD(score_matrix_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, n_q, nullptr, t_off, t_len, n_t, max_score, status, score, out_stride))
+}
+extern "C" int wfahip_score_matrix_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                                      const uint32_t *q_len, uint64_t n_q, const uint8_t *q_rc, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_t,
+                                      uint32_t max_score, int32_t *status, uint32_t *score, uint64_t out_stride) {
+    WFAHIP_GUARD(score_matrix_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, n_q, q_rc, t_off, t_len, n_t, max_score, status, score, out_stride))
 }

@@ -14,6 +14,8 @@
 // / the target of pair i ({word offset lo, hi, length, -} into P.mx_words; the query's .w is the pair's slot of P.score_out).
 // MATRIX: the pair is a cell of a tile (wfa_matrix.hpp) and the kernel takes the cells with a sequence flagged MXF_LONG only --
 // the others belong to wfa_score_kernel<MATRIX>, launched over the same tile.
+// A query flagged for its reverse complement (wfahip_score_batch_packed_rc, wfahip_score_matrix_rc) is read from words wfa_rc_words_kernel
+// wrote before this launch: the list's entry names them, a matrix row's lie P.mx_rc_shift words behind the table entry's.
 #pragma once
 #include "wfa_score.hpp"
 
@@ -28,6 +30,21 @@ __host__ __device__ inline uint32_t score_long_lds_words(uint32_t win_words) {
 inline uint32_t score_long_window(int64_t v) { return (v >= 16 && v <= 4096 && v % 4 == 0) ? (uint32_t)v : SCORE_LONG_WINDOW; }
 
 #ifdef WFA_SCORE_UNIT
+// The reverse complements of the flagged long queries of a call (wfahip_score_batch_packed_rc, wfahip_score_matrix_rc), written once behind
+// the uploaded words: the windows of wfa_score_long_kernel slide forward over global memory, and reading a sequence backwards through them is
+// not worth it.  A workgroup per job; job i is jobs[2 i] = {source word offset lo, hi, length, -} and jobs[2 i + 1] = {destination word offset
+// lo, hi, -, -}, both into `words`: (length + 15) / 16 words and a zero pad word go to the destination.
+__global__ __launch_bounds__(256) void wfa_rc_words_kernel(const uint4 *jobs, uint32_t *words, uint32_t n_jobs) {
+    const uint32_t i = blockIdx.x;
+    if (i >= n_jobs) return;
+    const uint4           s = jobs[2ull * i], d = jobs[2ull * i + 1ull];
+    const uint32_t *const src = words + ((uint64_t)s.y << 32 | s.x);
+    uint32_t *const       dst = words + ((uint64_t)d.y << 32 | d.x);
+    const uint32_t        nw  = (s.z + 15u) >> 4;
+    for (uint32_t j = threadIdx.x; j < nw; j += 256u) dst[j] = rc_word(src, s.z, j);
+    if (threadIdx.x == 0) dst[nw] = 0u;
+}
+
 template <bool MATRIX = false>
 __global__ __launch_bounds__(64) void wfa_score_long_kernel(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -71,7 +88,8 @@ __global__ __launch_bounds__(64) void wfa_score_long_kernel(const KParams P) {
     const auto emit = [&](uint32_t st, uint32_t sc) {
         if (lane == 0) P.score_out[slot] = make_uint2(st, sc);
     };
-    const uint32_t *const gq = P.mx_words + ((uint64_t)qd.y << 32 | qd.x);
+    // (a flagged query row of the matrix: the words wfa_rc_words_kernel wrote; the list's entry of a flagged pair names them itself)
+    const uint32_t *const gq = P.mx_words + ((uint64_t)qd.y << 32 | qd.x) + ((MATRIX && (qd.w & MXF_RC) != 0u) ? P.mx_rc_shift : 0ull);
     const uint32_t *const gt = P.mx_words + ((uint64_t)td.y << 32 | td.x);
     const int      n = (int)qd.z, m = (int)td.z, Ak = m - n;
     const uint32_t nwq = (qd.z + 15u) >> 4, nwt = (td.z + 15u) >> 4;  // index of each sequence's pad word
