@@ -363,6 +363,25 @@ int  wfahip_score_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const
  * WFAHIP_MAX_SEQ_LEN. */
 int  wfahip_revcomp_packed(const uint32_t *src, uint32_t len, uint32_t *dst);
 
+/* Full alignment of the reverse strand of packed queries: the last step of pack once, score both strands, align the survivors -- with a
+ * subset of the same offsets AND flags, on the same buffer.  Nothing is reverse-complemented on the host and nothing is uploaded twice.
+ * q_rc: n_pairs flags (NULL = none set).  q_rc[i] != 0: every field of pair i and every CIGAR op equals what wfahip_align_batch returns
+ * for the bytes (revcomp(query i), target i) under the same p; qbegin / qend are coordinates on the reverse-complemented query.  A pair
+ * whose flag is clear is a pair of wfahip_align_batch_packed, which IS this entry with q_rc = NULL: results, whole-call errors (checked
+ * before the device is touched), empty and too long pairs (whose offsets are never looked at, whatever their flag) and
+ * wfahip_last_timing included.  Offsets may come in any order, may repeat, and may name one offset under different lengths and flags:
+ * both strands of a pair are the pair listed twice, once flagged, and a query offset may point into the middle of a longer sequence.
+ * Where the reverse complement is made: the passes that take words make it from the words (wfa_prepack_words_kernel for the slots of
+ * the duo, lane and long-window first passes, the packed prologue of wfa_wide_kernel; wfa_rc.hpp has the word function); the passes
+ * that read bytes -- the retry rungs, the lane kernel when it packs itself, the generic, team and long-pair kernels -- read a flagged
+ * query at an address of its own in a MIRROR of the byte blob, which exists only in device memory and only in a call with a flag set:
+ * byte 2 B + 47 - a is the complement of byte a of the B = 16 n_words bytes the words stand for, so the reverse complement of any
+ * (offset, length) is a contiguous run of it, and wfa_unpack_pairs_kernel expands a flagged query word by word into it.  A call
+ * with a flag set holds 2 B + 96 bytes of blob on the device in place of B + 32. */
+int  wfahip_align_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                  const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                  const uint8_t *q_rc, uint64_t n_pairs, wfahip_results *out);
+
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns
  * at once with the pair's ticket (0, 1, 2, ... since the last collect) -- and collects all results with ONE batch

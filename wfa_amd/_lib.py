@@ -22,7 +22,7 @@ EXPORTS = [
     "wfahip_version", "wfahip_strerror", "wfahip_device_count", "wfahip_create", "wfahip_destroy",
     "wfahip_align_batch", "wfahip_results_free", "wfahip_align_batch_device", "wfahip_last_timing",
     "wfahip_set_option", "wfahip_debug_wavefronts", "wfahip_free", "wfahip_gen_stride",
-    "wfahip_generate_pairs", "wfahip_packed_words", "wfahip_pack_pairs", "wfahip_align_batch_packed", "wfahip_submit",
+    "wfahip_generate_pairs", "wfahip_packed_words", "wfahip_pack_pairs", "wfahip_align_batch_packed", "wfahip_align_batch_packed_rc", "wfahip_submit",
     "wfahip_pending", "wfahip_collect", "wfahip_create_multi", "wfahip_destroy_multi", "wfahip_multi_size",
     "wfahip_multi_ctx", "wfahip_align_batch_multi", "wfahip_debug_compact_arena",
     "wfahip_generate_pairs_device", "wfahip_align_pair", "wfahip_last_error", "wfahip_debug_clock",
@@ -145,6 +145,8 @@ def lib():
         L.wfahip_pack_pairs.argtypes = [vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, C.POINTER(u64)]
         L.wfahip_align_batch_packed.restype = C.c_int
         L.wfahip_align_batch_packed.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, C.POINTER(Results)]
+        L.wfahip_align_batch_packed_rc.restype = C.c_int
+        L.wfahip_align_batch_packed_rc.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, vp, u64, C.POINTER(Results)]
         L.wfahip_submit.restype = C.c_int
         L.wfahip_submit.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, C.POINTER(u64)]
         L.wfahip_pending.restype = u64

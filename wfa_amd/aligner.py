@@ -270,17 +270,35 @@ class Aligner:
     def align_arrays_packed(self, packed, q_woff, q_len, t_woff, t_len) -> "BatchResult":
         """Batch alignment of pre-packed 2-bit input (include/wfa_hip.h: wfahip_align_batch_packed); pack with
         pack_pairs().  A quarter of the bytes cross PCIe; results are those of align_arrays on the unpacked bytes."""
+        return self.align_arrays_packed_rc(packed, q_woff, q_len, t_woff, t_len, None)
+
+    def align_arrays_packed_rc(self, packed, q_woff, q_len, t_woff, t_len, q_rc) -> "BatchResult":
+        """align_arrays_packed with a flag per pair (include/wfa_hip.h: wfahip_align_batch_packed_rc): a pair whose flag is non-zero
+        aligns the reverse complement of its query, made on the GPU from the same words -- every field and CIGAR op equals
+        align_arrays' on the bytes (revcomp(query), target); qbegin / qend count on the reverse-complemented query.  The last step of
+        pack once, score_arrays_packed_rc both strands, align the survivors: a subset of the same offsets and flags on the same buffer.
+        Offsets may repeat, under any lengths and flags.  q_rc=None: no flag set."""
         n = int(len(q_len))
         packed = np.ascontiguousarray(packed, dtype=np.uint32)
         q_woff = np.ascontiguousarray(q_woff, dtype=np.uint64)
         t_woff = np.ascontiguousarray(t_woff, dtype=np.uint64)
         q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
         t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+        if len(q_woff) != n or len(t_woff) != n or len(t_len) != n:
+            raise ValueError("offset and length arrays differ in length")
+        if q_rc is not None:
+            q_rc = np.ascontiguousarray(np.asarray(q_rc) != 0, dtype=np.uint8)
+            if q_rc.shape != (n,):
+                raise ValueError("q_rc must hold one flag per pair")
         res = L.Results()
         prm = self._params()
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        L.check(L.lib().wfahip_align_batch_packed(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len),
-                                                  vp(t_woff), vp(t_len), n, C.byref(res)), "wfahip_align_batch_packed")
+        if q_rc is None:
+            L.check(L.lib().wfahip_align_batch_packed(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len),
+                                                      vp(t_woff), vp(t_len), n, C.byref(res)), "wfahip_align_batch_packed")
+        else:
+            L.check(L.lib().wfahip_align_batch_packed_rc(self._ctx, C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len),
+                                                         vp(t_woff), vp(t_len), vp(q_rc), n, C.byref(res)), "wfahip_align_batch_packed_rc")
         return _take_results(res, n)
 
     # -- new: score only (include/wfa_hip.h: wfahip_score_batch) -----------------------------------

@@ -148,6 +148,10 @@ struct KParams {
                                      // complement of the query, made as its words are staged (mx_stage); nullptr: none set
     uint64_t        mx_rc_shift;     // wfa_score_long_kernel<MATRIX>: the reverse-complemented words of a flagged long query (wfa_rc_words_kernel) lie this
                                      // many words behind its table entry's
+    // ---- reverse-strand full alignment (wfahip_align_batch_packed_rc; appended last for the same reason)
+    uint64_t        rc_top;          // TOP of the blob's mirror (wfa_rc.hpp: rc_mirror_top), 0 = the call has no flag set.  q_off of a pair whose q_rc
+                                     // flag is set is then the MIRROR address of its query's reverse complement: the passes that read bytes read it
+                                     // like any other offset, the three that read words recover the forward word offset from it (rc_mirror_word)
 };
 
 }  // namespace wfa

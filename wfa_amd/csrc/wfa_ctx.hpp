@@ -104,6 +104,8 @@ struct wfahip_ctx {
     int64_t       opt_autopack             = 1;   // 1: wfahip_align_batch 2-bit packs large pure-ACGT batches on host threads while earlier slices upload
     const uint32_t *pk_words = nullptr;      // host entries with packed input, while they call the alignment: the uploaded 2-bit words (device); the byte
                                              // blob they stand for is filled in only for the pairs a pass reads as bytes (wfa_unpack_pairs_kernel)
+    const uint8_t *pk_rc = nullptr;          // ... wfahip_align_batch_packed_rc with a flag set: the flags of the pairs the alignment is called with (device,
+    uint64_t      pk_top = 0;                //     in_rc) and the TOP of the blob's mirror, where the flagged queries' offsets point (wfa_rc.hpp); else nullptr, 0
     bool          one_ctl_clean = false;     // ... whose control words the last call's kernel left zeroed
     DevBuf        one_ctl;                   // ... and its control words: queue head / redo count / ops cursor, then the done queue of the streamed backtrace
     int64_t       opt_arena_budget_pct     = 60;  // long-pair ladder: percent of device memory its arenas may take (80 / 85 / 90: five or six slots
@@ -177,7 +179,7 @@ struct wfahip_ctx {
     DevBuf        score_out;                      // wfahip_score_batch: {status, score} per pair
     DevBuf        wide_ckpt;                      // wfa_wide_kernel: what its first launch hands its second, per pair of the chunk
     DevBuf        mx_seq, mx_words;               // wfahip_score_matrix: the call's sequence table (wfa_matrix.hpp)
-    DevBuf        in_rc, rc_jobs;                 // the _rc score entries: the call's flags (per pair / per query row), the jobs of wfa_rc_words_kernel (whose
+    DevBuf        in_rc, rc_jobs;                 // the _rc entries: the call's flags (per pair / per query row), the jobs of wfa_rc_words_kernel (whose
                                                   // words lie in mx_words, behind the uploaded ones)
     DevBuf        sd_ctl, sd_blk, sd_list, sd_redo;  // wfahip_score_batch_device (wfa_score_dev.hpp): control words, tile sums, the long pairs, the pairs of the full path
     uint64_t      sd_n_words = 0, sd_n_listed = 0;   // ... what its last call left in mx_words / mx_seq (wfahip_debug_score_device_list)
@@ -349,7 +351,15 @@ int align_batch_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *se
                       const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
 // wfahip_align_batch_packed behind its guard: the same for wfahip_score_batch_packed, over a word buffer of that entry's own
 int align_batch_packed_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
-                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out);
+                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out,
+                             const uint8_t *q_rc = nullptr);
+// the flags of a call as the kernels take them: nullptr when none of the n is set (they then run as without flags)
+inline const uint8_t *any_flag(const uint8_t *f, uint64_t n) {
+    if (f)
+        for (uint64_t i = 0; i < n; i++)
+            if (f[i]) return f;
+    return nullptr;
+}
 
 // ---- defined in wfa_debug.hip
 // behind a launch of the team kernels (team_c: wfa_teamc_kernel) and its synchronisation: prints the reports of their control words and

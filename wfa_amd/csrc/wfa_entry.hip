@@ -5,6 +5,7 @@
 #define WFA_NO_AUX_KERNELS 1  // (device functions and constants of the kernels' headers only: the kernels are launched by wfa_host.hip)
 #include "wfa_ctx.hpp"
 #include "wfa_hostpack.hpp"
+#include "wfa_rc.hpp"
 #include "wfa_generic.hpp"
 #include "wfa_packed.hpp"
 #include "wfa_blk.hpp"
@@ -216,9 +217,28 @@ __global__ __launch_bounds__(256) void wfa_unpack_kernel(const uint32_t *__restr
     bytes[i] = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-__global__ __launch_bounds__(256) void wfa_scale_offsets_kernel(uint64_t *q_off, uint64_t *t_off, uint64_t n) {  // words -> bytes
+// ... and, option "unpack_all" of a call with flags (wfahip_align_batch_packed_rc), the mirror of the same words behind the blob: word i
+// reversed and complemented into its 16-byte block (wfa_rc.hpp), so that the old route works unchanged on the flagged queries' offsets
+__global__ __launch_bounds__(256) void wfa_unpack_mirror_kernel(const uint32_t *__restrict__ words, uint8_t *__restrict__ blob, uint64_t top, uint64_t w0,
+                                                                uint64_t w1) {
+    const uint64_t i = w0 + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= w1) return;
+    uint32_t o[4];
+    rc_mirror_letters(words[i], o);
+    *reinterpret_cast<uint4 *>(blob + rc_mirror_block(top, i)) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// words -> bytes.  rc != nullptr (a call with a flag set): the query of a flagged pair that is neither empty nor too long gets the
+// address of its reverse complement in the blob's mirror instead (wfa_rc.hpp); an empty or too long pair's offsets are never read
+__global__ __launch_bounds__(256) void wfa_scale_offsets_kernel(uint64_t *q_off, uint64_t *t_off, uint64_t n, const uint32_t *__restrict__ q_len,
+                                                                const uint32_t *__restrict__ t_len, const uint8_t *__restrict__ rc, uint64_t top) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) q_off[i] *= 16, t_off[i] *= 16;
+    if (i >= n) return;
+    t_off[i] *= 16;
+    if (rc != nullptr && rc[i] != 0 && q_len[i] != 0u && t_len[i] != 0u && q_len[i] <= WFAHIP_MAX_SEQ_LEN && t_len[i] <= WFAHIP_MAX_SEQ_LEN)
+        q_off[i] = rc_mirror_off(top, q_off[i], q_len[i]);
+    else
+        q_off[i] *= 16;
 }
 
 struct PackedFacts {
@@ -231,11 +251,13 @@ static int align_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
                             uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
                             const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs,
                             wfahip_results *out, const uint32_t *packed = nullptr,
-                            const std::function<int(uint64_t, uint64_t)> *lazy_pack = nullptr, const PackedFacts *facts = nullptr) {
+                            const std::function<int(uint64_t, uint64_t)> *lazy_pack = nullptr, const PackedFacts *facts = nullptr,
+                            const uint8_t *q_rc = nullptr) {
     // (facts: the caller is the library itself -- it laid the packed words out pair after pair and has already validated the
     // caller's offsets and summed the lengths: the three passes over a million pairs this function would make are 3 ms of a 38 ms call)
     // (lazy_pack: `packed` is the library's own buffer and is only filled as the pipeline gets to a range of pairs --
     // lazy_pack(first, last) packs pairs [first, last) and returns 0, or 2 when it meets a byte outside ACGT)
+    // (q_rc, packed input only: a flag per pair, != 0 = the pair aligns the reverse complement of its query -- wfahip_align_batch_packed_rc)
     if (!ctx || !out) return WFAHIP_ERR_BAD_ARG;
     // (pre-packed input: q_off / t_off arrive in WORDS of 16 bases; they are uploaded as they are and scaled to byte
     // offsets on the device -- a second pair of host arrays would cost more in page faults than the alignment of a slice)
@@ -245,26 +267,7 @@ static int align_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
     if (rc) return rc;
     if (n_pairs == 0) return WFAHIP_OK;
     if (!q_off || !q_len || !t_off || !t_len || (!seq_blob && !packed && blob_bytes)) return WFAHIP_ERR_BAD_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the bytes [lo, hi) of the blob -> in_blob on stream `s` (packed input: the words that hold them, then the unpack kernel)
-    const auto upload_range = [&](uint64_t lo, uint64_t hi, hipStream_t s) -> hipError_t {
-        if (hi <= lo) return hipSuccess;
-        if (!packed) return hipMemcpyAsync(static_cast<char *>(ctx->in_blob.p) + lo, seq_blob + lo, hi - lo, hipMemcpyHostToDevice, s);
-        // (the words stay words: the alignment copies them into the first pass's slots and expands only the pairs a pass reads
-        // as bytes -- ctx->pk_words below; wfa_unpack_kernel, which expanded everything, is kept for option "unpack_all")
-        const uint64_t w0 = lo / 16, w1 = (hi + 15) / 16;
-        hipError_t     e  = hipMemcpyAsync(static_cast<uint32_t *>(ctx->in_packed.p) + w0, packed + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess || ctx->opt_unpack_all == 0) return e;
-        hipLaunchKernelGGL(wfa_unpack_kernel, dim3((uint32_t)((w1 - w0 + 255) / 256)), dim3(256), 0, s,
-                           static_cast<const uint32_t *>(ctx->in_packed.p), static_cast<uint4 *>(ctx->in_blob.p), w0, w1);
-        return hipGetLastError();
-    };
-    struct PkGuard {  // the packed words are the alignment's input for the duration of this call only
-        wfahip_ctx *c;
-        ~PkGuard() { c->pk_words = nullptr; }
-    } pk_guard{ctx};
-    // (ctx->pk_words is set once in_packed is allocated, below)
-
+    // (the last of the whole-call errors: nothing above or in this loop dereferences the context)
     uint32_t max_len = facts ? std::max(1u, facts->max_len) : 1;
     uint64_t sum_len = facts ? facts->sum_len : 0;
     for (uint64_t i = 0; i < n_pairs && !facts; i++) {
@@ -277,9 +280,38 @@ static int align_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
             sum_len += (uint64_t)q_len[i] + t_len[i];
         }
     }
+    // the flags as the kernels take them: nullptr when none is set -- the call is then the one without flags, to the byte
+    q_rc = packed ? any_flag(q_rc, n_pairs) : nullptr;
+    const uint64_t rc_top = q_rc ? rc_mirror_top(blob_bytes / 16) : 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the bytes [lo, hi) of the blob -> in_blob on stream `s` (packed input: the words that hold them, then the unpack kernel)
+    const auto upload_range = [&](uint64_t lo, uint64_t hi, hipStream_t s) -> hipError_t {
+        if (hi <= lo) return hipSuccess;
+        if (!packed) return hipMemcpyAsync(static_cast<char *>(ctx->in_blob.p) + lo, seq_blob + lo, hi - lo, hipMemcpyHostToDevice, s);
+        // (the words stay words: the alignment copies them into the first pass's slots and expands only the pairs a pass reads
+        // as bytes -- ctx->pk_words below; wfa_unpack_kernel, which expanded everything, is kept for option "unpack_all")
+        const uint64_t w0 = lo / 16, w1 = (hi + 15) / 16;
+        hipError_t     e  = hipMemcpyAsync(static_cast<uint32_t *>(ctx->in_packed.p) + w0, packed + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess || ctx->opt_unpack_all == 0) return e;
+        hipLaunchKernelGGL(wfa_unpack_kernel, dim3((uint32_t)((w1 - w0 + 255) / 256)), dim3(256), 0, s,
+                           static_cast<const uint32_t *>(ctx->in_packed.p), static_cast<uint4 *>(ctx->in_blob.p), w0, w1);
+        if (rc_top)  // (w1 <= n_words: the mirror blocks of these words lie inside the enlarged blob)
+            hipLaunchKernelGGL(wfa_unpack_mirror_kernel, dim3((uint32_t)((w1 - w0 + 255) / 256)), dim3(256), 0, s,
+                               static_cast<const uint32_t *>(ctx->in_packed.p), static_cast<uint8_t *>(ctx->in_blob.p), rc_top, w0, w1);
+        return hipGetLastError();
+    };
+    struct PkGuard {  // the packed words are the alignment's input for the duration of this call only
+        wfahip_ctx *c;
+        ~PkGuard() { c->pk_words = nullptr, c->pk_rc = nullptr, c->pk_top = 0; }
+    } pk_guard{ctx};
+    // (ctx->pk_words is set once in_packed is allocated, below)
+
     hipStream_t st = ctx->stream;
     // device staging (+16 bytes so aligned dword loads at the tail stay inside the allocation)
-    if ((rc = ensure(ctx, ctx->in_blob, blob_bytes + 32))) return rc;
+    // (a call with flags: the blob's mirror behind it, where the flagged queries' reverse complements are read -- wfa_rc.hpp)
+    if ((rc = ensure(ctx, ctx->in_blob, q_rc ? rc_mirror_bytes(blob_bytes / 16) : blob_bytes + 32))) return rc;
+    if (q_rc && (rc = ensure(ctx, ctx->in_rc, n_pairs))) return rc;
+    if (q_rc) ctx->pk_rc = static_cast<const uint8_t *>(ctx->in_rc.p), ctx->pk_top = rc_top;
     if (packed && (rc = ensure(ctx, ctx->in_packed, (blob_bytes + 15) / 16 * 4 + 16))) return rc;
     if (packed && ctx->opt_unpack_all == 0) ctx->pk_words = static_cast<const uint32_t *>(ctx->in_packed.p);
     if ((rc = ensure(ctx, ctx->in_qoff, n_pairs * 8))) return rc;
@@ -368,9 +400,11 @@ static int align_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
         HIP_TRY(hipMemcpyAsync(ctx->in_toff.p, t_off, n_pairs * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ctx->in_qlen.p, q_len, n_pairs * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ctx->in_tlen.p, t_len, n_pairs * 4, hipMemcpyHostToDevice, st));
+        if (q_rc) HIP_TRY(hipMemcpyAsync(ctx->in_rc.p, q_rc, n_pairs, hipMemcpyHostToDevice, st));
         if (packed) {
             hipLaunchKernelGGL(wfa_scale_offsets_kernel, dim3((uint32_t)((n_pairs + 255) / 256)), dim3(256), 0, st,
-                               static_cast<uint64_t *>(ctx->in_qoff.p), static_cast<uint64_t *>(ctx->in_toff.p), n_pairs);
+                               static_cast<uint64_t *>(ctx->in_qoff.p), static_cast<uint64_t *>(ctx->in_toff.p), n_pairs,
+                               static_cast<const uint32_t *>(ctx->in_qlen.p), static_cast<const uint32_t *>(ctx->in_tlen.p), ctx->pk_rc, rc_top);
             HIP_TRY(hipGetLastError());
         }
     }
@@ -496,6 +530,7 @@ static int align_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
                     (void)hipEventSynchronize(ctx->ev_up[k]);
                     std::fprintf(stderr, "[wfahip]   slice %d: blob part here at +%.1f ms\n", k, ms_of(t_dev, now()));
                 }
+                if (q_rc) ctx->pk_rc = static_cast<const uint8_t *>(ctx->in_rc.p) + k0;  // (the slice's pairs count from 0)
                 rc = align_device(ctx, p, ctx->in_blob.p, blob_bytes, static_cast<char *>(ctx->in_qoff.p) + 8 * k0,
                                   static_cast<char *>(ctx->in_qlen.p) + 4 * k0, static_cast<char *>(ctx->in_toff.p) + 8 * k0,
                                   static_cast<char *>(ctx->in_tlen.p) + 4 * k0, nk, max_len,
@@ -588,6 +623,7 @@ static int align_batch_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8
                              ms_of(t_h2d, t_dev), ms_of(t_dev, now()));
             return WFAHIP_OK;
         }
+        if (q_rc) ctx->pk_rc = static_cast<const uint8_t *>(ctx->in_rc.p);  // (all pairs again, after slices that moved it)
         rc = align_device(ctx, p, d_blob, blob_bytes, d_qoff, d_qlen, d_toff, d_tlen, n_pairs, max_len, ctx->out_rec.p, ctx->out_ops.p,
                           ops_cap, &needed, st, false);
         if (rc == WFAHIP_ERR_OOM && needed > ops_cap) {
@@ -771,24 +807,32 @@ extern "C" int wfahip_align_batch_bounded(wfahip_ctx *ctx, const wfahip_params *
 }
 
 // ---- pre-packed input (a quarter of the bytes cross PCIe)
+// (q_rc: a flag per pair, nullptr = none set -- wfahip_align_batch_packed_rc; the entry without flags is this one with nullptr)
 int align_batch_packed_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
-                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out) {
+                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out,
+                             const uint8_t *q_rc) {
     if (!ctx || !out || (!packed && n_words)) return WFAHIP_ERR_BAD_ARG;
     if (n_pairs && (!q_woff || !t_woff)) return WFAHIP_ERR_BAD_ARG;
     static const uint32_t no_words[4] = {0, 0, 0, 0};
-    return align_batch_impl(ctx, p, nullptr, n_words * 16, q_woff, q_len, t_woff, t_len, n_pairs, out, packed ? packed : no_words);
+    return align_batch_impl(ctx, p, nullptr, n_words * 16, q_woff, q_len, t_woff, t_len, n_pairs, out, packed ? packed : no_words, nullptr, nullptr, q_rc);
 }
 
-extern "C" int wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
-                                         const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff,
-                                         const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out) {
+extern "C" int wfahip_align_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                            const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                            const uint8_t *q_rc, uint64_t n_pairs, wfahip_results *out) {
     try {
-        return align_batch_packed_entry(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, n_pairs, out);
+        return align_batch_packed_entry(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, n_pairs, out, q_rc);
     } catch (const std::bad_alloc &) {
         return WFAHIP_ERR_OOM;
     } catch (...) {
         return WFAHIP_ERR_INTERNAL;
     }
+}
+
+extern "C" int wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                         const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff,
+                                         const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out) {
+    return wfahip_align_batch_packed_rc(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, nullptr, n_pairs, out);
 }
 
 extern "C" uint64_t wfahip_packed_words(uint32_t len) { return ((uint64_t)len + 15) / 16 + 1; }  // (+1: the pad word the kernels' 16-base windows may read)

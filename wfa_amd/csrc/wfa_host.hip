@@ -163,7 +163,17 @@ __global__ __launch_bounds__(256) void wfa_prepack_words_kernel(const KParams P,
     else if (((nq > mt ? nq : mt) + 15u) / 16u + 1u > SW)
         status = ST_REDO_LDS;
     uint32_t *const slot = out + (uint64_t)wi * PW;
-    if (status == ST_PENDING) {
+    if (WFA_RARE(status == ST_PENDING && P.q_rc != nullptr && __builtin_amdgcn_readfirstlane((int)P.q_rc[pr]) != 0)) {
+        // (wfahip_align_batch_packed_rc, a flagged pair -- a wave per pair: the branch is uniform: the query half of the slot is the reverse
+        // complement, made word by word from the forward words its mirror address names; the bits beyond its last base are zero)
+        const uint32_t *const qw = words + rc_mirror_word(P.rc_top, P.q_off[pr], nq), *const tw = words + P.t_off[pr] / 16u;
+        const uint32_t nwq = (nq + 15u) >> 4, nwt = (mt + 15u) >> 4;
+        for (uint32_t v = lane; v < 2u * SW; v += 64u) {
+            const bool     isq = v < SW;
+            const uint32_t j   = isq ? v : v - SW;
+            slot[4u + v]       = j < (isq ? nwq : nwt) ? (isq ? rc_word(qw, nq, j) : tw[j]) : 0u;
+        }
+    } else if (status == ST_PENDING) {
         const uint32_t *const qw = words + P.q_off[pr] / 16u, *const tw = words + P.t_off[pr] / 16u;
         const uint32_t nwq = (nq + 15u) >> 4, nwt = (mt + 15u) >> 4;
         for (uint32_t v = lane; v < 2u * SW; v += 64u) {
@@ -182,8 +192,22 @@ __global__ __launch_bounds__(256) void wfa_unpack_pairs_kernel(const KParams P, 
     const uint32_t len[2] = {P.q_len[pr], P.t_len[pr]};
     const uint64_t off[2] = {P.q_off[pr], P.t_off[pr]};
     if (len[0] == 0u || len[1] == 0u || len[0] > 0x1FFFFFFFu || len[1] > 0x1FFFFFFFu) return;
+    bool rcq = false;
+    if (WFA_RARE(P.q_rc != nullptr && __builtin_amdgcn_readfirstlane((int)P.q_rc[pr]) != 0)) {
+        // (a flagged query: every forward word goes, reversed and complemented, to its own 16-byte block of the mirror, whose bytes from
+        // off[0] on are then the reverse complement -- wfa_rc.hpp.  Whoever else writes the block writes the same 16 bytes)
+        const uint64_t w0 = rc_mirror_word(P.rc_top, off[0], len[0]);
+        const uint32_t nw = (len[0] + 15u) >> 4;
+        for (uint32_t j = lane; j < nw; j += 64u) {
+            uint32_t o[4];
+            rc_mirror_letters(words[w0 + j], o);
+            *reinterpret_cast<uint4 *>(blob + rc_mirror_block(P.rc_top, w0 + j)) = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+        rcq = true;
+    }
 #pragma unroll
     for (int q = 0; q < 2; q++) {
+        if (q == 0 && rcq) continue;
         const uint32_t nw = (len[q] + 15u) >> 4;
         for (uint32_t j = lane; j < nw; j += 64u) {
             const uint32_t w = words[off[q] / 16u + j];
@@ -658,6 +682,10 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
 
     KParams P{};
     P.blob = static_cast<const uint8_t *>(d_blob), P.blob_bytes = blob_bytes;
+    if (ctx->pk_top) {  // (packed input with flags: the blob has its mirror behind it, and the flagged queries' offsets point there)
+        P.blob_bytes = rc_mirror_bytes(blob_bytes / 16);
+        P.q_rc = ctx->pk_rc, P.rc_top = ctx->pk_top;
+    }
     P.q_off = static_cast<const uint64_t *>(d_q_off), P.q_len = static_cast<const uint32_t *>(d_q_len);
     P.t_off = static_cast<const uint64_t *>(d_t_off), P.t_len = static_cast<const uint32_t *>(d_t_len);
     P.queue_head = d_ctrl + 0;

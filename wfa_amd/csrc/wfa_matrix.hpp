@@ -37,10 +37,14 @@ __device__ inline void mx_cell(const KParams &P, uint32_t idx, uint4 &qd, uint4 
 }
 // entry of pair `pair` of a packed pair list (wave-uniform): {word offset lo, hi, length, 0 or MXF_RC}; rc: the list's flags (nullptr: none set)
 // (shift = 4: the offsets count BYTES of the blob the words stand for, 16 to a word -- the full-alignment path, wfa_scale_offsets_kernel)
-__device__ inline uint4 pk_entry(const uint64_t *woff, uint32_t pair, uint32_t len, uint32_t shift = 0u, const uint8_t *rc = nullptr) {
-    const uint64_t o   = woff[pair] >> shift;
+// (top != 0, the full-alignment path with flags, wfahip_align_batch_packed_rc: a flagged pair's offset is the mirror address of its
+// reverse complement -- the entry names the forward words it was made from, wfa_rc.hpp)
+__device__ inline uint4 pk_entry(const uint64_t *woff, uint32_t pair, uint32_t len, uint32_t shift = 0u, const uint8_t *rc = nullptr, uint64_t top = 0u) {
+    uint64_t       o   = woff[pair] >> shift;
     const auto     rfl = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-    return make_uint4(rfl((uint32_t)o), rfl((uint32_t)(o >> 32)), len, (rc != nullptr && rfl(rc[pair]) != 0u) ? MXF_RC : 0u);
+    const uint32_t f   = (rc != nullptr && rfl(rc[pair]) != 0u) ? MXF_RC : 0u;
+    if (WFA_RARE(f != 0u && top != 0u)) o = rc_mirror_word(top, woff[pair], len);
+    return make_uint4(rfl((uint32_t)o), rfl((uint32_t)(o >> 32)), len, f);
 }
 // words 0 .. (len + 15) / 16 of a packed sequence (the last one its pad word) into LDS: stage_pack's layout.  (Caller-packed words:
 // the pad word and the bits of the last word beyond the sequence may hold anything -- SeqView<0>::lcp clamps to the sequence ends,

@@ -372,13 +372,6 @@ void revcomp_packed_seq(const uint32_t *src, uint32_t len, uint32_t *dst) {
     for (uint32_t j = 0; j < nw; j++) dst[j] = rc_word(src, len, j);
     dst[nw] = 0u;
 }
-// the flags of a call as the kernels take them: nullptr when none of the n is set (they then run as without flags)
-const uint8_t *any_flag(const uint8_t *f, uint64_t n) {
-    if (f)
-        for (uint64_t i = 0; i < n; i++)
-            if (f[i]) return f;
-    return nullptr;
-}
 }  // namespace
 
 // Host only: the reverse complement of one packed sequence, as wfahip_pack_pairs would have written it (include/wfa_hip.h)

@@ -172,7 +172,8 @@ __global__ __launch_bounds__(64 * NW) WFA_WIDE_EU_ATTR void wfa_wide_kernel(cons
         if constexpr (STAGE == STAGE_PACKED) {
             if (status == ST_PENDING) {
                 // (full alignment, packed host entries: P.mx_words = the uploaded words, word i bytes [16 i, 16 i + 16) of the blob P.q_off / P.t_off count)
-                mx_stage<64 * NW>(P.mx_words, pk_entry(P.q_off, pair, nq, SCORE ? 0u : 4u, SCORE ? P.q_rc : nullptr), lq, tid);
+                // (a flagged query of the full path lies at its mirror address: pk_entry names the forward words, mx_stage reverse-complements them)
+                mx_stage<64 * NW>(P.mx_words, pk_entry(P.q_off, pair, nq, SCORE ? 0u : 4u, P.q_rc, SCORE ? 0ull : P.rc_top), lq, tid);
                 mx_stage<64 * NW>(P.mx_words, pk_entry(P.t_off, pair, mt, SCORE ? 0u : 4u), lt, tid);
             }
         } else if (status == ST_PENDING) {
