@@ -382,6 +382,59 @@ int  wfahip_align_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const
                                   const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                                   const uint8_t *q_rc, uint64_t n_pairs, wfahip_results *out);
 
+/* CIGAR text, rendered where the ops are.  AlignmentResult.CIGAR(onlyAlignedRegion) (wfa_cigar.go:217-255) of every pair of a
+ * batch as bytes: what a SAM / PAF writer puts into a file.  The rule (wfa_amd/csrc/wfa_cigar.hpp, one source for the kernels and
+ * the host renderer): every op renders as the decimal of op & 0xFFFFFFFF -- a full u32, one to ten digits, no leading zero, a
+ * count of 0 as "0" -- followed by the byte op >> 32, verbatim, whatever byte it is; the ops render in the order the record indexes
+ * them.  only_aligned != 0 renders the ops from the first 'M' op to the last 'M' op, inclusive (trimOps); a pair without an 'M' op
+ * (A against C, global: 1X), where the reference would panic, renders the empty string.  A pair's op count is OPS_LEN when its
+ * status is WFAHIP_PAIR_OK, else 0 -- the records of failed pairs may hold stale words: empty, too long, no-memory and over-max
+ * pairs render the empty string.
+ *
+ * wfahip_cigar_text_device: d_rec / d_ops as wfahip_align_batch_device (or _bounded_device) left them, or any records and ops of
+ * that layout; every pointer is a device address on the context's GPU and stays the caller's.  Pair i's text is
+ * d_text[d_text_off[i] .. d_text_off[i + 1]), without terminators; d_text_off (u64[n_pairs + 1], 8-byte aligned) starts at 0 and
+ * ends at the total, which *text_needed (if non-NULL) receives.  No byte of d_text at or beyond the total is written; d_rec and
+ * d_ops are never written.  text_cap below the total: WFAHIP_ERR_OOM with d_text untouched and d_text_off filled -- a caller sizes
+ * with d_text = NULL, text_cap = 0 and calls again.  An OK pair whose ops leave [0, ops_cap) (OPS_LEN > ops_cap or OPS_OFF >
+ * ops_cap - OPS_LEN): WFAHIP_ERR_BAD_ARG with d_text untouched, before the kernel that reads those ops to write text is launched
+ * (d_text_off then holds nothing of use).  WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx; with n_pairs > 0 a
+ * null d_rec or d_text_off; a null d_ops with ops_cap > 0; a null d_text with text_cap > 0; n_pairs beyond 0xFFFFFFF0.
+ * n_pairs == 0 returns WFAHIP_OK with *text_needed = 0 and writes d_text_off[0] = 0 when d_text_off is non-null (the only case in
+ * which it touches the context or the device).  stream = hipStream_t (NULL = the context's own).  Synchronous.  wfahip_last_timing
+ * is not touched.
+ * Three passes (wfa_cigar.hip): wfa_cigar_len_kernel, a wave per pair -- the trimmed range from ballots, the text length from
+ * compares; an exclusive 64-bit scan of the lengths in pair order, in place in d_text_off; wfa_cigar_write_kernel, a wave per pair
+ * in rounds of 64 ops, each lane rendering its op where a wave prefix sum puts it.  Scratch lives in the context and is allocated
+ * once per shape; one fetch of 64 bytes of counters per call crosses PCIe.  1e6 x 1 kbp pairs, 92 ops each: 0.96 ms for the three
+ * passes (136 ms for wfahip_cigar_text on 16 host threads).  WFAHIP_DEBUG_TIMING=1 prints the passes' times to stderr. */
+int  wfahip_cigar_text_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                              uint64_t n_pairs, int only_aligned, void *d_text, uint64_t text_cap,
+                              void *d_text_off /* u64[n_pairs + 1] */, uint64_t *text_needed, void *stream);
+
+/* Host only, no device, no context: the same bytes for a wfahip_results in host memory (n_threads host threads over contiguous
+ * ranges of pairs, the same header functions as the kernels).  out->text holds n_bytes bytes (NULL when n_bytes == 0), out->off
+ * n + 1 offsets, off[0] = 0 and off[n] = n_bytes; both are malloc'd and released with wfahip_cigars_free.  r->n == 0 gives
+ * n = n_bytes = 0, text = NULL and off pointing at one 0.  WFAHIP_ERR_BAD_ARG (out zeroed, when there is one): a null r or out;
+ * with r->n > 0 a null status, ops_off or ops_len; a null ops with n_ops > 0; an OK pair with ops_off[i] + ops_len[i] > n_ops. */
+typedef struct { uint64_t n; uint64_t n_bytes; char *text; uint64_t *off; /* n + 1 */ } wfahip_cigars;
+int  wfahip_cigar_text(const wfahip_results *r, int only_aligned, int n_threads, wfahip_cigars *out);
+void wfahip_cigars_free(wfahip_cigars *c);
+
+/* Host blobs in, fields + CIGAR text out: no ops cross PCIe.  Inputs and whole-call errors as wfahip_align_batch, checked first
+ * (plus WFAHIP_ERR_BAD_ARG for a null cig).  out has every field array of wfahip_align_batch for the same input; ops_len is the
+ * op count, ops_off is all 0, ops == NULL and n_ops == 0 (release with wfahip_results_free, as ever).  cig holds the text of
+ * wfahip_cigar_text(.., only_aligned) over that entry's results, byte for byte (release with wfahip_cigars_free).
+ * The PLAIN path only: one upload of the blob and the four arrays, the alignment with its op-capacity retry, the three kernels
+ * above, one download of records, text and offsets, the records unpacked on the host.  There is no slicing, no overlap of the
+ * upload with the alignment and no autopack -- what wfahip_align_batch does for batches of 200 000 pairs and more.  Measured on
+ * 1e6 x 1 kbp pairs it is the faster way to the text all the same (160 ms host to host against 224 ms for wfahip_align_batch
+ * followed by wfahip_cigar_text on 16 threads: 215 MB of text leave the device in place of 737 MB of ops; KERNELS.md 4p).  A
+ * caller picks by what it needs: this entry where the text is the product and the ops are not. */
+int  wfahip_align_batch_text(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
+                             const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
+                             uint64_t n_pairs, int only_aligned, wfahip_results *out, wfahip_cigars *cig);
+
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns
  * at once with the pair's ticket (0, 1, 2, ... since the last collect) -- and collects all results with ONE batch

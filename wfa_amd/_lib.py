@@ -31,6 +31,7 @@ EXPORTS = [
     "wfahip_align_batch_bounded", "wfahip_align_batch_bounded_device", "wfahip_score_batch_packed",
     "wfahip_wide_class_bounds", "wfahip_debug_wide_plan",
     "wfahip_score_batch_packed_rc", "wfahip_score_matrix_rc", "wfahip_revcomp_packed",
+    "wfahip_cigar_text_device", "wfahip_cigar_text", "wfahip_cigars_free", "wfahip_align_batch_text",
 ]
 
 
@@ -52,6 +53,11 @@ class Results(C.Structure):
 
 class Scores(C.Structure):
     _fields_ = [("n", C.c_uint64), ("status", C.POINTER(C.c_int32)), ("score", C.POINTER(C.c_uint32))]
+
+
+class Cigars(C.Structure):
+    """wfahip_cigars: pair i's CIGAR text is text[off[i] .. off[i + 1])"""
+    _fields_ = [("n", C.c_uint64), ("n_bytes", C.c_uint64), ("text", C.POINTER(C.c_uint8)), ("off", C.POINTER(C.c_uint64))]
 
 
 class Timing(C.Structure):
@@ -122,6 +128,14 @@ def lib():
         L.wfahip_align_batch_bounded_device.restype = C.c_int
         L.wfahip_align_batch_bounded_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, u32, vp, vp,
                                                         u64, C.POINTER(u64), vp]
+        L.wfahip_cigar_text_device.restype = C.c_int
+        L.wfahip_cigar_text_device.argtypes = [vp, vp, vp, u64, u64, C.c_int, vp, u64, vp, C.POINTER(u64), vp]
+        L.wfahip_cigar_text.restype = C.c_int
+        L.wfahip_cigar_text.argtypes = [C.POINTER(Results), C.c_int, C.c_int, C.POINTER(Cigars)]
+        L.wfahip_cigars_free.argtypes = [C.POINTER(Cigars)]
+        L.wfahip_align_batch_text.restype = C.c_int
+        L.wfahip_align_batch_text.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, C.c_int, C.POINTER(Results),
+                                              C.POINTER(Cigars)]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

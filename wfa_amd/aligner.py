@@ -459,6 +459,167 @@ class Aligner:
         L.check(rc, "wfahip_score_batch_device" + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return status, score
 
+    # -- new: full alignment and CIGAR text on device-resident data (include/wfa_hip.h: wfahip_align_batch_device, wfahip_cigar_text_device)
+    def _want_tensor(self, name, t, dtype, dev=None, dim=1):
+        """the checks score_tensors makes, for one tensor: ValueError unless t is a contiguous dim-dimensional tensor of dtype on
+        the aligner's device (and on dev, when given); returns its device"""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor on the aligner's device, not {type(t).__name__}")
+        if not t.is_cuda:
+            raise ValueError(f"{name} is on the host: a tensor on the aligner's device is needed")
+        if getattr(self, "_device", None) is not None and t.device.index != self._device:
+            raise ValueError(f"{name} is on {t.device}, the aligner on device {self._device}")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, not on {dev}")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+        if t.dim() != dim or not t.is_contiguous():
+            raise ValueError(f"{name} must be {dim}-dimensional and contiguous")
+        return t.device
+
+    @staticmethod
+    def _want_stream(stream, dev):
+        import torch
+        if stream is None:
+            return torch.cuda.current_stream(dev)
+        if not isinstance(stream, torch.cuda.Stream):
+            raise ValueError("stream must be a torch.cuda.Stream")
+        return stream
+
+    @staticmethod
+    def _order_after_torch(stream, dev):
+        """what torch has queued on its current stream comes before the call on `stream`.  Torch's default stream has the handle 0,
+        which the C-ABI reads as "the context's own stream" -- a non-blocking one, not ordered behind torch's: it is drained."""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        if stream.cuda_stream == 0:
+            cur.synchronize()
+            stream.synchronize()
+        else:
+            stream.wait_stream(cur)
+
+    def align_tensors(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, stream=None):
+        """Full alignment of a batch that lives on the aligner's GPU, the results left there: torch tensors in, as score_tensors takes
+        them (blob uint8, q_off int64, q_len int32, t_off int64, t_len int32 -- what generate_pairs_device returns); out
+        (rec, ops): rec int32 [n, 16], one record per pair (the words of include/wfa_hip.h's WFAHIP_REC_*, the C-ABI's uint32 bit
+        for bit), and ops int64, the op buffer the records' OPS_OFF / OPS_LEN index (op << 32 | count; in completion order, with
+        slack between pairs and behind the last).  max_score > 0: wfahip_align_batch_bounded_device -- a pair over the bound has
+        the record {8, 0, ..}.  The op buffer is sized by a first guess and the call repeated with what it needed when that was too
+        small.  cigar_tensors renders the pair (rec, ops) to text.  Conventions, stream and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("blob", blob, torch.uint8)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(q_len.numel())
+        if q_off.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors differ in length")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        stream = self._want_stream(stream, dev)
+        rec = torch.zeros((n, L.REC_WORDS), dtype=torch.int32, device=dev)
+        if n == 0:
+            return rec, torch.zeros(0, dtype=torch.int64, device=dev)
+        # CIGAR ops are merged runs: the host entry's first guess of (n + m) / 4 + 8 per pair
+        ops_cap = (int(q_len.sum(dtype=torch.int64)) + int(t_len.sum(dtype=torch.int64))) // 4 + 8 * n + 1024
+        prm = self._params()
+        lib = L.lib()
+        for _attempt in range(6):
+            ops = torch.zeros(ops_cap, dtype=torch.int64, device=dev)
+            self._order_after_torch(stream, dev)  # (the fills above ran on torch's current stream)
+            needed = C.c_uint64(0)
+            ins = (blob.data_ptr(), blob.numel(), q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n, 0)
+            if int(max_score):
+                rc = lib.wfahip_align_batch_bounded_device(self._ctx, C.byref(prm), *ins, int(max_score), rec.data_ptr(), ops.data_ptr(),
+                                                           ops_cap, C.byref(needed), stream.cuda_stream)
+            else:
+                rc = lib.wfahip_align_batch_device(self._ctx, C.byref(prm), *ins, rec.data_ptr(), ops.data_ptr(), ops_cap,
+                                                   C.byref(needed), stream.cuda_stream)
+            if rc == L.ERR_OOM and needed.value > ops_cap:
+                ops_cap = needed.value + needed.value // 3 + 1024
+                continue
+            break
+        L.check(rc, "wfahip_align_batch_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return rec, ops
+
+    def cigar_tensors(self, rec, ops, only_aligned: bool = False, out=None, stream=None):
+        """AlignmentResult.CIGAR(only_aligned) of every pair of (rec, ops) -- align_tensors' output, or any records and ops of that
+        layout on the aligner's GPU -- rendered there (include/wfa_hip.h: wfahip_cigar_text_device): returns (text uint8,
+        off int64 [n + 1]); pair i's text is text[off[i]:off[i + 1]], without terminators, and off[n] the total.  A pair that is not
+        OK renders the empty string, and so does, under only_aligned, a pair without an M op.  out=None: the text is sized by one
+        call and written by a second, and has exactly off[n] bytes.  out=(text, off): contiguous tensors on that device, off of at
+        least n + 1 elements, text of any size -- bytes at and beyond off[n] keep their contents; a text tensor that is too small
+        raises WfaHipError (ERR_OOM) with off filled, so that off[n] says what is needed.  rec and ops are never written.  stream
+        and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        n = int(rec.shape[0])
+        if out is not None:
+            try:
+                text, off = out
+            except (TypeError, ValueError):
+                raise ValueError("out must be a pair (text, off) of tensors") from None
+            self._want_tensor("out text", text, torch.uint8, dev), self._want_tensor("out off", off, torch.int64, dev)
+            if off.numel() < n + 1:
+                raise ValueError(f"out off must hold at least {n + 1} elements")
+        stream = self._want_stream(stream, dev)
+        if out is None:
+            off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        self._order_after_torch(stream, dev)  # (the fill above, and whatever made rec and ops, ran on torch's current stream)
+        if n == 0:
+            if out is not None:
+                off[:1] = 0
+            return (torch.zeros(0, dtype=torch.uint8, device=dev) if out is None else text), off
+        lib = L.lib()
+        needed = C.c_uint64(0)
+
+        def call(t):
+            return lib.wfahip_cigar_text_device(self._ctx, rec.data_ptr(), ops.data_ptr() if ops.numel() else None, ops.numel(), n,
+                                                1 if only_aligned else 0, t.data_ptr() if t is not None and t.numel() else None,
+                                                t.numel() if t is not None else 0, off.data_ptr(), C.byref(needed), stream.cuda_stream)
+        if out is None:
+            rc = call(None)  # the sizing call
+            if rc == L.ERR_OOM:
+                text = torch.empty(needed.value, dtype=torch.uint8, device=dev)
+                rc = call(text)
+            elif rc == L.OK:
+                text = torch.zeros(0, dtype=torch.uint8, device=dev)
+        else:
+            rc = call(text)
+        L.check(rc, "wfahip_cigar_text_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return text, off
+
+    def align_arrays_text(self, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False):
+        """align_arrays with the CIGARs as text in place of the ops (include/wfa_hip.h: wfahip_align_batch_text): returns
+        (BatchResult, text np.uint8, off np.uint64 [n + 1]).  Every field of the BatchResult equals align_arrays' except that
+        ops_off is all 0 and ops is empty -- no op crosses PCIe; pair i's CIGAR(only_aligned) is text[off[i]:off[i + 1]].  The plain
+        path: no sliced upload, no autopack (the header says when that matters)."""
+        n = int(len(q_len))
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+        for name, a in (("blob", blob), ("q_off", q_off), ("q_len", q_len), ("t_off", t_off), ("t_len", t_len)):
+            if a.ndim != 1:
+                raise ValueError(f"{name} must be one-dimensional")
+        if len(q_off) != n or len(t_off) != n or len(t_len) != n:
+            raise ValueError("offset and length arrays differ in length")
+        res, cig = L.Results(), L.Cigars()
+        prm = self._params()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        L.check(L.lib().wfahip_align_batch_text(self._ctx, C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len),
+                                                n, 1 if only_aligned else 0, C.byref(res), C.byref(cig)), "wfahip_align_batch_text")
+        try:
+            text, off = _take_cigars(cig)
+        finally:
+            L.lib().wfahip_cigars_free(C.byref(cig))
+        return _take_results(res, n), text, off
+
     # -- new: score matrix (include/wfa_hip.h: wfahip_score_matrix) ------------------------------------
     def score_matrix_arrays(self, blob, q_off, q_len, t_off, t_len, max_score: int = 0, out=None, q_rc=None):
         """(status: np.int32[n_q, n_t], score: np.uint32[n_q, n_t]) of every query against every target: cell (i, j) is what
@@ -693,6 +854,43 @@ def _take_results(res: "L.Results", n: int) -> "BatchResult":
         return BatchResult.from_c(res, n)
     finally:
         L.lib().wfahip_results_free(C.byref(res))
+
+
+def _take_cigars(cig: "L.Cigars"):
+    """numpy copies (text uint8 [n_bytes], off uint64 [n + 1]) of a wfahip_cigars, which stays the caller's to free"""
+    n, nb = int(cig.n), int(cig.n_bytes)
+    text = np.ctypeslib.as_array(cig.text, shape=(nb,)).copy() if nb else np.zeros(0, dtype=np.uint8)
+    off = np.ctypeslib.as_array(cig.off, shape=(n + 1,)).copy() if cig.off else np.zeros(n + 1, dtype=np.uint64)
+    return text, off
+
+
+def cigar_text(batch_result: "BatchResult", only_aligned: bool = False, n_threads: int = 8):
+    """AlignmentResult.CIGAR(only_aligned) of every pair of a BatchResult as bytes, rendered by host threads (include/wfa_hip.h:
+    wfahip_cigar_text; no GPU, no Aligner): returns (text np.uint8, off np.uint64 [n + 1]); pair i's text is
+    text[off[i]:off[i + 1]], empty for a pair that is not OK and, under only_aligned, for one without an M op.  ValueError for
+    arrays of the wrong shape; WfaHipError (ERR_BAD_ARG) when an OK pair's ops lie outside batch_result.ops."""
+    br = batch_result
+    status = np.ascontiguousarray(br.status, dtype=np.int32)
+    ops_off = np.ascontiguousarray(br.ops_off, dtype=np.uint64)
+    ops_len = np.ascontiguousarray(br.ops_len, dtype=np.uint32)
+    ops = np.ascontiguousarray(br.ops, dtype=np.uint64)
+    n = int(status.size)
+    if status.ndim != 1 or ops.ndim != 1 or ops_off.shape != (n,) or ops_len.shape != (n,):
+        raise ValueError("status, ops_off and ops_len must be one-dimensional and of one length, ops one-dimensional")
+    if int(n_threads) < 1:
+        raise ValueError("n_threads must be at least 1")
+    res = L.Results()
+    res.n, res.n_ops = n, int(ops.size)
+    res.status = status.ctypes.data_as(C.POINTER(C.c_int32))
+    res.ops_off = ops_off.ctypes.data_as(C.POINTER(C.c_uint64))
+    res.ops_len = ops_len.ctypes.data_as(C.POINTER(C.c_uint32))
+    res.ops = ops.ctypes.data_as(C.POINTER(C.c_uint64))
+    cig = L.Cigars()
+    L.check(L.lib().wfahip_cigar_text(C.byref(res), 1 if only_aligned else 0, int(n_threads), C.byref(cig)), "wfahip_cigar_text")
+    try:
+        return _take_cigars(cig)
+    finally:
+        L.lib().wfahip_cigars_free(C.byref(cig))
 
 
 def _results_and_errors(br: "BatchResult"):
