@@ -435,6 +435,64 @@ int  wfahip_align_batch_text(wfahip_ctx *ctx, const wfahip_params *p, const uint
                              const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
                              uint64_t n_pairs, int only_aligned, wfahip_results *out, wfahip_cigars *cig);
 
+/* The display rows, rendered where the ops and the sequences are.  AlignmentResult.AlignmentText(q, t, onlyAlignedRegion)
+ * (wfa_cigar.go:259-333) of every pair of a batch: a query row, a row of bars and a target row of one length, one column per
+ * aligned or gapped base.  The rule (wfa_amd/csrc/wfa_altext.hpp, one source for the kernels and the host renderer): the count
+ * columns of an op are, in the three rows, M: query byte, '|', target byte; X: query byte, ' ', target byte; I: '-', ' ', target
+ * byte; D and H: query byte, ' ', '-'.  An op of any other letter has no column and consumes nothing, a count of 0 gives no
+ * column, and sequence bytes are copied verbatim, whatever they are.  only_aligned == 0 renders all ops over the whole sequences.
+ * only_aligned != 0 renders the ops from the first 'M' op to the last (as the CIGAR text does) over the windows the RECORD names,
+ * read as int32: query bytes [QBEGIN - 1, QEND) and target bytes [TBEGIN - 1, TEND); the bases of the trimmed-away ops are not
+ * summed.  A pair's rows are empty when its status is not WFAHIP_PAIR_OK, when OPS_LEN is 0 and, under only_aligned, when it has
+ * no 'M' op (where the reference would panic).
+ * Where the reference would index out of range the call fails, checked for every OK pair with an op that renders: its ops lie in
+ * [0, ops_cap) (the CIGAR entry's two compares); both sequences lie in [0, blob_bytes); trimmed, 1 <= BEGIN, BEGIN - 1 <= END and
+ * END <= the sequence's length, for both; the query and the target bases its ops consume, as 64-bit sums, do not exceed the
+ * window's length.  The library's results meet them with equality, with one exception that is the reference's own: under
+ * wf-adaptive its ops now and then consume one base more than both sequences hold (pair 61 309 of the 1 kbp benchmark batch ends
+ * ..5M1X3I over a query of 1 000 bases; the CPU oracle returns the same ops).  Untrimmed, a batch with such a pair is refused;
+ * trimmed it renders, the windows being the record's.  A caller sets the pair aside (scripts/alignment_text_bench.py does).
+ *
+ * wfahip_alignment_text_device: d_rec / d_ops as wfahip_align_batch_device (or _bounded_device) left them, or any records and ops
+ * of that layout; the blob and the four arrays (offsets u64, lengths u32) are the ones that call was given.  Only bytes inside the
+ * sequences are read: the blob needs NO readable bytes behind blob_bytes for this entry.  Every pointer is a device address on
+ * the context's GPU and stays the caller's.  Pair i's rows are d_q_row, d_a_row and d_t_row[d_row_off[i] .. d_row_off[i + 1]):
+ * three planes, one offset array (u64[n_pairs + 1], 8-byte aligned) that starts at 0 and ends at the total -- the bytes of ONE
+ * plane -- which *row_needed (if non-NULL) receives.  No byte of a plane at or beyond the total is written; no input is written.
+ * Planes that are all 4-byte aligned are written four columns to a store, others byte by byte.  row_cap (the capacity of each
+ * plane) below the total: WFAHIP_ERR_OOM with the planes untouched and d_row_off filled -- a caller sizes with null planes and
+ * row_cap = 0 and calls again.  A failed check of the paragraph above: WFAHIP_ERR_BAD_ARG with the planes untouched, before the
+ * kernel that reads ops or sequence bytes to write rows is launched (d_row_off then holds nothing of use).  WFAHIP_ERR_BAD_ARG
+ * before the context is dereferenced: a null ctx; with n_pairs > 0 a null d_rec, d_row_off, d_q_off, d_q_len, d_t_off or d_t_len;
+ * a null d_ops with ops_cap > 0; a null d_seq_blob with blob_bytes > 0; a null plane with row_cap > 0; n_pairs beyond 0xFFFFFFF0.
+ * n_pairs == 0 returns WFAHIP_OK with *row_needed = 0 and writes d_row_off[0] = 0 when d_row_off is non-null (the only case in
+ * which it touches the context or the device).  stream = hipStream_t (NULL = the context's own).  Synchronous.  wfahip_last_timing
+ * is not touched.
+ * Three passes (wfa_cigar.hip): wfa_altext_len_kernel, a wave per pair -- the range from ballots, the columns and the bases as
+ * three 64-bit sums, the checks; the CIGAR entry's scan, in place in d_row_off; wfa_altext_write_kernel, a wave per pair in rounds
+ * of 64 ops, the round's starts in LDS, the lanes sweeping the round's columns four to a lane (KERNELS.md 4q).  Scratch lives in
+ * the context; one fetch of 64 bytes of counters per call crosses PCIe.  1e6 x 1 kbp pairs, 3 x 1 014 bytes each: 4.5 ms for the
+ * three passes (1.04 s for wfahip_alignment_text on 16 host threads).  WFAHIP_DEBUG_TIMING=1 prints the passes' times to stderr. */
+int  wfahip_alignment_text_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                  const void *d_seq_blob, uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
+                                  const void *d_t_off, const void *d_t_len, uint64_t n_pairs, int only_aligned,
+                                  void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap,
+                                  void *d_row_off /* u64[n_pairs + 1] */, uint64_t *row_needed, void *stream);
+
+/* Host only, no device, no context: the same bytes and offsets for a wfahip_results in host memory and the blob and arrays it was
+ * aligned from (n_threads host threads over contiguous ranges of pairs, the same header functions as the kernels).  The trimmed
+ * windows are r->qbegin / qend / tbegin / tend.  out->q_row, a_row and t_row hold n_bytes bytes each (NULL when n_bytes == 0),
+ * out->off n + 1 offsets, off[0] = 0 and off[n] = n_bytes; all are malloc'd and released with wfahip_align_texts_free.  r->n == 0
+ * gives n = n_bytes = 0, null rows and off pointing at one 0.  WFAHIP_ERR_BAD_ARG (out zeroed, when there is one): a null r or
+ * out; with r->n > 0 a null status, ops_off, ops_len, offset or length array, and under only_aligned a null qbegin, qend, tbegin
+ * or tend; a null ops with n_ops > 0; a null seq_blob with blob_bytes > 0; a pair that fails a check of the device entry (with
+ * n_ops as ops_cap). */
+typedef struct { uint64_t n, n_bytes; char *q_row, *a_row, *t_row; uint64_t *off; /* n + 1 */ } wfahip_align_texts;
+int  wfahip_alignment_text(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                           const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, int only_aligned,
+                           int n_threads, wfahip_align_texts *out);
+void wfahip_align_texts_free(wfahip_align_texts *t);
+
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns
  * at once with the pair's ticket (0, 1, 2, ... since the last collect) -- and collects all results with ONE batch

@@ -7,5 +7,5 @@ from .aligner import (  # noqa: F401
     AdaptiveReductionOption, Aligner, AlignmentResult, MultiAligner, pack_pairs, generate_pairs_device, BatchResult, DefaultAdaptiveOption, DefaultOptions,
     DefaultPenalties, ErrEmptySeq, ErrOverMaxScore, ErrSeqTooLong, MaskLower32, MaxSeqLen, New, Op, OpD, OpH, OpI, OpM, OpX,
     Options, Penalties, RecycleAligner, RecycleAlignmentResult, RecycleAlignmentText, WfaError, generate_pairs,
-    make_blob, plot_component, trimOps, wide_class_bounds, revcomp_packed, best_strand, cigar_text,
+    make_blob, plot_component, trimOps, wide_class_bounds, revcomp_packed, best_strand, cigar_text, alignment_text,
 )

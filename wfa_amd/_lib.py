@@ -32,6 +32,7 @@ EXPORTS = [
     "wfahip_wide_class_bounds", "wfahip_debug_wide_plan",
     "wfahip_score_batch_packed_rc", "wfahip_score_matrix_rc", "wfahip_revcomp_packed",
     "wfahip_cigar_text_device", "wfahip_cigar_text", "wfahip_cigars_free", "wfahip_align_batch_text",
+    "wfahip_alignment_text_device", "wfahip_alignment_text", "wfahip_align_texts_free",
 ]
 
 
@@ -58,6 +59,12 @@ class Scores(C.Structure):
 class Cigars(C.Structure):
     """wfahip_cigars: pair i's CIGAR text is text[off[i] .. off[i + 1])"""
     _fields_ = [("n", C.c_uint64), ("n_bytes", C.c_uint64), ("text", C.POINTER(C.c_uint8)), ("off", C.POINTER(C.c_uint64))]
+
+
+class AlignTexts(C.Structure):
+    """wfahip_align_texts: pair i's rows are q_row, a_row and t_row[off[i] .. off[i + 1])"""
+    _fields_ = [("n", C.c_uint64), ("n_bytes", C.c_uint64), ("q_row", C.POINTER(C.c_uint8)), ("a_row", C.POINTER(C.c_uint8)),
+                ("t_row", C.POINTER(C.c_uint8)), ("off", C.POINTER(C.c_uint64))]
 
 
 class Timing(C.Structure):
@@ -136,6 +143,12 @@ def lib():
         L.wfahip_align_batch_text.restype = C.c_int
         L.wfahip_align_batch_text.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, C.c_int, C.POINTER(Results),
                                               C.POINTER(Cigars)]
+        L.wfahip_alignment_text_device.restype = C.c_int
+        L.wfahip_alignment_text_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, u64, vp,
+                                                   C.POINTER(u64), vp]
+        L.wfahip_alignment_text.restype = C.c_int
+        L.wfahip_alignment_text.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(AlignTexts)]
+        L.wfahip_align_texts_free.argtypes = [C.POINTER(AlignTexts)]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

@@ -593,6 +593,73 @@ class Aligner:
         L.check(rc, "wfahip_cigar_text_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return text, off
 
+    def alignment_text_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, out=None, stream=None):
+        """AlignmentResult.AlignmentText(q, t, only_aligned) of every pair of (rec, ops) -- align_tensors' output -- over the blob
+        and the four tensors that call was given, rendered on the aligner's GPU (include/wfa_hip.h: wfahip_alignment_text_device):
+        returns (q_row uint8, a_row uint8, t_row uint8, off int64 [n + 1]); pair i's three rows are the planes' [off[i]:off[i + 1]],
+        and off[n] is the length of each plane.  A pair that is not OK has empty rows, and so has, under only_aligned, a pair
+        without an M op.  out=None: the planes are sized by one call and written by a second, and have exactly off[n] bytes.
+        out=(q_row, a_row, t_row, off): contiguous tensors on that device, off of at least n + 1 elements, the planes of any one
+        size -- bytes at and beyond off[n] keep their contents; planes that are too small raise WfaHipError (ERR_OOM) with off
+        filled.  A record whose ops or windows leave the op buffer or the sequences raises WfaHipError (ERR_BAD_ARG) and writes
+        no row.  No input is written.  stream and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        self._want_tensor("blob", blob, torch.uint8, dev)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(rec.shape[0])
+        if q_off.numel() != n or q_len.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors must hold one element per record")
+        if out is not None:
+            try:
+                q_row, a_row, t_row, off = out
+            except (TypeError, ValueError):
+                raise ValueError("out must be (q_row, a_row, t_row, off), four tensors") from None
+            for name, t in (("out q_row", q_row), ("out a_row", a_row), ("out t_row", t_row)):
+                self._want_tensor(name, t, torch.uint8, dev)
+            self._want_tensor("out off", off, torch.int64, dev)
+            if not q_row.numel() == a_row.numel() == t_row.numel():
+                raise ValueError("out q_row, a_row and t_row must be of one size")
+            if off.numel() < n + 1:
+                raise ValueError(f"out off must hold at least {n + 1} elements")
+        stream = self._want_stream(stream, dev)
+        if out is None:
+            off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        self._order_after_torch(stream, dev)  # (the fill above, and whatever made the inputs, ran on torch's current stream)
+        empty = lambda: torch.zeros(0, dtype=torch.uint8, device=dev)
+        if n == 0:
+            if out is not None:
+                off[:1] = 0
+                return q_row, a_row, t_row, off
+            return empty(), empty(), empty(), off
+        lib = L.lib()
+        needed = C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+
+        def call(planes):
+            cap = planes[0].numel() if planes else 0
+            rows = [ptr(p) for p in planes] if cap else [None] * 3
+            return lib.wfahip_alignment_text_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(blob), blob.numel(),
+                                                    q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n,
+                                                    1 if only_aligned else 0, *rows, cap, off.data_ptr(), C.byref(needed),
+                                                    stream.cuda_stream)
+        if out is None:
+            rc = call(None)  # the sizing call
+            if rc == L.ERR_OOM:
+                q_row, a_row, t_row = (torch.empty(needed.value, dtype=torch.uint8, device=dev) for _ in range(3))
+                rc = call((q_row, a_row, t_row))
+            elif rc == L.OK:
+                q_row, a_row, t_row = empty(), empty(), empty()
+        else:
+            rc = call((q_row, a_row, t_row))
+        L.check(rc, "wfahip_alignment_text_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return q_row, a_row, t_row, off
+
     def align_arrays_text(self, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False):
         """align_arrays with the CIGARs as text in place of the ops (include/wfa_hip.h: wfahip_align_batch_text): returns
         (BatchResult, text np.uint8, off np.uint64 [n + 1]).  Every field of the BatchResult equals align_arrays' except that
@@ -891,6 +958,50 @@ def cigar_text(batch_result: "BatchResult", only_aligned: bool = False, n_thread
         return _take_cigars(cig)
     finally:
         L.lib().wfahip_cigars_free(C.byref(cig))
+
+
+def alignment_text(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, n_threads: int = 8):
+    """AlignmentResult.AlignmentText(q, t, only_aligned) of every pair of a BatchResult over the blob and arrays it was aligned from,
+    rendered by host threads (include/wfa_hip.h: wfahip_alignment_text; no GPU, no Aligner): returns (q_row np.uint8, a_row
+    np.uint8, t_row np.uint8, off np.uint64 [n + 1]); pair i's rows are the three arrays' [off[i]:off[i + 1]], empty for a pair
+    that is not OK and, under only_aligned, for one without an M op.  ValueError for arrays of the wrong shape; WfaHipError
+    (ERR_BAD_ARG) when an OK pair's ops lie outside batch_result.ops, or its ops or windows leave the sequences."""
+    br = batch_result
+    status = np.ascontiguousarray(br.status, dtype=np.int32)
+    ops_off = np.ascontiguousarray(br.ops_off, dtype=np.uint64)
+    ops_len = np.ascontiguousarray(br.ops_len, dtype=np.uint32)
+    ops = np.ascontiguousarray(br.ops, dtype=np.uint64)
+    windows = [np.ascontiguousarray(getattr(br, f), dtype=np.int32) for f in ("qbegin", "qend", "tbegin", "tend")]
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+    n = int(status.size)
+    if status.ndim != 1 or ops.ndim != 1 or blob.ndim != 1:
+        raise ValueError("status, ops and blob must be one-dimensional")
+    if any(a.shape != (n,) for a in [ops_off, ops_len, q_off, q_len, t_off, t_len] + windows):
+        raise ValueError("ops_off, ops_len, qbegin, qend, tbegin, tend and the offset and length arrays must hold one element per pair")
+    if int(n_threads) < 1:
+        raise ValueError("n_threads must be at least 1")
+    res = L.Results()
+    res.n, res.n_ops = n, int(ops.size)
+    res.status = status.ctypes.data_as(C.POINTER(C.c_int32))
+    res.ops_off = ops_off.ctypes.data_as(C.POINTER(C.c_uint64))
+    res.ops_len = ops_len.ctypes.data_as(C.POINTER(C.c_uint32))
+    res.ops = ops.ctypes.data_as(C.POINTER(C.c_uint64))
+    res.qbegin, res.qend, res.tbegin, res.tend = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in windows)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    txt = L.AlignTexts()
+    L.check(L.lib().wfahip_alignment_text(C.byref(res), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len),
+                                          1 if only_aligned else 0, int(n_threads), C.byref(txt)), "wfahip_alignment_text")
+    try:
+        nb = int(txt.n_bytes)
+        rows = [np.ctypeslib.as_array(p, shape=(nb,)).copy() if nb else np.zeros(0, dtype=np.uint8) for p in (txt.q_row, txt.a_row, txt.t_row)]
+        off = np.ctypeslib.as_array(txt.off, shape=(n + 1,)).copy()
+    finally:
+        L.lib().wfahip_align_texts_free(C.byref(txt))
+    return rows[0], rows[1], rows[2], off
 
 
 def _results_and_errors(br: "BatchResult"):

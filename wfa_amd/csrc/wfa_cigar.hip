@@ -12,9 +12,15 @@
 //                           places it, the round's total is carried into the next round.  The bytes go straight to global memory.
 //                           (A round staged in LDS and stored as aligned dwords measured 9 % slower: KERNELS.md 4p.)
 // The host learns two numbers per call -- the total and whether a record points outside the op buffer -- from one 64-byte fetch.
+//
+// The display rows of AlignmentResult.AlignmentText (wfahip_alignment_text_device, wfahip_alignment_text; the rule is
+// wfa_altext.hpp's) are the same three passes with the same scan kernels: wfa_altext_len_kernel adds the columns and the bases a
+// pair's ops consume and checks them against the windows of its sequences, wfa_altext_write_kernel expands the runs -- a wave per
+// pair in rounds of 64 ops, the round's table of starts in LDS, the lanes sweeping the round's columns four to a lane.
 #include "wfa_ctx.hpp"
 #include "wfa_hostpack.hpp"
 #include "wfa_cigar.hpp"
+#include "wfa_altext.hpp"
 
 using namespace wfa;
 
@@ -22,7 +28,7 @@ namespace {
 
 constexpr int CIG_SCAN_BLOCK = 1024, CIG_SCAN_ITEMS = 4;  // scan: pairs per block = CIG_SCAN_BLOCK * CIG_SCAN_ITEMS
 constexpr uint64_t CIG_PER_BLOCK = (uint64_t)CIG_SCAN_BLOCK * CIG_SCAN_ITEMS;
-constexpr int CIG_CTL_WORDS = 8;  // u64 counters, one 64-byte fetch: [0] total bytes [1] != 0: an OK record's ops leave the op buffer
+constexpr int CIG_CTL_WORDS = 8;  // u64 counters, one 64-byte fetch: [0] total bytes [1] != 0: an OK record's ops leave the op buffer (the rows: or fail another check)
 enum { CIG_TOTAL = 0, CIG_BAD_RANGE = 1 };
 static_assert(CIG_CTL_WORDS * 8 <= HPIN_REDO * 4, "the counters fit the head of the pinned block");
 
@@ -38,13 +44,23 @@ struct CigParams {
     unsigned long long *ctl;   // [CIG_CTL_WORDS]
 };
 
+// the display rows: C's text_off is the rows' offset array (text is not used), CIG_BAD_RANGE is raised by every failed check
+struct AltParams {
+    CigParams       C;
+    const uint8_t  *blob;
+    uint64_t        blob_bytes;
+    const uint64_t *q_off, *t_off;  // [n]
+    const uint32_t *q_len, *t_len;  // [n]
+    uint8_t        *q_row, *a_row, *t_row;
+    uint32_t        dwords;  // != 0: the three planes are 4-byte aligned, four columns go out as one store
+};
+
 }  // namespace
 
-// pass 1: the range of each pair's ops that renders and the bytes of its text
-__global__ __launch_bounds__(256) void wfa_cigar_len_kernel(const CigParams C) {
-    const uint64_t i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    if (i >= C.n) return;
+// a wave's pair: the ops [*first, *end) of its *ops that render (under only_aligned the first to the last 'M' op, from ballots;
+// none without one).  An OK record whose ops leave the op buffer raises CIG_BAD_RANGE and renders nothing.
+__device__ __forceinline__ void cig_wave_range(const CigParams &C, uint64_t i, uint32_t lane, const uint64_t **ops_out, uint32_t *first_out,
+                                               uint32_t *end_out) {
     const uint32_t *r   = C.rec + i * REC_WORDS;
     uint32_t        len = r[REC_STATUS] == ST_OK ? r[REC_OPS_LEN] : 0u;  // (fin_len's rule: a failed pair's record may hold stale words)
     const uint64_t  src = (uint64_t)r[REC_OPS_OFF_LO] | ((uint64_t)r[REC_OPS_OFF_HI] << 32);
@@ -66,6 +82,17 @@ __global__ __launch_bounds__(256) void wfa_cigar_len_kernel(const CigParams C) {
         }
         if (end == 0u) first = 0u;  // no 'M' op: nothing renders
     }
+    *ops_out = ops, *first_out = first, *end_out = end;
+}
+
+// pass 1: the range of each pair's ops that renders and the bytes of its text
+__global__ __launch_bounds__(256) void wfa_cigar_len_kernel(const CigParams C) {
+    const uint64_t i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (i >= C.n) return;
+    const uint64_t *ops;
+    uint32_t        first, end;
+    cig_wave_range(C, i, lane, &ops, &first, &end);
     unsigned long long bytes = 0ull;
     for (uint32_t k = first + lane; k < end; k += 64u) bytes += cig_op_bytes(ops[k]);
 #pragma unroll
@@ -162,12 +189,152 @@ __global__ __launch_bounds__(256) void wfa_cigar_write_kernel(const CigParams C)
     }
 }
 
+// ---- the display rows (wfa_altext.hpp)
+
+// the windows of pair i's sequences, from its record and the caller's four arrays
+__device__ __forceinline__ bool alt_pair_window(const AltParams &A, uint64_t i, AltWindow *w) {
+    const uint32_t *r = A.C.rec + i * REC_WORDS;
+    return alt_window(A.C.only_aligned != 0u, A.blob_bytes, A.q_off[i], A.q_len[i], A.t_off[i], A.t_len[i], (int32_t)r[REC_QBEGIN],
+                      (int32_t)r[REC_QEND], (int32_t)r[REC_TBEGIN], (int32_t)r[REC_TEND], w);
+}
+
+__device__ __forceinline__ uint32_t alt_load4(const uint8_t *p) {  // four bytes at any alignment
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
+// rows, pass 1: the range of each pair's ops that renders, its columns, and every check that keeps pass 3 inside the op buffer,
+// the blob and the windows.  A pair that fails one raises CIG_BAD_RANGE; pass 3 is then not launched.
+__global__ __launch_bounds__(256) void wfa_altext_len_kernel(const AltParams A) {
+    const CigParams &C    = A.C;
+    const uint64_t   i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t   lane = threadIdx.x & 63;
+    if (i >= C.n) return;
+    const uint64_t *ops;
+    uint32_t        first, end;
+    cig_wave_range(C, i, lane, &ops, &first, &end);
+    AltSums s = {0, 0, 0};
+    for (uint32_t k = first + lane; k < end; k += 64u) alt_add(&s, ops[k]);
+    unsigned long long cols = s.cols, qb = s.q, tb = s.t;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cols += __shfl_xor(cols, o, 64);
+        qb += __shfl_xor(qb, o, 64);
+        tb += __shfl_xor(tb, o, 64);
+    }
+    if (lane == 0) {
+        uint32_t count = end - first;
+        if (count != 0u) {
+            const AltSums all = {cols, qb, tb};
+            AltWindow     w;
+            if (!alt_pair_window(A, i, &w) || !alt_fits(all, w)) {
+                atomicOr(&C.ctl[CIG_BAD_RANGE], 1ull);
+                cols = 0ull;
+            }
+        }
+        if (cols == 0ull) count = 0u;  // (ops without a column: pass 3 has nothing to do)
+        C.text_off[i] = cols;
+        C.range[i]    = make_uint2(first, count);
+    }
+}
+
+// rows, pass 3.  A round is 64 ops: a wave prefix sum gives every op its first column of the round and its first query and target
+// byte of the windows, and the table goes to the wave's LDS.  The lanes then sweep the round's columns in groups of four that are
+// aligned in the PLANE (not in the pair), consecutive lanes taking consecutive groups: a lane finds the op of its first column by a
+// search over the 64 starts and walks on from there.  A group inside one op -- most of them -- is one 4-byte load per sequence
+// and, where the planes are 4-byte aligned, one 4-byte store per plane; a group that crosses an op boundary gathers byte by byte;
+// a group cut by the round's first or last column stores bytes, and the next round stores the rest of it.
+__global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A) {
+    __shared__ unsigned long long s_col[4][64];                      // first column of the op, in the round
+    __shared__ uint32_t           s_q[4][64], s_t[4][64], s_kind[4][64];  // first query / target byte in the windows; alt_kind | a byte << 8
+    const CigParams &C    = A.C;
+    const uint32_t   wv   = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t   i    = (uint64_t)blockIdx.x * 4 + wv;
+    if (i >= C.n) return;
+    const uint2 rg = C.range[i];
+    if (rg.y == 0u) return;
+    AltWindow w;
+    (void)alt_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+    const uint32_t *r   = C.rec + i * REC_WORDS;
+    const uint64_t *ops = C.ops + ((uint64_t)r[REC_OPS_OFF_LO] | ((uint64_t)r[REC_OPS_OFF_HI] << 32)) + rg.x;
+    const uint8_t  *qs = A.blob + w.q_at, *ts = A.blob + w.t_at;
+    uint64_t        g0 = C.text_off[i];  // the round's first column, as an index into the planes
+    uint32_t        qc = 0u, tc = 0u;    // bases the rounds before consumed (pass 1: at most the windows' lengths)
+    for (uint32_t b = 0; b < rg.y; b += 64u) {
+        const uint64_t     op   = b + lane < rg.y ? ops[b + lane] : 0ull;  // (letter 0: no column)
+        const uint32_t     kind = alt_kind(op), cnt = alt_cols(op);
+        const uint32_t     myq = (kind & ALT_Q) ? cnt : 0u, myt = (kind & ALT_T) ? cnt : 0u;
+        unsigned long long ci = cnt;  // (64 counts of a full u32 each)
+        uint32_t           qi = myq, ti = myt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long c2 = __shfl_up(ci, o, 64);
+            const uint32_t           q2 = __shfl_up(qi, o, 64), t2 = __shfl_up(ti, o, 64);
+            if (lane >= (uint32_t)o) ci += c2, qi += q2, ti += t2;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the round before has read its table)
+        __builtin_amdgcn_wave_barrier();
+        s_col[wv][lane]  = ci - cnt;
+        s_q[wv][lane]    = qc + qi - myq;
+        s_t[wv][lane]    = tc + ti - myt;
+        s_kind[wv][lane] = kind | ((uint32_t)alt_a_byte(op) << 8);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const unsigned long long R    = __shfl(ci, 63, 64);  // the round's columns
+        const uint64_t           gend = g0 + R;
+        for (uint64_t g = (g0 & ~3ull) + 4u * lane; g < gend; g += 256u) {
+            const uint64_t lo = g > g0 ? g : g0, hi = g + 4u < gend ? g + 4u : gend;  // the group's columns of this round: lo < hi
+            const uint32_t j0 = (uint32_t)(lo - g), j1 = (uint32_t)(hi - g);
+            unsigned long long c = lo - g0;  // column in the round, < R
+            uint32_t           k = 0u;       // the last op whose first column is <= c: the one with a column there
+#pragma unroll
+            for (uint32_t step = 32u; step != 0u; step >>= 1)
+                if (s_col[wv][k + step] <= c) k += step;
+            unsigned long long cs = s_col[wv][k], ce = k < 63u ? s_col[wv][k + 1u] : R;
+            uint32_t           kd = s_kind[wv][k], qb = s_q[wv][k], tb = s_t[wv][k];
+            uint32_t           qv = 0u, av = 0u, tv = 0u;  // the group's bytes, column g + j in bits 8 j ..
+            if (j1 - j0 == 4u && c + 4u <= ce) {
+                const uint64_t d = c - cs;
+                qv = (kd & ALT_Q) ? alt_load4(qs + (uint64_t)qb + d) : ALT_GAP * 0x01010101u;
+                tv = (kd & ALT_T) ? alt_load4(ts + (uint64_t)tb + d) : ALT_GAP * 0x01010101u;
+                av = (kd >> 8) * 0x01010101u;
+            } else {
+                for (uint32_t j = j0; j < j1; j++, c++) {
+                    if (c >= ce) {
+                        do {  // (ops without a column have cs == ce; c < R ends the walk at op 63 at the latest)
+                            k++;
+                            cs = ce, ce = k < 63u ? s_col[wv][k + 1u] : R;
+                        } while (c >= ce);
+                        kd = s_kind[wv][k], qb = s_q[wv][k], tb = s_t[wv][k];
+                    }
+                    const uint64_t d  = c - cs;
+                    const uint32_t qx = (kd & ALT_Q) ? qs[(uint64_t)qb + d] : ALT_GAP, tx = (kd & ALT_T) ? ts[(uint64_t)tb + d] : ALT_GAP;
+                    qv |= qx << (8u * j), av |= (kd >> 8) << (8u * j), tv |= tx << (8u * j);
+                }
+            }
+            if (j1 - j0 == 4u && A.dwords != 0u) {
+                *reinterpret_cast<uint32_t *>(A.q_row + g) = qv;
+                *reinterpret_cast<uint32_t *>(A.a_row + g) = av;
+                *reinterpret_cast<uint32_t *>(A.t_row + g) = tv;
+            } else {
+                for (uint32_t j = j0; j < j1; j++) {
+                    A.q_row[g + j] = (uint8_t)(qv >> (8u * j));
+                    A.a_row[g + j] = (uint8_t)(av >> (8u * j));
+                    A.t_row[g + j] = (uint8_t)(tv >> (8u * j));
+                }
+            }
+        }
+        g0 = gend;
+        qc += __shfl(qi, 63, 64), tc += __shfl(ti, 63, 64);
+    }
+}
+
 namespace {
 
-// the three passes on stream st.  Returns WFAHIP_OK with *total set and the text written; WFAHIP_ERR_OOM (total > text_cap) with
-// *total set, the offsets filled and no text byte written; WFAHIP_ERR_BAD_ARG when an OK record's ops leave the op buffer.
-int cigar_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n, int only_aligned, void *d_text,
-                      uint64_t text_cap, void *d_text_off, uint64_t *total, hipStream_t st) {
+// what every pass of a call shares, its scratch in ctx->cig included
+int cig_params(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n, int only_aligned, void *d_off,
+               CigParams *out) {
     const uint32_t n_blocks = (uint32_t)((n + CIG_PER_BLOCK - 1) / CIG_PER_BLOCK);
     // layout of ctx->cig (bytes): counters | blk_sum[n_blocks] | range[n]
     const uint64_t o_blk = CIG_CTL_WORDS * 8, o_rng = o_blk + 8ull * n_blocks;
@@ -177,9 +344,21 @@ int cigar_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uin
     CigParams   C{};
     C.rec = static_cast<const uint32_t *>(d_rec), C.ops = static_cast<const uint64_t *>(d_ops), C.ops_cap = ops_cap, C.n = n;
     C.only_aligned = only_aligned ? 1u : 0u;
-    C.text_off = static_cast<uint64_t *>(d_text_off), C.text = static_cast<uint8_t *>(d_text);
+    C.text_off = static_cast<uint64_t *>(d_off);
     C.ctl = reinterpret_cast<unsigned long long *>(sb), C.blk_sum = reinterpret_cast<uint64_t *>(sb + o_blk);
     C.range = reinterpret_cast<uint2 *>(sb + o_rng);
+    *out = C;
+    return WFAHIP_OK;
+}
+
+// the three passes on stream st: len(grid) launches the length kernel of a wave per pair, write(grid) the one that writes.
+// Returns WFAHIP_OK with *total set and the bytes written; WFAHIP_ERR_OOM (total > cap) with *total set, the offsets filled and no
+// byte written; WFAHIP_ERR_BAD_ARG when the length kernel raised CIG_BAD_RANGE, no byte written either.
+template <class Len, class Write>
+int cig_passes(wfahip_ctx *ctx, const CigParams &C, uint64_t cap, uint64_t *total, hipStream_t st, const char *what, Len &&len,
+               Write &&write) {
+    const uint64_t n         = C.n;
+    const uint32_t n_blocks  = (uint32_t)((n + CIG_PER_BLOCK - 1) / CIG_PER_BLOCK);
     const uint32_t pair_grid = (uint32_t)((n + 3) / 4);
     // WFAHIP_DEBUG_TIMING=1 (diagnostics, as in the host entry): the passes' hipEvent times on stderr
     struct Stamps {
@@ -200,7 +379,7 @@ int cigar_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uin
     stamps.on = std::getenv("WFAHIP_DEBUG_TIMING") != nullptr;
     HIP_TRY(hipMemsetAsync(C.ctl, 0, CIG_CTL_WORDS * 8, st));
     stamps.mark(0, st);
-    hipLaunchKernelGGL(wfa_cigar_len_kernel, dim3(pair_grid), dim3(256), 0, st, C);
+    len(pair_grid);
     stamps.mark(1, st);
     hipLaunchKernelGGL(wfa_cigar_scan_blocks, dim3(n_blocks), dim3(CIG_SCAN_BLOCK), 0, st, C);
     hipLaunchKernelGGL(wfa_cigar_scan_sums, dim3(1), dim3(1024), 0, st, C, n_blocks);
@@ -214,17 +393,71 @@ int cigar_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uin
     std::memcpy(hc, ctx->hpin + HPIN_CTRL, sizeof hc);
     if (hc[CIG_BAD_RANGE] != 0) return WFAHIP_ERR_BAD_ARG;
     *total = hc[CIG_TOTAL];
-    if (hc[CIG_TOTAL] > text_cap) return WFAHIP_ERR_OOM;
+    if (hc[CIG_TOTAL] > cap) return WFAHIP_ERR_OOM;
     if (hc[CIG_TOTAL] == 0) return WFAHIP_OK;
     stamps.mark(3, st);
-    hipLaunchKernelGGL(wfa_cigar_write_kernel, dim3(pair_grid), dim3(256), 0, st, C);
+    write(pair_grid);
     HIP_TRY(hipGetLastError());
     stamps.mark(4, st);
     HIP_TRY(hipStreamSynchronize(st));
     if (stamps.on)
-        std::fprintf(stderr, "[wfahip] cigar text: %llu pairs, %llu bytes: len %.4f ms, scan %.4f ms, write %.4f ms\n", (unsigned long long)n,
+        std::fprintf(stderr, "[wfahip] %s: %llu pairs, %llu bytes: len %.4f ms, scan %.4f ms, write %.4f ms\n", what, (unsigned long long)n,
                      (unsigned long long)hc[CIG_TOTAL], stamps.ms(0, 1), stamps.ms(1, 2), stamps.ms(3, 4));
     return WFAHIP_OK;
+}
+
+int cigar_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n, int only_aligned, void *d_text,
+                      uint64_t text_cap, void *d_text_off, uint64_t *total, hipStream_t st) {
+    CigParams C{};
+    const int rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, d_text_off, &C);
+    if (rc) return rc;
+    C.text = static_cast<uint8_t *>(d_text);
+    return cig_passes(
+        ctx, C, text_cap, total, st, "cigar text",
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_cigar_len_kernel, dim3(grid), dim3(256), 0, st, C); },
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_cigar_write_kernel, dim3(grid), dim3(256), 0, st, C); });
+}
+
+// the rows' three passes; the bytes of a call are those of ONE plane (the three hold the same number)
+int altext_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob, uint64_t blob_bytes,
+                       const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n, int only_aligned,
+                       void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *total, hipStream_t st) {
+    AltParams A{};
+    const int rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, d_row_off, &A.C);
+    if (rc) return rc;
+    A.blob = static_cast<const uint8_t *>(d_seq_blob), A.blob_bytes = blob_bytes;
+    A.q_off = static_cast<const uint64_t *>(d_q_off), A.t_off = static_cast<const uint64_t *>(d_t_off);
+    A.q_len = static_cast<const uint32_t *>(d_q_len), A.t_len = static_cast<const uint32_t *>(d_t_len);
+    A.q_row = static_cast<uint8_t *>(d_q_row), A.a_row = static_cast<uint8_t *>(d_a_row), A.t_row = static_cast<uint8_t *>(d_t_row);
+    A.dwords = ((reinterpret_cast<uintptr_t>(d_q_row) | reinterpret_cast<uintptr_t>(d_a_row) | reinterpret_cast<uintptr_t>(d_t_row)) & 3u) == 0u;
+    return cig_passes(
+        ctx, A.C, row_cap, total, st, "alignment text",
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_altext_len_kernel, dim3(grid), dim3(256), 0, st, A); },
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_altext_write_kernel, dim3(grid), dim3(256), 0, st, A); });
+}
+
+int altext_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob, uint64_t blob_bytes,
+                        const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n_pairs, int only_aligned,
+                        void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *row_needed,
+                        hipStream_t st) {
+    // (nothing in these checks dereferences the context)
+    if (!ctx || (n_pairs && (!d_rec || !d_row_off || !d_q_off || !d_q_len || !d_t_off || !d_t_len))) return WFAHIP_ERR_BAD_ARG;
+    if ((!d_ops && ops_cap) || (!d_seq_blob && blob_bytes) || ((!d_q_row || !d_a_row || !d_t_row) && row_cap)) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit: no entry leaves records of more pairs)
+    if (row_needed) *row_needed = 0;
+    if (n_pairs == 0 && !d_row_off) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    if (n_pairs == 0) {
+        HIP_TRY(hipMemsetAsync(d_row_off, 0, 8, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return WFAHIP_OK;
+    }
+    uint64_t  total = 0;
+    const int rc    = altext_device_impl(ctx, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs,
+                                         only_aligned, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, &total, st);
+    if (row_needed && (rc == WFAHIP_OK || rc == WFAHIP_ERR_OOM)) *row_needed = total;
+    return rc;
 }
 
 int cigar_text_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n_pairs, int only_aligned,
@@ -249,47 +482,42 @@ int cigar_text_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_op
 
 void cigars_zero(wfahip_cigars *c) { std::memset(c, 0, sizeof *c); }
 
-int cigar_text_host(const wfahip_results *r, int only_aligned, int n_threads, wfahip_cigars *out) {
-    if (out) cigars_zero(out);
-    if (!r || !out) return WFAHIP_ERR_BAD_ARG;
-    const uint64_t n = r->n;
-    if (n && (!r->status || !r->ops_off || !r->ops_len)) return WFAHIP_ERR_BAD_ARG;
-    if (!r->ops && r->n_ops) return WFAHIP_ERR_BAD_ARG;
+// the ops of pair i of host results that render: *count of them at *ops (none for a pair that is not OK).  false: an OK pair whose
+// ops leave [0, n_ops); none of them is read.
+bool host_pair_ops(const wfahip_results *r, uint64_t i, bool trim, const uint64_t **ops, uint32_t *count) {
+    *ops = nullptr, *count = 0u;
+    if (r->status[i] != WFAHIP_PAIR_OK) return true;
+    const uint32_t len = r->ops_len[i];
+    if (len > r->n_ops || r->ops_off[i] > r->n_ops - len) return false;  // (compared without a sum that could wrap)
+    if (len == 0u) return true;
+    uint32_t first;
+    cig_range(r->ops + r->ops_off[i], len, trim, &first, count);
+    *ops = r->ops + r->ops_off[i] + first;
+    return true;
+}
+
+// the host renderers' plan: n_threads threads over contiguous ranges of pairs, twice.  len(i, &bytes) gives the bytes of pair i
+// (false: the pair is invalid, the call WFAHIP_ERR_BAD_ARG); the ranges' sums give their bases; alloc(total) makes the output
+// (not called for a total of 0; false: WFAHIP_ERR_OOM); write(i, at) renders a pair with bytes at its offset.  *off_out is
+// malloc'd, n + 1 offsets; nothing is left allocated on an error.
+template <class Len, class Alloc, class Write>
+int host_render(uint64_t n, int n_threads, uint64_t **off_out, uint64_t *total_out, Len &&len, Alloc &&alloc, Write &&write) {
     if (n > (SIZE_MAX / 8) - 1) return WFAHIP_ERR_OOM;
     uint64_t *const off = static_cast<uint64_t *>(std::malloc((size_t)(n + 1) * 8));
     if (!off) return WFAHIP_ERR_OOM;
     off[n] = 0;
-    // threads over contiguous ranges of pairs: the lengths (kept in off[]) and each range's sum, then -- the bases of the ranges
-    // known -- the offsets and the text
     const unsigned        T   = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, n_threads), n));
     const uint64_t        per = T ? (n + T - 1) / T : 0;
     std::vector<uint64_t> part(T + 1, 0);
     std::atomic<int>      bad{0};
-    const bool            trim = only_aligned != 0;
-    const auto pair_ops = [&](uint64_t i, uint32_t *first, uint32_t *count) -> const uint64_t * {
-        const uint32_t len = r->status[i] == WFAHIP_PAIR_OK ? r->ops_len[i] : 0u;
-        if (len == 0u) {
-            *first = *count = 0u;
-            return nullptr;
-        }
-        const uint64_t *ops = r->ops + r->ops_off[i];
-        cig_range(ops, len, trim, first, count);
-        return ops + *first;
-    };
-    uint64_t *const part_p = part.data();
+    uint64_t *const       part_p = part.data();
     parallel_ranges(0, T, T, [&, part_p](uint64_t t0, uint64_t t1) {
         for (uint64_t t = t0; t < t1; t++) {
             const uint64_t a = std::min(n, t * per), b = std::min(n, a + per);
             uint64_t       sum = 0;
             for (uint64_t i = a; i < b; i++) {
-                if (r->status[i] == WFAHIP_PAIR_OK && (r->ops_len[i] > r->n_ops || r->ops_off[i] > r->n_ops - r->ops_len[i])) {
-                    bad = 1;  // (compared without a sum that could wrap; none of this pair's ops is read)
-                    off[i] = 0;
-                    continue;
-                }
-                uint32_t        first, count;
-                const uint64_t *ops = pair_ops(i, &first, &count);
-                off[i] = count ? cig_text_bytes(ops, count) : 0;
+                off[i] = 0;
+                if (!len(i, &off[i])) bad = 1, off[i] = 0;
                 sum += off[i];
             }
             part_p[t + 1] = sum;
@@ -301,13 +529,9 @@ int cigar_text_host(const wfahip_results *r, int only_aligned, int n_threads, wf
     }
     for (unsigned t = 0; t < T; t++) part[t + 1] += part[t];
     const uint64_t total = part[T];
-    char          *text  = nullptr;
-    if (total) {
-        text = static_cast<char *>(std::malloc((size_t)total));
-        if (!text) {
-            std::free(off);
-            return WFAHIP_ERR_OOM;
-        }
+    if (total && !alloc(total)) {
+        std::free(off);
+        return WFAHIP_ERR_OOM;
     }
     parallel_ranges(0, T, T, [&, part_p](uint64_t t0, uint64_t t1) {
         for (uint64_t t = t0; t < t1; t++) {
@@ -316,20 +540,104 @@ int cigar_text_host(const wfahip_results *r, int only_aligned, int n_threads, wf
             for (uint64_t i = a; i < b; i++) {
                 const uint64_t bytes = off[i];
                 off[i]               = run;
-                if (bytes) {
-                    uint32_t        first, count;
-                    const uint64_t *ops = pair_ops(i, &first, &count);
-                    cig_text_write(ops, count, reinterpret_cast<uint8_t *>(text) + run);
-                }
+                if (bytes) write(i, run);
                 run += bytes;
             }
         }
     });
-    off[n]       = total;
+    off[n]     = total;
+    *off_out   = off;
+    *total_out = total;
+    return WFAHIP_OK;
+}
+
+int cigar_text_host(const wfahip_results *r, int only_aligned, int n_threads, wfahip_cigars *out) {
+    if (out) cigars_zero(out);
+    if (!r || !out) return WFAHIP_ERR_BAD_ARG;
+    const uint64_t n = r->n;
+    if (n && (!r->status || !r->ops_off || !r->ops_len)) return WFAHIP_ERR_BAD_ARG;
+    if (!r->ops && r->n_ops) return WFAHIP_ERR_BAD_ARG;
+    char      *text = nullptr;
+    uint64_t  *off = nullptr, total = 0;
+    const bool trim = only_aligned != 0;
+    const int  rc   = host_render(
+        n, n_threads, &off, &total,
+        [&](uint64_t i, uint64_t *bytes) {
+            uint32_t        count;
+            const uint64_t *ops;
+            if (!host_pair_ops(r, i, trim, &ops, &count)) return false;
+            *bytes = count ? cig_text_bytes(ops, count) : 0;
+            return true;
+        },
+        [&](uint64_t bytes) { return (text = static_cast<char *>(std::malloc((size_t)bytes))) != nullptr; },
+        [&](uint64_t i, uint64_t at) {
+            uint32_t        count;
+            const uint64_t *ops;
+            (void)host_pair_ops(r, i, trim, &ops, &count);
+            cig_text_write(ops, count, reinterpret_cast<uint8_t *>(text) + at);
+        });
+    if (rc) return rc;
     out->n       = n;
     out->n_bytes = total;
     out->text    = text;
     out->off     = off;
+    return WFAHIP_OK;
+}
+
+void align_texts_zero(wfahip_align_texts *t) { std::memset(t, 0, sizeof *t); }
+
+int alignment_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                        const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads, wfahip_align_texts *out) {
+    if (out) align_texts_zero(out);
+    if (!r || !out) return WFAHIP_ERR_BAD_ARG;
+    const uint64_t n = r->n;
+    if (n && (!r->status || !r->ops_off || !r->ops_len || !q_off || !q_len || !t_off || !t_len)) return WFAHIP_ERR_BAD_ARG;
+    if (n && only_aligned && (!r->qbegin || !r->qend || !r->tbegin || !r->tend)) return WFAHIP_ERR_BAD_ARG;
+    if ((!r->ops && r->n_ops) || (!seq_blob && blob_bytes)) return WFAHIP_ERR_BAD_ARG;
+    char      *rows[3] = {nullptr, nullptr, nullptr};
+    uint64_t  *off = nullptr, total = 0;
+    const bool trim = only_aligned != 0;
+    // a pair's rendering ops and windows; false where wfa_altext.hpp's checks fail
+    const auto pair = [&](uint64_t i, const uint64_t **ops, uint32_t *count, AltWindow *w, uint64_t *cols) {
+        if (!host_pair_ops(r, i, trim, ops, count)) return false;
+        *cols = 0;
+        if (*count == 0u) return true;
+        const AltSums s = alt_sums(*ops, *count);
+        if (!alt_window(trim, blob_bytes, q_off[i], q_len[i], t_off[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                        trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w) ||
+            !alt_fits(s, *w))
+            return false;
+        *cols = s.cols;
+        return true;
+    };
+    const int rc = host_render(
+        n, n_threads, &off, &total,
+        [&](uint64_t i, uint64_t *bytes) {
+            uint32_t        count;
+            const uint64_t *ops;
+            AltWindow       w;
+            return pair(i, &ops, &count, &w, bytes);
+        },
+        [&](uint64_t bytes) {
+            for (char *&p : rows) p = static_cast<char *>(std::malloc((size_t)bytes));
+            if (rows[0] && rows[1] && rows[2]) return true;
+            for (char *&p : rows) std::free(p), p = nullptr;
+            return false;
+        },
+        [&](uint64_t i, uint64_t at) {
+            uint32_t        count;
+            const uint64_t *ops;
+            AltWindow       w;
+            uint64_t        cols;
+            (void)pair(i, &ops, &count, &w, &cols);
+            alt_rows_write(ops, count, seq_blob + w.q_at, seq_blob + w.t_at, reinterpret_cast<uint8_t *>(rows[0]) + at,
+                           reinterpret_cast<uint8_t *>(rows[1]) + at, reinterpret_cast<uint8_t *>(rows[2]) + at);
+        });
+    if (rc) return rc;
+    out->n       = n;
+    out->n_bytes = total;
+    out->q_row = rows[0], out->a_row = rows[1], out->t_row = rows[2];
+    out->off = off;
     return WFAHIP_OK;
 }
 
@@ -467,6 +775,26 @@ extern "C" void wfahip_cigars_free(wfahip_cigars *c) {
     if (!c) return;
     std::free(c->text), std::free(c->off);
     cigars_zero(c);
+}
+
+extern "C" int wfahip_alignment_text_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob,
+                                            uint64_t blob_bytes, const void *d_q_off, const void *d_q_len, const void *d_t_off,
+                                            const void *d_t_len, uint64_t n_pairs, int only_aligned, void *d_q_row, void *d_a_row,
+                                            void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *row_needed, void *stream) {
+    WFAHIP_GUARD(altext_device_entry(ctx, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs,
+                                     only_aligned, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, row_needed, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_alignment_text(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                                     const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads,
+                                     wfahip_align_texts *out) {
+    WFAHIP_GUARD(alignment_text_host(r, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, only_aligned, n_threads, out))
+}
+
+extern "C" void wfahip_align_texts_free(wfahip_align_texts *t) {
+    if (!t) return;
+    std::free(t->q_row), std::free(t->a_row), std::free(t->t_row), std::free(t->off);
+    align_texts_zero(t);
 }
 
 extern "C" int wfahip_align_batch_text(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,

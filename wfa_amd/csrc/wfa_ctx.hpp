@@ -6,7 +6,8 @@
 //                  wfahip_align_pair, submit / collect, the results cache
 //   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_packed, wfahip_score_batch_device, wfahip_score_matrix -- a
 //                  router each over the launch section, the geometry and the full-path fallback they share
-//   wfa_cigar.hip  CIGAR text: the three rendering kernels, wfahip_cigar_text_device, the host renderer wfahip_cigar_text, wfahip_align_batch_text
+//   wfa_cigar.hip  CIGAR text: the three rendering kernels, wfahip_cigar_text_device, the host renderer wfahip_cigar_text, wfahip_align_batch_text;
+//                  the display rows on the same scan: wfahip_alignment_text_device, the host renderer wfahip_alignment_text
 //   wfa_debug.hip  parity and measurement aids: wavefront dumps, the compact arenas, the device-side generator, the clock probe,
 //                  the read-back behind a launch of the team kernels
 #pragma once
@@ -184,7 +185,7 @@ struct wfahip_ctx {
                                                   // words lie in mx_words, behind the uploaded ones)
     DevBuf        sd_ctl, sd_blk, sd_list, sd_redo;  // wfahip_score_batch_device (wfa_score_dev.hpp): control words, tile sums, the long pairs, the pairs of the full path
     uint64_t      sd_n_words = 0, sd_n_listed = 0;   // ... what its last call left in mx_words / mx_seq (wfahip_debug_score_device_list)
-    DevBuf        cig;                            // wfahip_cigar_text_device (wfa_cigar.hip): its counters, the scan's block sums, the trimmed op range of every pair
+    DevBuf        cig;                            // wfahip_cigar_text_device, wfahip_alignment_text_device (wfa_cigar.hip): its counters, the scan's block sums, the trimmed op range of every pair
     DevBuf        cig_text, cig_off;              // wfahip_align_batch_text: the batch's text and its offsets, until they are downloaded
     DevBuf        mx_out;                         // ... {status, score} of two tiles (double-buffered: tile c downloads while tile c + 1 runs)
     uint2        *mx_pin       = nullptr;         // ... their page-locked host copies
