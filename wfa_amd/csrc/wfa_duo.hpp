@@ -92,6 +92,19 @@ struct DuoRed {
 #undef WFA_DUO_1
 };
 
+// The lanes in which a compare holds, as a mask for the scalar unit (WFA_DUO_UNIFORM, wfa_duo_cfg.hpp).  b must be ONE compare, made where the
+// mask is asked for: the ballot of a compare is that compare's own result and costs nothing, but the ballot of anything else -- an AND or an OR
+// of compares, a compare made in an earlier block, a stored flag -- is v_cndmask 0 / 1 of the lane mask and a v_cmp with zero of that register:
+// two vector instructions to copy a mask that already sits in scalar registers.  `__ballot(run && x) != 0ull` is lowered like that; here the
+// masks are combined and tested by the scalar unit instead (s_and_b64, s_cmp_lg_u64), as WF_EXTEND's candidate masks are.  The empty asm keeps
+// the compiler from folding mask and test back into a branch on the lane value.
+static WFA_DEV unsigned long long duo_lanes(bool b) {
+    unsigned long long mask = __builtin_amdgcn_ballot_w64(b);
+    asm("" : "+s"(mask));
+    return mask;
+}
+static WFA_DEV bool duo_lane_of(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }  // the lane's bit: no instruction
+
 // DX / DOE: the penalty shape, as in wfa_blk_kernel (R = max(DX, DOE) rows in the M ring)
 // PK: the rings as 16-bit pairs -- a lane's diagonals (p0, p1) in one register and (p2, p3) in another, the lower diagonal in the
 // low half -- and WF_NEXT's rejection-free path two diagonals per instruction (wide_next2()); wfa_duo_kernel runs this form.
@@ -102,6 +115,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     static_assert(DX >= 1 && DOE >= 1 && DX <= 4 && DOE <= 4, "ring depths of one to four score steps");
     constexpr int R  = DX > DOE ? DX : DOE;
     constexpr int RW = PK ? 2 : PP;  // ring registers per row of a lane
+    // the uniform tests as scalar code and the lane constants of set_derived() (wfa_duo_cfg.hpp).  The packed kernel only: the 32-bit-ring
+    // reference with three ring rows needs two more scalar registers in this form, and stays as it was
+    constexpr bool UNI = WFA_DUO_UNIFORM != 0 && PK;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int  lane = threadIdx.x, l7 = lane & 7, l15 = lane & 15;
     const bool hi_half = (lane & 8) != 0;
@@ -124,8 +140,17 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     uint32_t  pidx = 0, si = 0, cells = 0, sbuf = 0;
     int       n = 0, m = 0, kb = 0;
     bool      slow = false, first_eq = false;
+    // ---- UNI: the lanes with st == 1 and the lanes with `wide`, as masks in scalar registers: st and wide change in a restructuring round, in fill() and
+    // in the finish branch, nowhere else, and each of those ends in set_derived(), which forms the masks again.  The step and the round's trigger
+    // read the masks -- `run &&` is a scalar AND, the free halves are ~run_m, DuoRed's fourth stage takes wide_m as it is -- and compare neither
+    // st nor wide again.  Between a change and its set_derived() the lane values are the truth, and the code there reads those.
+    unsigned long long run_m = 0ull, wide_m = 0ull;
     // ---- per-lane values derived from them
     int             j = l7, k0 = 0;
+    // (UNI: what the step would otherwise form again every time, kept in registers -- the kernel has sixteen to spare under the 128 of four waves per
+    // SIMD: the window-relative indices 4 j + p and the diagonals k0 + p of the lane's cells, and the upper edge of the window, kb + Wc - 1,
+    // that the restructuring trigger compares with.  Written by set_derived() and by nothing else; read through jx(), kx() and kedge)
+    int             jp[4] = {4 * l7, 4 * l7 + 1, 4 * l7 + 2, 4 * l7 + 3}, kp[4] = {0, 1, 2, 3}, kedge = 31;
     uint32_t        mdn = 0u, mup = 0u;  // all-ones unless the lane is the first / last of its group
     const uint32_t *lq = lds + 4, *lt = lds + 4;
     uint32_t       *rowp = nullptr;
@@ -192,13 +217,28 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     const auto dn1 = [&](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true) & mdn; };
     const auto up1 = [&](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x101, 0xf, 0xf, true) & mup; };
     const auto other_half = [&](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, true); };  // row_ror:8
+    const auto jx = [&](int p) { return UNI ? jp[p] : PP * j + p; };
+    const auto kx = [&](int p) { return UNI && p != 0 ? kp[p] : k0 + p; };
     const auto set_derived = [&]() {
+        if constexpr (UNI) run_m = duo_lanes(st == 1), wide_m = duo_lanes(wide);
         j   = wide ? l15 : l7;
         mdn = j == 0 ? 0u : ~0u;
         mup = j == (wide ? 15 : 7) ? 0u : ~0u;
         k0  = kb + PP * j;
 #pragma unroll
         for (int p = 0; p < PP; p++) lim[p] = imax2(1, imin2(n + k0 + p, m)), lmx[p] = imax2(n + k0 + p, m);
+        if constexpr (UNI) {
+            static_assert(PP == 4, "four cells a lane");
+#pragma unroll
+            for (int p = 0; p < PP; p++) {
+                jp[p] = PP * j + p, kp[p] = k0 + p;
+                // (opaque: knowing how they are formed, the compiler may move the additions back behind the loop's phi, into the step)
+                asm("" : "+v"(jp[p]));
+                if (p != 0) asm("" : "+v"(kp[p]));
+            }
+            kedge = kb + (wide ? 64 : 32) - 1;
+            asm("" : "+v"(kedge));
+        }
         lq   = lds + sbuf * PW + 4u;
         lt   = lq + SW;
         if constexpr (DUO_ARENA_FMT == 10u)  // [pair of groups][score / 8][group & 1][score & 7]: the lane's base; the score's part is added at the store
@@ -375,18 +415,33 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         unsigned long long m_free;
         WFA_STAMP(0);  // prefetch stage
         for (;;) {
-        const bool run   = st == 1;
         const int  Wc    = wide ? 64 : 32;
-        const bool touch = run && rhi[NEW] >= rlo[NEW] && (rlo[NEW] <= kb || rhi[NEW] >= kb + Wc - 1);
-        bool       narrowable = false;
-        if constexpr (ph == 0) {  // (looked at every fourth step: a wide pair that could be narrow costs a half row, nothing else)
-            int ulo = rlo[0], uhi = rhi[0];
+        const bool run   = UNI ? duo_lane_of(run_m) : st == 1;
+        bool       touch, narrowable = false;
+        unsigned long long m_ev;
+        if constexpr (UNI) {
+            // (every compare's lane mask on its own, combined by the scalar unit -- duo_lanes(); the window's upper edge from set_derived())
+            const unsigned long long touch_m =
+                run_m & duo_lanes(rhi[NEW] >= rlo[NEW]) & (duo_lanes(rlo[NEW] <= kb) | duo_lanes(rhi[NEW] >= kedge));
+            unsigned long long narrow_m = 0ull;
+            if constexpr (ph == 0) {  // (looked at every fourth step: a wide pair that could be narrow costs a half row, nothing else)
+                int ulo = rlo[0], uhi = rhi[0];
 #pragma unroll
-            for (int d = 1; d < R; d++) ulo = imin2(ulo, rlo[d]), uhi = imax2(uhi, rhi[d]);
-            narrowable    = run && wide && uhi - ulo + 1 <= DUO_NARROW_AT;
+                for (int d = 1; d < R; d++) ulo = imin2(ulo, rlo[d]), uhi = imax2(uhi, rhi[d]);
+                narrow_m = run_m & wide_m & duo_lanes(uhi - ulo + 1 <= DUO_NARROW_AT);
+            }
+            touch = duo_lane_of(touch_m), narrowable = duo_lane_of(narrow_m);
+            m_ev = touch_m | narrow_m, m_free = ~run_m;
+        } else {
+            touch = run && rhi[NEW] >= rlo[NEW] && (rlo[NEW] <= kb || rhi[NEW] >= kb + Wc - 1);
+            if constexpr (ph == 0) {  // (looked at every fourth step: a wide pair that could be narrow costs a half row, nothing else)
+                int ulo = rlo[0], uhi = rhi[0];
+#pragma unroll
+                for (int d = 1; d < R; d++) ulo = imin2(ulo, rlo[d]), uhi = imax2(uhi, rhi[d]);
+                narrowable    = run && wide && uhi - ulo + 1 <= DUO_NARROW_AT;
+            }
+            m_ev = __ballot(touch || narrowable), m_free = __ballot(st == 0);
         }
-        const unsigned long long m_ev = __ballot(touch || narrowable);
-        m_free = __ballot(st == 0);
         // (expected: nothing to do -- tells the register allocator that what follows is the cold side of the loop)
         if (__builtin_expect(!(m_ev != 0ull || (m_free != 0ull && (park_used != 0u || (pf & PF_STAGED) != 0u))), 1)) break;
         WFA_EVT(1, 1);
@@ -559,8 +614,13 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     // ================================================================ one score step of every running pair
     const auto step = [&](auto ph_c) __attribute__((always_inline)) {
         constexpr int ph = decltype(ph_c)::value;
-        const bool run = (st == 1);
-        const unsigned long long wm = __ballot(wide);  // lanes of the 16-lane pairs (DuoRed's fourth stage)
+        // (UNI: "does any RUNNING lane ..." is the ballot of ONE compare and a scalar AND with the mask of the running lanes -- duo_lanes())
+        const bool run = UNI ? duo_lane_of(run_m) : st == 1;
+        const auto any_run = [&](bool b) {  // b: ONE compare
+            if constexpr (UNI) return (duo_lanes(b) & run_m) != 0ull;
+            else return __ballot(run && b) != 0ull;
+        };
+        const unsigned long long wm = UNI ? wide_m : __ballot(wide);  // lanes of the 16-lane pairs (DuoRed's fourth stage)
         WFA_EVT(0, 1), WFA_EVT(6, __builtin_popcountll(__ballot(run)) / 8);
 
         uint32_t(&Mo)[RW] = M[(ph + R - DOE) % R];  // M[s-o-e]
@@ -574,14 +634,14 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         // register, k+1 of its last the low half of the upper lane's first)
         const uint32_t a_edge = dn1(Mo[RW - 1]), b_edge = dn1(I[RW - 1]);
         const uint32_t c_edge = up1(Mo[0]), d_edge = up1(D[0]);
-        const bool     slow_any = __ballot(run && slow) != 0ull;
+        const bool     slow_any = any_run(slow);
         // the path with rejections near a sequence end: 32-bit sources in, 32-bit cells out
         const auto next_slow = [&](const uint32_t(&Mo4)[PP], const uint32_t(&I4)[PP], const uint32_t(&D4)[PP], const uint32_t(&Mx4)[PP],
                                    uint32_t ae, uint32_t be, uint32_t ce, uint32_t de, uint32_t(&nI4)[PP], uint32_t(&nD4)[PP],
                                    uint32_t(&wd4)[PP]) __attribute__((always_inline)) {
 #pragma unroll
             for (int p = 0; p < PP; p++) {
-                const int      k  = k0 + p;
+                const int      k  = kx(p);
                 const uint32_t a0 = p ? Mo4[p - 1] : ae, b0 = p ? I4[p - 1] : be;
                 const uint32_t c0 = p < PP - 1 ? Mo4[p + 1] : ce, d0 = p < PP - 1 ? D4[p + 1] : de;
                 const uint32_t x0 = Mx4[p];
@@ -658,11 +718,11 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             next_slow(Mo, I, D, Mx, a_edge, b_edge, c_edge, d_edge, nI, nD, wd);
         }
         // seeds of initComponents (wfa.go:155-160): M[0][0] = 1/Match or M[x][0] = 1/Mismatch
-        if (__builtin_expect(__ballot(run && si <= seed_si) != 0ull, 0)) {  // (ONE compare on the step's path; `want` below is the exact test)
+        if (__builtin_expect(any_run(si <= seed_si), 0)) {  // (ONE compare on the step's path; `want` below is the exact test)
             const bool want = run && ((si == 0u && first_eq) || (si == seed_si && !first_eq));
 #pragma unroll
             for (int p = 0; p < PP; p++)
-                if (want && k0 + p == 0 && nM[p] == 0u) {
+                if (want && kx(p) == 0 && nM[p] == 0u) {
                     const uint32_t sw = first_eq ? BLK_SEED_MATCH : BLK_SEED_MISMATCH;
                     nM[p] = 1u, cc[p] = CENSUS ? 1u : 0u;
                     if constexpr (PK) wd[p >> 1] = (p & 1) ? (wd[p >> 1] & 0xFFFFu) | (sw << 16) : (wd[p >> 1] & 0xFFFF0000u) | sw;
@@ -675,7 +735,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         // lane's four diagonals are one 8-byte store, and a 64-byte piece of a line holds 8 scores of 4 diagonals.  Half
         // the bytes of fmt 3 to write here and to fetch in the backtrace's walk (round 3; WRITE_SIZE was 31 GB per
         // 1e6 pairs with 32-bit words).
-        const bool no_room = run && (int)si >= rows_cap;
+        // (UNI: read again at the finish -- the mask, not a second compare)
+        const unsigned long long room_m = UNI ? run_m & duo_lanes((int)si >= rows_cap) : 0ull;
+        const bool no_room = UNI ? duo_lane_of(room_m) : run && (int)si >= rows_cap;
         {
             uint32_t anyc = 0u;
 #pragma unroll
@@ -699,7 +761,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 uint32_t       rem;  // max(lim - h, 0): one saturating subtraction
                 asm("v_sub_u32_e64 %0, %1, %2 clamp" : "=v"(rem) : "v"(lim[p]), "v"(h));
                 const uint32_t room = h ? rem : 0u;
-                const int      v    = h - (k0 + p);
+                const int      v    = h - kx(p);
                 const uint32_t xr   = SeqView<0>::win16(lq, v) ^ SeqView<0>::win16(lt, h);
                 const uint32_t rn   = umin2(ffbl_raw(xr) >> 1, room);
                 nM[p] += umin2(rn, 16u);
@@ -745,7 +807,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 uint32_t rem;  // max(lim - h, 0): one saturating subtraction
                 asm("v_sub_u32_e64 %0, %1, %2 clamp" : "=v"(rem) : "v"(lim[p]), "v"(h));
                 const uint32_t room = nz[p] ? rem : 0u;
-                const int      v    = h - (k0 + p);
+                const int      v    = h - kx(p);
                 const uint32_t xr   = SeqView<0>::win16(lq, v) ^ SeqView<0>::win16(lt, h);
                 const uint32_t rn   = umin2(ffbl_raw(xr) >> 1, room);
                 nM[p] = (uint32_t)h + umin2(rn, 16u);
@@ -762,9 +824,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                                       __builtin_amdgcn_inverse_ballot_w64(s2), __builtin_amdgcn_inverse_ballot_w64(s3)};
                 // a lane without a candidate gets h = lm = 0: nothing left, so it counts nothing and never asks for another round
                 uint32_t h  = sel[PP - 1] ? nM[PP - 1] : 0u;
-                int      kd = k0 + PP - 1;
+                int      kd = kx(PP - 1);
 #pragma unroll
-                for (int p = PP - 2; p >= 0; p--) h = sel[p] ? nM[p] : h, kd = sel[p] ? k0 + p : kd;
+                for (int p = PP - 2; p >= 0; p--) h = sel[p] ? nM[p] : h, kd = sel[p] ? kx(p) : kd;
                 // lim[] of that diagonal (a candidate has more than 16 bases left: the lower bound of 1 in lim[] cannot bind)
                 const uint32_t lm = __builtin_amdgcn_inverse_ballot_w64(pend) ? (uint32_t)imin2(n + kd, m) : 0u;
                 // A round counts min(matching bases, bases left, 32); exactly 32 asks for another round.  A lane that has stopped adds
@@ -794,16 +856,20 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
 #pragma unroll
         for (int p = 0; p < PP; p++) hit[p] = nM[p] >= (uint32_t)lim[p], hitl |= hit[p];
         bool       term    = false;
-        const bool hit_any = __ballot(hitl) != 0ull;
+        static_assert(PP == 4, "hit masks of four diagonals");
+        // (UNI: the OR of the four compares' masks, in scalar registers; hitl, the same OR as a lane value, is read in the rare branch only)
+        const bool hit_any = UNI ? (duo_lanes(hit[0]) | duo_lanes(hit[1]) | duo_lanes(hit[2]) | duo_lanes(hit[3])) != 0ull : __ballot(hitl) != 0ull;
+        unsigned long long term_m = 0ull;  // UNI: the lanes of `term`
         bool       ghit    = false;
         if (hit_any) {
             bool tl = false;
 #pragma unroll
-            for (int p = 0; p < PP; p++) tl |= (k0 + p == m - n && nz[p] && (int)nM[p] >= m);
+            for (int p = 0; p < PP; p++) tl |= (kx(p) == m - n && nz[p] && (int)nM[p] >= m);
             const int r = DuoRed::or1((hitl ? 1 : 0) | (tl ? 2 : 0), wm);
             ghit = (r & 1) != 0;
             slow |= ghit;
-            term = run && (r & 2) != 0;
+            if constexpr (UNI) term_m = duo_lanes((r & 2) != 0) & run_m, term = duo_lane_of(term_m);
+            else term = run && (r & 2) != 0;
         }
 
         // ------------------------------------------------------------ band of the row + wf-adaptive (wfa.go:461-540)
@@ -815,10 +881,10 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             constexpr int ABSENT = BK_BIG + 1;
             int glo = BK_BIG, ghi = -BK_BIG, dd[PP];
 #pragma unroll
-            for (int p = PP - 1; p >= 0; p--) glo = nz[p] ? PP * j + p : glo;
+            for (int p = PP - 1; p >= 0; p--) glo = nz[p] ? jx(p) : glo;
 #pragma unroll
             for (int p = 0; p < PP; p++) {
-                ghi   = nz[p] ? PP * j + p : ghi;
+                ghi   = nz[p] ? jx(p) : ghi;
                 dd[p] = nz[p] ? lmx[p] - (int)nM[p] : ABSENT;
             }
             static_assert(PP == 4, "minimum of four distances");
@@ -829,14 +895,14 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             const int  thr  = want ? mind + mdd : BK_BIG;
             int        first_ok = BK_BIG, last_ok = -BK_BIG;
 #pragma unroll
-            for (int p = PP - 1; p >= 0; p--) first_ok = dd[p] <= thr ? PP * j + p : first_ok;
+            for (int p = PP - 1; p >= 0; p--) first_ok = dd[p] <= thr ? jx(p) : first_ok;
 #pragma unroll
-            for (int p = 0; p < PP; p++) last_ok = dd[p] <= thr ? PP * j + p : last_ok;
+            for (int p = 0; p < PP; p++) last_ok = dd[p] <= thr ? jx(p) : last_ok;
             DuoRed::min_max(first_ok, last_ok, wm);
             ilo = first_ok, ihi = last_ok;
 #pragma unroll
             for (int p = 0; p < PP; p++) {  // Delete of wfa.go:526-535: the words never exist
-                const int  ix   = PP * j + p;
+                const int  ix   = jx(p);
                 const bool keep = ix >= ilo && ix <= ihi;
                 nM[p] = keep ? nM[p] : 0u;
                 if constexpr (!PK) nI[p] = keep ? nI[p] : 0u, nD[p] = keep ? nD[p] : 0u;  // (PK: at the ring's entry)
@@ -845,9 +911,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         } else {
             int glo = BK_BIG, ghi = -BK_BIG;
 #pragma unroll
-            for (int p = PP - 1; p >= 0; p--) glo = nz[p] ? PP * j + p : glo;
+            for (int p = PP - 1; p >= 0; p--) glo = nz[p] ? jx(p) : glo;
 #pragma unroll
-            for (int p = 0; p < PP; p++) ghi = nz[p] ? PP * j + p : ghi;
+            for (int p = 0; p < PP; p++) ghi = nz[p] ? jx(p) : ghi;
             DuoRed::min_max(glo, ghi, wm);
             anyM = ghi >= 0;
             ilo = glo, ihi = ghi;
@@ -871,21 +937,21 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 if (__ballot(found) != 0ull) {
                     int first_ok = BK_BIG, last_ok = -BK_BIG;
 #pragma unroll
-                    for (int p = PP - 1; p >= 0; p--) first_ok = (vd[p] && dd[p] <= thr) ? PP * j + p : first_ok;
+                    for (int p = PP - 1; p >= 0; p--) first_ok = (vd[p] && dd[p] <= thr) ? jx(p) : first_ok;
 #pragma unroll
-                    for (int p = 0; p < PP; p++) last_ok = (vd[p] && dd[p] <= thr) ? PP * j + p : last_ok;
+                    for (int p = 0; p < PP; p++) last_ok = (vd[p] && dd[p] <= thr) ? jx(p) : last_ok;
                     DuoRed::min_max(first_ok, last_ok, wm);
                     // wfa.go:509-511 (see wfa_blk.hpp: per pair, not per wave)
                     int leadp = -1;
 #pragma unroll
-                    for (int p = 0; p < PP; p++) leadp = (vd[p] && PP * j + p < first_ok) ? PP * j + p : leadp;
+                    for (int p = 0; p < PP; p++) leadp = (vd[p] && jx(p) < first_ok) ? jx(p) : leadp;
                     leadp = DuoRed::max1(leadp, wm);
                     const int newlo = ghit ? (leadp >= 0 ? leadp + 1 : glo) : first_ok;
                     if (found) ilo = newlo, ihi = last_ok;  // wfa.go:517-524
                     csum = 0u;
 #pragma unroll
                     for (int p = 0; p < PP; p++) {
-                        const int  ix   = PP * j + p;
+                        const int  ix   = jx(p);
                         const bool keep = ix >= ilo && ix <= ihi;
                         nM[p] = keep ? nM[p] : 0u;
                         if constexpr (!PK) nI[p] = keep ? nI[p] : 0u, nD[p] = keep ? nD[p] : 0u;
@@ -924,7 +990,8 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         rhi[ph] = keepl ? kb + ihi : -BK_BIG;
 
         // ------------------------------------------------------------ finish / next score
-        const bool fin = run && (term || no_room);
+        const unsigned long long fin_m = term_m | room_m;  // (UNI; both inside run_m)
+        const bool fin = UNI ? duo_lane_of(fin_m) : run && (term || no_room);
         // (WFA_DUO_FILL: the score index moves on before the finish, not after it -- a pair that finishes keeps its own for pair_meta, and
         // the set_derived() behind the fill forms the row pointer of arena formats 7 and 9 from the index of the next step)
         if constexpr (WFA_DUO_FILL != 0)
@@ -933,13 +1000,13 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         // registers -- 0.05 ms of a 14 ms step.  Not on the 32-bit rings: at their 124 .. 128 registers the hint costs wfa_duo32_kernel<false, 2, 4>
         // eight spilled ones)
         constexpr bool cold    = WFA_DUO_FILL != 0 && PK;
-        const bool     any_fin = __ballot(fin) != 0ull;
+        const bool     any_fin = UNI ? fin_m != 0ull : __ballot(fin) != 0ull;
         if (cold ? __builtin_expect(any_fin, 0) : any_fin) {
             const int ctot = (CENSUS && P.census) ? (int)cells : 0;
             int hf   = 0;  // extended offset of the end cell M[s][Ak]: where the backtrace starts
 #pragma unroll
             for (int p = 0; p < PP; p++)
-                if (k0 + p == m - n) hf = (int)nM[p];  // (= the ring's new row)
+                if (kx(p) == m - n) hf = (int)nM[p];  // (= the ring's new row)
             hf = DuoRed::max1(hf, wm);
             if (fin && j == 0) {
                 if (no_room) {
@@ -965,8 +1032,11 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
         }
-        if constexpr (WFA_DUO_FILL == 0)
+        if constexpr (WFA_DUO_FILL == 0) {
             if (run && !fin) si += 1u;
+            if constexpr (UNI)
+                if (any_fin) set_derived();  // (st and wide of the finished pairs have changed: the masks; nothing else of it differs)
+        }
         WFA_STAMP(5);  // ring + finish
     };
 

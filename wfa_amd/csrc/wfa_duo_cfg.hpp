@@ -43,6 +43,14 @@ namespace wfa {
 #ifndef WFA_DUO_FILL
 #define WFA_DUO_FILL 1
 #endif
+// How the score step asks wave-uniform questions and where it keeps what only set_derived() changes (wfa_duo.hpp): 1 = "does any lane ..." is a
+// scalar compare of the lane mask the vector compare wrote, the masks of the running and of the wide lanes live in scalar registers, and the
+// lane's diagonal indices and its trigger edge are formed once per set_derived() (the default); 0 = the form before -- every such test through a
+// 0/1 vector register, the constants formed in every step -- kept for A/B builds: scripts/mkvariant.sh <name> -DWFA_DUO_UNIFORM=0
+// (wfa_duo_kernel only: the 32-bit-ring reference wfa_duo32_kernel keeps the form before either way -- profiles/r13_duo_uniform.txt)
+#ifndef WFA_DUO_UNIFORM
+#define WFA_DUO_UNIFORM 1
+#endif
 // Arena layout of wfa_duo_kernel (16-bit words; a lane's four diagonals of a score are one 8-byte store, and 8 scores of them
 // one 64-byte piece, in every one of the three):
 //   0  CompactView fmt 7 (round 3) -- tiles of 8 scores x 64 diagonals (1 KB), inside a tile [diagonal / 4][score & 7][diagonal & 3]:
