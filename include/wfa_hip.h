@@ -234,7 +234,12 @@ int  wfahip_score_matrix_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint8
  * bound of every q_len/t_len (0 = let the library compute it).  stream = hipStream_t to launch on
  * (NULL = the context's own stream).  Synchronous: returns when results are complete.
  * If ops_cap is too small the call returns WFAHIP_ERR_OOM and *ops_needed (if non-NULL) holds
- * the required capacity. */
+ * the required capacity.
+ * Memory behind a sequence: the packing pass reads a sequence that starts at a 16-byte boundary in 16-byte pieces, its last
+ * piece too.  The allocation behind d_seq_blob must therefore be readable up to the next 16-byte boundary behind the last
+ * base of every sequence (every device allocator's granularity gives that; a view that ends inside a larger allocation has it
+ * as well).  The bytes read there do not influence any result.  This holds for every device entry that takes d_seq_blob
+ * (wfahip_align_batch_bounded_device, wfahip_debug_prepack). */
 int  wfahip_align_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_seq_blob,
                                uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
                                const void *d_t_off, const void *d_t_len, uint64_t n_pairs,
@@ -679,6 +684,16 @@ int  wfahip_debug_score_long_list(const uint8_t *seq_blob, const uint64_t *q_off
  * wfahip_debug_score_long_list returns for the same batch.  *n_words == 0 (and NULL arrays) when that call ran no long pairs on
  * wfa_score_long_kernel; valid until the next score call on ctx.  Caller frees *words and *table with wfahip_free. */
 int  wfahip_debug_score_device_list(wfahip_ctx *ctx, uint32_t **words, uint64_t *n_words, uint32_t **table, uint64_t *n_listed);
+
+/* Debug / test aid, refused with WFAHIP_ERR_UNSUPPORTED unless WFAHIP_DEBUG=1 is in the environment: the byte-input packing pass
+ * (wfa_prepack_kernel) alone, over device-resident pairs.  Slot i of the n is that of pair d_work[i] (d_work: n device uint32, or
+ * NULL: pair i), 4 + 2 * seq_words words: {q_len, t_len, status, 0, seq_words query words, seq_words text words} -- 16 bases a word,
+ * the first in the low bits, code (byte >> 1) & 3, 0 behind a sequence's end; status 0xFFFFFFFF (to be aligned), 1 (an empty
+ * sequence), 2 (too long), 102 (longer than the slot), 100 (a byte outside ACGT).  Only slots of status 0xFFFFFFFF and 100 hold
+ * words.  ppw (1 .. 32): pairs a wave packs.  slots: host memory for n * (4 + 2 * seq_words) words; a word the kernel did not
+ * store reads 0xA5A5A5A5. */
+int  wfahip_debug_prepack(wfahip_ctx *ctx, const void *d_seq_blob, const void *d_q_off, const void *d_q_len, const void *d_t_off,
+                          const void *d_t_len, const void *d_work, uint64_t n, uint32_t seq_words, uint32_t ppw, uint32_t *slots);
 
 /* The length classes semi-global batches are cut into before wfa_wide_kernel takes them: upper bounds of max(q_len, t_len),
  * strictly ascending, the last one 2 047.  Host only, no device.  Fills bounds[0 .. min(cap, count)) (bounds may be NULL when

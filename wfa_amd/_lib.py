@@ -29,7 +29,7 @@ EXPORTS = [
     "wfahip_debug_team_compact", "wfahip_score_batch", "wfahip_scores_free", "wfahip_score_matrix",
     "wfahip_debug_score_long_list", "wfahip_score_batch_device", "wfahip_debug_score_device_list",
     "wfahip_align_batch_bounded", "wfahip_align_batch_bounded_device", "wfahip_score_batch_packed",
-    "wfahip_wide_class_bounds", "wfahip_debug_wide_plan",
+    "wfahip_wide_class_bounds", "wfahip_debug_wide_plan", "wfahip_debug_prepack",
     "wfahip_score_batch_packed_rc", "wfahip_score_matrix_rc", "wfahip_revcomp_packed",
     "wfahip_cigar_text_device", "wfahip_cigar_text", "wfahip_cigars_free", "wfahip_align_batch_text",
     "wfahip_alignment_text_device", "wfahip_alignment_text", "wfahip_align_texts_free",
@@ -127,6 +127,8 @@ def lib():
         L.wfahip_debug_wide_plan.restype = C.c_int
         L.wfahip_debug_wide_plan.argtypes = [vp, vp, vp, u64, C.POINTER(C.POINTER(u32)), C.POINTER(u64), C.POINTER(u32),
                                              C.POINTER(u64)]
+        L.wfahip_debug_prepack.restype = C.c_int
+        L.wfahip_debug_prepack.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, vp]
         L.wfahip_align_batch_device.restype = C.c_int
         L.wfahip_align_batch_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, u64, u32, vp, vp,
                                                 u64, C.POINTER(u64), vp]

@@ -898,6 +898,25 @@ class Aligner:
         lists = [flat[cuts[c]:cuts[c + 1]] for c in range(nc)]
         return lists, counts, [int(x) for x in longest], flat[cuts[nc]:cuts[nc] + int(n_ladder.value)]
 
+    def debug_prepack(self, blob, q_off, q_len, t_off, t_len, seq_words: int, ppw: int = 4, work=None):
+        """The slots wfa_prepack_kernel makes of a batch on the aligner's GPU (include/wfa_hip.h: wfahip_debug_prepack): torch tensors
+        in, as align_tensors takes them; work: an int32 tensor of pair indices (slot i = pair work[i]) or None (slot i = pair i).
+        Returns uint32 [n, 4 + 2 * seq_words]; a word the kernel did not store reads 0xA5A5A5A5."""
+        import torch
+        dev = self._want_tensor("blob", blob, torch.uint8)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        if work is not None:
+            self._want_tensor("work", work, torch.int32, dev)
+        n = int(work.numel() if work is not None else q_len.numel())
+        slots = np.zeros((n, 4 + 2 * int(seq_words)), dtype=np.uint32)
+        torch.cuda.current_stream(dev).synchronize()
+        L.check(L.lib().wfahip_debug_prepack(self._ctx, blob.data_ptr(), q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(),
+                                             work.data_ptr() if work is not None else None, n, int(seq_words), int(ppw),
+                                             slots.ctypes.data_as(C.c_void_p)), "wfahip_debug_prepack")
+        return slots
+
     def Plot(self, q: bytes, t: bytes, component: str = "M", notChangeToMatch: bool = False, maxScore: int = -1) -> str:
         """(*Aligner).Plot (wfa_component_plot.go:41): the component table, from the DEVICE wavefronts of one pair."""
         wf, _ = self.debug_wavefronts(q, t)

@@ -1293,12 +1293,14 @@ __global__ __launch_bounds__(64, (G == 8 && PPT == 0 ? WFA_BLK8_WAVES : (G == 16
     }
 }
 
-// The sequences of a chunk, 2-bit packed once, by the whole GPU, before the forward kernel starts: 2 GB read, 0.5 GB
-// written per 1e6 x 1 kbp pairs.  One workgroup per pair, one thread per packed word (16 bases): four or five aligned
-// dword loads, a funnel shift, and per dword ten integer instructions -- the 2-bit codes are (byte >> 1) & 3, gathered
-// with two shift-or steps; a byte outside ACGT shows when the code's canonical letter (one v_perm_b32 through "ACTG")
-// differs from the byte.  (Round 2's version ran stage_word(), ~100 instructions per word, and was bound by them:
-// 0.89 ms; the forward kernels' own refill still uses stage_word.)  slot = {n, m, status, 0, q words [SW], t words [SW]}.
+// The sequences of a chunk, 2-bit packed once, by the whole GPU, before the forward kernel starts (wfa_prepack_kernel, below): 2 GB read,
+// 0.54 GB written per 1e6 x 1 kbp pairs.  slot = {n, m, status, 0, q words [SW], t words [SW]}; a word is 16 bases, the 2-bit codes are
+// (byte >> 1) & 3, and a byte outside ACGT shows when the code's canonical letter (one v_perm_b32 through "ACTG") differs from the byte.
+// prepack_dword / prepack_fetch / prepack_finish / prepack_word: a word from four or five aligned dword loads (one 16-byte load at a
+// 16-byte boundary), a funnel shift and ten integer instructions a dword.  The first form of wfa_prepack_kernel (-DWFA_PREPACK_V2=0) is
+// built on them, and wfa_lane_kernel's own packing (wfa_lane.hpp) uses prepack_word; the kernel's second form has its own (pp_fetch,
+// pp_finish).  (Round 2's version ran stage_word(), ~100 instructions per word, and was bound by them: 0.89 ms; the forward kernels' own
+// refill still uses stage_word.)
 // four bases (the bytes of w) as eight bits; bad |= a byte outside ACGT
 WFA_DEV uint32_t prepack_dword(uint32_t w, bool &bad) {
     const uint32_t x = (w >> 1) & 0x03030303u;
@@ -1351,9 +1353,237 @@ WFA_DEV uint32_t prepack_word(const uint8_t *blob, uint64_t off, uint32_t len, u
 // (a wave per pair, PREPACK_PAIRS pairs per wave: one workgroup per pair was bound by the dispatch of a million tiny
 // workgroups -- 1.01 ms for 2.5 GB of traffic)
 constexpr int PREPACK_PAIRS = 4;
+// The form of wfa_prepack_kernel: 1 = one load round per pair and the word packed as a whole (below), 0 = the form before, kept for
+// A/B builds: HOST=1 scripts/mkvariant.sh <name> -DWFA_PREPACK_V2=0
+#ifndef WFA_PREPACK_V2
+#define WFA_PREPACK_V2 1
+#endif
+
+// ---- wfa_prepack_kernel, second form.  What the first form cost, counted in its assembly at 1 kbp (SW = 66, 132 word positions): two
+// trips of two fetches, the second trip for four lanes; every fetch a divergent choice between five guarded dword loads and one 16-byte
+// load into registers it has cleared before, so that the compiler waits for all loads in flight before each of them -- four dependent
+// load rounds a pair, not the two the source shows; the last word's masking (one lane of 64) 48 instructions a fetch; ten instructions
+// a dword.  Here:
+//   * a lane takes query word l and text word l of a round of 64 words; a remainder of at most 32 words per sequence shares ONE fetch
+//     (lanes below rem: the query's words, the next rem lanes: the text's), and so does a slot of at most 32 words per sequence (two
+//     such pairs side by side in a wave when it has at most 16).  Two rounds -- up to four fetches -- are issued before any of them
+//     is packed: one load round a pair up to SW = 128, ceil(SW / 128) beyond.  A fetch none of whose lanes holds a word of its sequence
+//     issues nothing and packs nothing; the slot's pad words are stored as 0.
+//   * the lengths and offsets of the wave's pairs are loaded once, lane j those of pair j, and handed out through v_readlane_b32: in
+//     scalar registers, so that which words exist and the pair's status are scalar tests.
+//   * aligned or not is decided once for the wave's pairs (AL: every sequence starts at a 16-byte boundary -- the usual layout) and
+//     selects one of two copies of the loop.  Each copy has ONE load site per fetch and clears no register a load writes: a choice
+//     between two load forms inside the loop makes the compiler merge their registers, and it waits for every load in flight to do so.
+//   * the word's sixteen codes are gathered at once: the four dwords' codes side by side (byte k = bases k, 4 + k, 8 + k, 12 + k) and a
+//     4 x 4 transposition of 2-bit fields in two delta swaps; one running OR of (canonical letter ^ byte) per pair instead of a compare
+//     per dword; the mask of a sequence's last word as two 64-bit shifts.
+//   * the next fetches of the wave are issued between packing and storing, so that they are not issued behind this pair's stores.
+//     (The wait at the head of the next trip, vmcnt(0), still covers those stores: on gfx950 stores count in vmcnt.  What that costs
+//     has not been measured.)
+// What bounds the pass at 1e6 x 1 kbp (profiles/r14_prepack.txt): memory, 2.56 GB = 0.41 ms at the 6.3 TB/s of a copy; vector issue was
+// 387 wave-instructions a pair = 0.41 ms at 1.08 ns each on 1 024 SIMDs, and is 208 = 0.22 ms.  The first form took 0.70 ms -- its two
+// costs added up behind its serial load rounds -- the second takes 0.48 ms (0.47 at best): 1.17 x the memory floor.
+// s_waitcnt's operand on gfx9 / gfx950 for vmcnt(0) alone: vmcnt in bits 3:0 and 15:14 (0), expcnt in 6:4 and lgkmcnt in 11:8 left at
+// their maxima (no wait)
+constexpr int PP_WAIT_VMCNT0 = 0x0F70;
+struct PpWord {
+    uint32_t d[5];    // the dwords that hold the word's bytes (AL: four); undefined where nb = 0, and past the last one that holds a base
+    uint32_t sh, nb;  // bit shift of the first byte within d[0] (AL: 0); bases (0: no such word -- it packs to 0)
+    uint32_t pos;     // word position in the slot behind the header
+    bool     st;      // the lane stores the word
+};
+// the loads of word jw of the sequence of len bases at blob + off, for the lanes that want one
+template <bool AL>
+WFA_DEV void pp_fetch(const uint8_t *__restrict__ blob, uint64_t off, uint32_t len, uint32_t jw, bool want, PpWord &w) {
+    const bool act = want && jw < ((len + 15u) >> 4);
+    // (d is not cleared: a register cleared here and loaded below would make the compiler wait, before it clears it, for every load in
+    // flight -- the fetches of a group would go one after the other)
+    w.sh = 0u, w.nb = 0u;
+    if (act) {
+        const uint32_t left = len - 16u * jw;
+        w.nb = left < 16u ? left : 16u;
+        if constexpr (AL) {
+            // (a sequence's last word too: the sixteen bytes lie in one aligned 16-byte piece with its last base, hence in memory that exists)
+            const uint4 v = *reinterpret_cast<const uint4 *>(blob + (off + 16ull * jw));
+            w.d[0] = v.x, w.d[1] = v.y, w.d[2] = v.z, w.d[3] = v.w;
+        } else {
+            const uint32_t lo3 = (uint32_t)((uintptr_t)blob + off) & 3u;
+            w.sh = lo3 * 8u;
+            const uint32_t        last = ((lo3 + w.nb + 3u) >> 2) - 1u;  // the last dword that holds a base: 0..4
+            const uint32_t *const p    = reinterpret_cast<const uint32_t *>(blob + (off + 16ull * jw - lo3));
+#pragma unroll
+            for (int i = 0; i < 5; i++)
+                if ((uint32_t)i <= last) w.d[i] = p[i];  // (no dword past it: the memory behind the sequence may not exist)
+        }
+    }
+}
+// ... and its sixteen codes; diff |= a byte outside ACGT
+template <bool AL>
+WFA_DEV uint32_t pp_finish(const PpWord &w, uint32_t &diff) {
+    if (w.nb == 0u) return 0u;
+    uint32_t b[4];
+    // (!AL: d[i] past the last dword that holds a base was never loaded, and the shift takes bits from it.  Such a dword holds only bytes
+    // at or past nb, nb is below 16 then, and km below replaces every one of those bytes before anything looks at them: whoever changes
+    // the mask or the guard in pp_fetch keeps the two in step.)
+#pragma unroll
+    for (int i = 0; i < 4; i++) b[i] = AL ? w.d[i] : __funnelshift_r(w.d[i], w.d[i + 1], w.sh);
+    if (w.nb < 16u) {  // the last word of a sequence: bytes past its end count as 'A' (code 0)
+        const uint32_t nbit = 8u * w.nb;  // 8 .. 120
+        const uint64_t klo = ~0ull >> (64u - (nbit < 64u ? nbit : 64u)), khi = ~(~0ull << (nbit > 64u ? nbit - 64u : 0u));
+        const uint32_t km[4] = {(uint32_t)klo, (uint32_t)(klo >> 32), (uint32_t)khi, (uint32_t)(khi >> 32)};
+#pragma unroll
+        for (int i = 0; i < 4; i++) b[i] = (b[i] & km[i]) | (0x41414141u & ~km[i]);
+    }
+    uint32_t z = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t x = (b[i] >> 1) & 0x03030303u;
+        diff |= __builtin_amdgcn_perm(0u, 0x47544341u, x) ^ b[i];  // code -> 'A' 'C' 'T' 'G'
+        z |= x << (2 * i);
+    }
+    // field (k, i) -- base k of dword i -- is at bit 8 k + 2 i and belongs at 8 i + 2 k: transposed within the 2 x 2 blocks, then by blocks
+    uint32_t t = ((z >> 6) ^ z) & 0x00CC00CCu;
+    z ^= t ^ (t << 6);
+    t = ((z >> 12) ^ z) & 0x0000F0F0u;
+    z ^= t ^ (t << 12);
+    return z;
+}
 #ifndef WFA_NO_AUX_KERNELS
 // ppw: pairs a wave packs one after the other -- PREPACK_PAIRS, or 1 for a few long pairs (500 x 50 kbp: 125 waves of four pairs
 // were 0.32 ms of latency; 500 waves: 0.08).
+#if WFA_PREPACK_V2 != 0
+// TWO: short reads (a slot of at most 32 words) -- two pairs side by side, 32 lanes each.  h_*: lane j holds the lengths and offsets of
+// the wave's pair j.
+template <bool TWO, bool AL>
+WFA_DEV void prepack_loop(const KParams &P, uint32_t *__restrict__ out, const uint32_t SW, const uint32_t PW, const uint32_t ppw, const uint32_t first,
+                          const uint32_t lane, const uint32_t h_nq, const uint32_t h_mt, const uint64_t h_qo, const uint64_t h_to) {
+    constexpr uint32_t LP = TWO ? 32u : 64u;
+    const uint32_t side = TWO ? lane >> 5 : 0u, l = TWO ? lane & 31u : lane;
+    const auto hand32 = [&](uint32_t v, uint32_t j) -> uint32_t {
+        if constexpr (TWO)
+            return (uint32_t)__shfl((int)v, (int)j);
+        else
+            return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j);
+    };
+    const auto hand64 = [&](uint64_t v, uint32_t j) -> uint64_t { return (uint64_t)hand32((uint32_t)v, j) | ((uint64_t)hand32((uint32_t)(v >> 32), j) << 32); };
+    struct Pair {
+        uint32_t  nq, mt, status;
+        uint64_t  qo, to;
+        bool      have, go;
+        uint32_t *slot;
+    };
+    const auto pair_of = [&](uint32_t k) -> Pair {  // the pair of this lane's side in the wave's step k
+        Pair           p;
+        const uint32_t j = k + side, wi = first + j;
+        p.have = j < ppw && wi < P.chunk_n;
+        p.nq = hand32(h_nq, j), p.mt = hand32(h_mt, j), p.qo = hand64(h_qo, j), p.to = hand64(h_to, j);
+        p.status = ST_PENDING;
+        if (p.nq == 0 || p.mt == 0)
+            p.status = ST_EMPTY;  // wfa.go:204-206
+        else if (p.nq > 0x1FFFFFFFu || p.mt > 0x1FFFFFFFu)
+            p.status = ST_TOO_LONG;  // wfa.go:207-209
+        else if (((p.nq > p.mt ? p.nq : p.mt) + 15u) / 16u + 1u > SW)
+            p.status = ST_REDO_LDS;
+        p.go   = p.have && p.status == ST_PENDING;
+        p.slot = out + (uint64_t)wi * PW;
+        return p;
+    };
+    // a round: LP words of each sequence from word w0 = LP r on.  More than LP / 2 of them left: a fetch per sequence (A: the query's,
+    // B: the text's); else one for both (A).  (One pp_fetch per fetch, whatever the round's form: see AL above.)
+    const auto round = [&](const Pair &p, uint32_t r, PpWord &A, PpWord *B) {
+        const uint32_t w0 = LP * r, rem = w0 < SW ? SW - w0 : 0u;
+        const bool     split = !TWO && rem > LP / 2u;
+        const bool     q     = split || l < rem;
+        const uint32_t jw    = w0 + (q ? l : l - rem);
+        A.st  = p.go && l < (split ? rem : 2u * rem);
+        A.pos = q ? jw : SW + jw;
+        pp_fetch<AL>(P.blob, q ? p.qo : p.to, q ? p.nq : p.mt, jw, A.st, A);
+        if (B) {
+            B->st  = p.go && split && l < rem;
+            B->pos = SW + w0 + l;
+            pp_fetch<AL>(P.blob, p.to, p.mt, w0 + l, B->st, *B);
+        }
+    };
+    constexpr int  NW = TWO ? 1 : 4;                    // fetches in flight: two rounds; a short slot is one shared fetch
+    const uint32_t G  = TWO ? 1u : (SW + 127u) / 128u;  // groups of two rounds a pair: 1 up to SW = 128
+    PpWord         W[NW];
+#pragma unroll
+    for (int f = 0; f < NW; f++) W[f].st = false, W[f].nb = 0u, W[f].pos = 0u, W[f].sh = 0u;
+    Pair cur;
+    cur.have = cur.go = false, cur.nq = cur.mt = 0u, cur.status = ST_PENDING, cur.qo = cur.to = 0ull, cur.slot = out;
+    // One site fetches, one packs: a trip packs the group fetched by the trip before (the first trip none), fetches the next group -- of
+    // this pair or of the wave's next -- and only then stores.
+    uint32_t kn = 0u, gn = 0u, diff = 0u;
+    bool     more = true, pend_last = false;
+    for (;;) {
+        uint32_t res[NW], pos[NW];
+        bool     st[NW];
+        // (vmcnt(0), the wait the first word packed below needs anyway, spelled out: packing is skipped when no lane holds a word, and
+        // behind a skipped wait the compiler would hold every load of the trip's fetches back until the load before it has landed)
+        // (It waits for the slot stores of the trip before as well: stores count in vmcnt on gfx950.)
+        __builtin_amdgcn_s_waitcnt(PP_WAIT_VMCNT0);
+#pragma unroll
+        for (int f = 0; f < NW; f++) {
+            pos[f] = W[f].pos, st[f] = W[f].st;
+            res[f] = st[f] ? pp_finish<AL>(W[f], diff) : 0u;
+        }
+        const Pair done = cur;
+        const bool done_last = pend_last, fetched = more;
+        if (more) {
+            if (gn == 0u) cur = pair_of(kn);
+            if constexpr (TWO)
+                round(cur, 0u, W[0], nullptr);
+            else {
+                round(cur, 2u * gn, W[0], &W[1]);
+                round(cur, 2u * gn + 1u, W[2], &W[3]);
+            }
+            pend_last = gn + 1u == G;
+            if (pend_last)
+                kn += TWO ? 2u : 1u, gn = 0u;
+            else
+                gn += 1u;
+            more = kn < ppw && first + kn < P.chunk_n;
+        }
+#pragma unroll
+        for (int f = 0; f < NW; f++)
+            if (st[f]) done.slot[4u + pos[f]] = res[f];
+        if (done_last) {
+            const unsigned long long bm = __ballot(diff != 0u), mine = TWO ? (0xFFFFFFFFull << (32u * side)) : ~0ull;
+            uint32_t                 status = done.status;
+            if ((bm & mine) != 0ull) status = ST_REDO_BYTES;  // a byte outside ACGT: the byte-compare path takes the pair
+            if (done.have && l == 0u) done.slot[0] = done.nq, done.slot[1] = done.mt, done.slot[2] = status, done.slot[3] = 0u;
+            diff = 0u;
+        }
+        if (!fetched) return;
+    }
+}
+template <bool TWO>
+WFA_DEV void prepack_wave(const KParams &P, uint32_t *__restrict__ out, const uint32_t SW, const uint32_t PW, const uint32_t ppw, const uint32_t wv,
+                          const uint32_t lane) {
+    const uint32_t first = wv * ppw;
+    if (first >= P.chunk_n) return;
+    uint32_t h_nq = 0u, h_mt = 0u;
+    uint64_t h_qo = 0ull, h_to = 0ull;
+    if (lane < ppw && first + lane < P.chunk_n) {
+        const uint32_t pr = P.work ? P.work[first + lane] : P.chunk_first + first + lane;
+        h_nq = P.q_len[pr], h_mt = P.t_len[pr], h_qo = P.q_off[pr], h_to = P.t_off[pr];
+    }
+    const uint32_t lo = (uint32_t)((uintptr_t)P.blob + h_qo) | (uint32_t)((uintptr_t)P.blob + h_to);
+    if (__ballot((lo & 15u) != 0u && lane < ppw) == 0ull)
+        prepack_loop<TWO, true>(P, out, SW, PW, ppw, first, lane, h_nq, h_mt, h_qo, h_to);
+    else
+        prepack_loop<TWO, false>(P, out, SW, PW, ppw, first, lane, h_nq, h_mt, h_qo, h_to);
+}
+__global__ __launch_bounds__(256) void wfa_prepack_kernel(const KParams P, uint32_t *out, uint32_t SW, uint32_t PW, uint32_t ppw) {
+    const uint32_t lane = threadIdx.x & 63u;
+    // (the wave's index as a scalar: what follows from it -- which pairs, how many trips -- is then wave-uniform for the compiler too)
+    const uint32_t wv = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (2u * SW <= 32u)
+        prepack_wave<true>(P, out, SW, PW, ppw, wv, lane);
+    else
+        prepack_wave<false>(P, out, SW, PW, ppw, wv, lane);
+}
+#else
 __global__ __launch_bounds__(256) void wfa_prepack_kernel(const KParams P, uint32_t *out, uint32_t SW, uint32_t PW, uint32_t ppw) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv   = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -1405,6 +1635,7 @@ __global__ __launch_bounds__(256) void wfa_prepack_kernel(const KParams P, uint3
         if (have && v0 == 0u) slot[0] = nq, slot[1] = mt, slot[2] = status, slot[3] = 0u;
     }
 }
+#endif  // WFA_PREPACK_V2
 
 #endif  // WFA_NO_AUX_KERNELS
 

@@ -377,6 +377,8 @@ int align_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_blob, ui
                  uint64_t *ops_needed, hipStream_t st, bool debug_single, uint64_t ops_cursor0 = 0);
 // one workgroup of wfa_backtrace_kernel behind a lone-pair forward launch (wfahip_align_pair)
 hipError_t wfa_launch_backtrace_one(const wfa::KParams &P, hipStream_t st);
+// wfa_prepack_kernel over the pairs P names: slots of 4 + 2 SW words into out, ppw pairs a wave (the first passes; wfahip_debug_prepack)
+hipError_t wfa_launch_prepack(const wfa::KParams &P, uint32_t *out, uint32_t SW, uint32_t ppw, hipStream_t st);
 
 // ---- defined in wfa_score.hip: the launches of the score-only kernels (stage: wfa_matrix.hpp's STAGE_* -- the byte instances, the
 // matrix ones that take the cells of a tile, the packed pair-list ones; the long kernel's list instance takes packed words as it is)

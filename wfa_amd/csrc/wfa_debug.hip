@@ -34,6 +34,42 @@ extern "C" int wfahip_debug_compact_arena(wfahip_ctx *ctx, uint64_t pair, uint32
     return WFAHIP_OK;
 }
 
+// ---- the byte-input packing pass alone (wfa_prepack_kernel, launched by wfa_host.hip's wfa_launch_prepack): the slots of n device-resident
+// pairs, copied to the host.  The slot buffer is filled with 0xA5 first: a word the kernel does not store reads 0xA5A5A5A5.
+static int debug_prepack_impl(wfahip_ctx *ctx, const void *d_blob, const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len,
+                              const void *d_work, uint64_t n, uint32_t seq_words, uint32_t ppw, uint32_t *slots) {
+    if (!ctx || !d_blob || !d_q_off || !d_q_len || !d_t_off || !d_t_len || !slots) return WFAHIP_ERR_BAD_ARG;
+    if (n == 0 || n > 0x7FFFFFFFull || seq_words == 0 || seq_words > (1u << 20) || ppw == 0 || ppw > 32) return WFAHIP_ERR_BAD_ARG;
+    const char *dbg = std::getenv("WFAHIP_DEBUG");
+    if (!dbg || !*dbg || std::strcmp(dbg, "0") == 0) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "wfahip_debug_prepack is a debug aid: set WFAHIP_DEBUG=1 in the environment to use it");
+        return WFAHIP_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * (4u + 2u * seq_words) * 4u;
+    DevBuf       buf;
+    int          rc = ensure(ctx, buf, bytes);
+    if (rc) return rc;
+    KParams P{};
+    P.blob = static_cast<const uint8_t *>(d_blob), P.q_off = static_cast<const uint64_t *>(d_q_off), P.q_len = static_cast<const uint32_t *>(d_q_len);
+    P.t_off = static_cast<const uint64_t *>(d_t_off), P.t_len = static_cast<const uint32_t *>(d_t_len), P.work = static_cast<const uint32_t *>(d_work);
+    P.chunk_first = 0, P.chunk_n = (uint32_t)n, P.lds_seq_words = seq_words;
+    rc = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(buf.p, 0xA5, bytes, ctx->stream));
+        HIP_TRY(wfa_launch_prepack(P, static_cast<uint32_t *>(buf.p), seq_words, ppw, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpy(slots, buf.p, bytes, hipMemcpyDeviceToHost));
+        return WFAHIP_OK;
+    }();
+    release(buf);
+    return rc;
+}
+
+extern "C" int wfahip_debug_prepack(wfahip_ctx *ctx, const void *d_seq_blob, const void *d_q_off, const void *d_q_len, const void *d_t_off,
+                                    const void *d_t_len, const void *d_work, uint64_t n, uint32_t seq_words, uint32_t ppw, uint32_t *slots) {
+    WFAHIP_GUARD(debug_prepack_impl(ctx, d_seq_blob, d_q_off, d_q_len, d_t_off, d_t_len, d_work, n, seq_words, ppw, slots))
+}
+
 // ---- the synthetic dataset generated where it is used (wfa_gen_dev.hpp): no host generation, no upload
 extern "C" int wfahip_generate_pairs_device(wfahip_ctx *ctx, uint64_t seed, uint64_t first_index, uint64_t n_pairs, uint32_t length,
                                             double error_rate, void *d_blob, void *d_q_off, void *d_q_len, void *d_t_off, void *d_t_len,

@@ -1123,8 +1123,7 @@ static int align_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void
                         // (a chunk that gives fewer than four waves per SIMD at four pairs per wave: a wave per pair; short slots pack
                         // two pairs side by side in a wave: they keep four)
                         const uint32_t ppw = (cn <= (uint64_t)ctx->num_cus * 64 && 2u * P.lds_seq_words > 32u) ? 1u : (uint32_t)PREPACK_PAIRS;
-                        hipLaunchKernelGGL(wfa_prepack_kernel, dim3((uint32_t)((cn + 4 * ppw - 1) / (4 * ppw))), dim3(256), 0, st, P,
-                                           static_cast<uint32_t *>(ctx->prepack.p), P.lds_seq_words, pw, ppw);
+                        HIP_TRY(wfa_launch_prepack(P, static_cast<uint32_t *>(ctx->prepack.p), P.lds_seq_words, ppw, st));
                     }
                     HIP_TRY(hipGetLastError());
                     P.prepack = static_cast<const uint32_t *>(ctx->prepack.p), P.prepack_words = pw;
@@ -1726,6 +1725,14 @@ extern "C" int wfahip_align_batch_bounded_device(wfahip_ctx *ctx, const wfahip_p
     BoundScope bound(ctx, max_score);
     return align_device(ctx, p, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs, max_len,
                         d_rec, d_ops, ops_cap, ops_needed, static_cast<hipStream_t>(stream), false);
+}
+
+// wfa_prepack_kernel over the pairs of P (blob, lengths, offsets, work, chunk_first, chunk_n): slots of 4 + 2 SW words each into out,
+// ppw (1 .. 32) pairs a wave
+hipError_t wfa_launch_prepack(const wfa::KParams &P, uint32_t *out, uint32_t SW, uint32_t ppw, hipStream_t st) {
+    if (SW == 0u || ppw == 0u || ppw > 32u || P.chunk_n == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wfa_prepack_kernel, dim3((uint32_t)(((uint64_t)P.chunk_n + 4u * ppw - 1u) / (4u * ppw))), dim3(256), 0, st, P, out, SW, 4u + 2u * SW, ppw);
+    return hipGetLastError();
 }
 
 hipError_t wfa_launch_backtrace_one(const wfa::KParams &P, hipStream_t st) {
