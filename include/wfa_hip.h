@@ -239,7 +239,9 @@ int  wfahip_score_matrix_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint8
  * piece too.  The allocation behind d_seq_blob must therefore be readable up to the next 16-byte boundary behind the last
  * base of every sequence (every device allocator's granularity gives that; a view that ends inside a larger allocation has it
  * as well).  The bytes read there do not influence any result.  This holds for every device entry that takes d_seq_blob
- * (wfahip_align_batch_bounded_device, wfahip_debug_prepack). */
+ * (wfahip_align_batch_bounded_device, wfahip_pack_pairs_device, wfahip_debug_prepack).
+ * Memory behind packed words: the entry that takes device-resident words (wfahip_align_batch_packed_device) needs d_packed
+ * readable for 16 bytes behind its n_words words; those bytes do not influence any result either. */
 int  wfahip_align_batch_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_seq_blob,
                                uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
                                const void *d_t_off, const void *d_t_len, uint64_t n_pairs,
@@ -386,6 +388,64 @@ int  wfahip_revcomp_packed(const uint32_t *src, uint32_t len, uint32_t *dst);
 int  wfahip_align_batch_packed_rc(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
                                   const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                                   const uint8_t *q_rc, uint64_t n_pairs, wfahip_results *out);
+
+/* The packed entries on device-resident input: bytes in HBM -> words -> both strands aligned -> CIGAR text (wfahip_cigar_text_device)
+ * without a sequence byte crossing PCIe.  Conventions as the other device entries: every pointer is a device address on the context's
+ * GPU and stays the caller's; offsets are u64 and lengths u32; stream = hipStream_t to launch on (NULL = the context's own);
+ * synchronous; the inputs are never written.
+ *
+ * wfahip_pack_pairs_device: wfahip_pack_pairs as kernels (wfa_amd/csrc/wfa_packdev.hip; the 16-bytes-to-a-word rule is
+ * wfa_packdev.hpp's).  d_packed, d_q_woff[i] / d_t_woff[i] (u64) and *n_words receive exactly what the host packer writes for the
+ * same bytes: the sequences follow one another as q0, t0, q1, t1, .., each at a word boundary and wfahip_packed_words(len) words
+ * long; a length over WFAHIP_MAX_SEQ_LEN counts as 0 and gives one zero word; the bits of a sequence's last word beyond its last base
+ * and its pad word are zero.  Each sequence is packed on its own: the query of a pair whose target is empty is packed.  No word at
+ * or beyond the total is written.  wfahip_last_timing is not touched.
+ *   WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx; with n_pairs > 0 a null offset, length or woff array; a
+ *     null blob with blob_bytes > 0; a null d_packed with words_cap > 0; n_pairs beyond 0xFFFFFFF0.  n_pairs == 0 returns WFAHIP_OK
+ *     with *n_words = 0 and touches nothing.
+ *   WFAHIP_ERR_BAD_ARG with d_packed untouched, before any kernel that reads a sequence byte is launched: a sequence with
+ *     0 < len <= WFAHIP_MAX_SEQ_LEN does not lie inside [0, blob_bytes) -- found on the device from the offset and length arrays
+ *     alone, compared without a sum that could wrap.
+ *   WFAHIP_ERR_OOM: words_cap is below the total; d_packed is untouched, the woff arrays are filled and *n_words holds the total --
+ *     a caller sizes with d_packed = NULL, words_cap = 0 and calls again.
+ *   WFAHIP_ERR_UNSUPPORTED: a byte INSIDE a packed sequence is outside uppercase ACGT (bytes before, between and behind the
+ *     sequences do not count); the contents of d_packed are then undefined, the woff arrays valid.
+ * Memory behind the blob as for wfahip_align_batch_device: readable up to the next 16-byte boundary behind every sequence; a
+ * sequence whose address is not a multiple of 16 is read in aligned dwords.
+ * Three passes: wfa_packdev_len_kernel (words per pair and the bounds check); an exclusive 64-bit scan in pair order, in place in
+ * d_q_woff; wfa_packdev_pack_kernel, laid out over OUTPUT words -- a workgroup takes a tile of 1 024 words and finds its sequences
+ * by a search in d_q_woff, a lane makes one word from 16 bytes --, so that 500 reads of 50 kbp and 1e6 reads of 100 bases both fill
+ * the GPU.  Scratch lives in the context.  64 bytes of counters are fetched before the pack pass (the total, the bounds verdict) and
+ * again behind it (the ACGT verdict); nothing else crosses PCIe.  WFAHIP_DEBUG_TIMING=1 prints the passes' times to stderr. */
+int  wfahip_pack_pairs_device(wfahip_ctx *ctx, const void *d_seq_blob, uint64_t blob_bytes, const void *d_q_off,
+                              const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n_pairs, void *d_packed,
+                              uint64_t words_cap, void *d_q_woff, void *d_t_woff, uint64_t *n_words, void *stream);
+
+/* wfahip_align_batch_packed_device: full alignment of device-resident words, both strands, optionally bounded.  d_rec, d_ops,
+ * ops_cap, *ops_needed, max_len and WFAHIP_ERR_OOM on a short op buffer are those of wfahip_align_batch_device.  Every record field
+ * and every op a record indexes equals what wfahip_align_batch_packed_rc returns for the same words, offsets, lengths and flags;
+ * with max_score > 0 the result equals wfahip_align_batch_bounded's on the corresponding bytes (a pair over the bound: the record
+ * {8, 0, .., 0}).  d_q_rc: a u8 per pair, NULL = none set; a call whose flags are all zero is the call without flags -- the same
+ * route, no mirror.  Offsets may come in any order, repeat, and name one offset under different lengths and flags; the offsets of an
+ * empty or too long pair are never looked at.
+ * The caller's arrays are never written: the byte offsets the kernels take, and the mirror addresses of flagged queries, go into
+ * scratch of the context, and so does the byte blob the byte-reading passes expand their pairs into (16 n_words + 32 bytes, 32
+ * n_words + 96 with a flag set; nothing is expanded up front unless option "unpack_all" is 1).
+ * Memory behind the words: d_packed must be readable for 16 bytes behind its n_words words (the slack the host entry gives its own
+ * staging buffer); what is read there influences no result.
+ *   WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx or p; with n_pairs > 0 a null offset, length or d_rec
+ *     pointer; a null d_packed with n_words > 0; a null d_ops with ops_cap > 0.  Then the params as wfahip_align_batch checks them;
+ *     n_pairs == 0 returns WFAHIP_OK.
+ *   WFAHIP_ERR_BAD_ARG with d_rec and d_ops untouched, before any kernel that reads a packed word is launched: a pair, neither empty
+ *     nor too long, has a sequence with woff + wfahip_packed_words(len) > n_words (compared without a sum that could wrap).
+ * One kernel, wfa_packed_check_kernel, finds that on the device, and with it the longest read (max_len = 0), whether any flag is set,
+ * and the scaled offsets; one 64-byte fetch brings its verdicts to the host.  wfahip_last_timing as after the host entry: for a
+ * batch that entry does not slice (under 200 000 pairs), main_kernel_kind, n_packed_pairs and n_retried_pairs are the host entry's
+ * on the same input when max_len is 0. */
+int  wfahip_align_batch_packed_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words,
+                                      const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len,
+                                      const void *d_q_rc, uint64_t n_pairs, uint32_t max_len, uint32_t max_score, void *d_rec,
+                                      void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, void *stream);
 
 /* CIGAR text, rendered where the ops are.  AlignmentResult.CIGAR(onlyAlignedRegion) (wfa_cigar.go:217-255) of every pair of a
  * batch as bytes: what a SAM / PAF writer puts into a file.  The rule (wfa_amd/csrc/wfa_cigar.hpp, one source for the kernels and

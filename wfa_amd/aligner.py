@@ -593,6 +593,93 @@ class Aligner:
         L.check(rc, "wfahip_cigar_text_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return text, off
 
+    # -- new: the packed entries on device-resident data (include/wfa_hip.h: wfahip_pack_pairs_device, wfahip_align_batch_packed_device)
+    def pack_tensors(self, blob, q_off, q_len, t_off, t_len, stream=None):
+        """pack_pairs for a batch that lives on the aligner's GPU (include/wfa_hip.h: wfahip_pack_pairs_device): torch tensors in, as
+        score_tensors takes them; out (packed int32, q_woff int64, t_woff int64) on the same device -- word for word, offset for
+        offset what pack_pairs returns for the same bytes (the C-ABI's uint32 / uint64 bit for bit).  packed has four words of slack
+        behind the words the offsets name (zero; packed.numel() - 4 is the total), so that it goes straight into
+        align_tensors_packed.  Sized by one call and written by a second.  Raises WfaHipError, as pack_pairs does: ERR_UNSUPPORTED
+        for a byte outside ACGT inside a sequence, ERR_BAD_ARG for a sequence outside the blob.  The inputs are never written.
+        stream and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("blob", blob, torch.uint8)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(q_len.numel())
+        if q_off.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors differ in length")
+        stream = self._want_stream(stream, dev)
+        q_woff = torch.zeros(n, dtype=torch.int64, device=dev)
+        t_woff = torch.zeros(n, dtype=torch.int64, device=dev)
+        if n == 0:
+            return torch.zeros(4, dtype=torch.int32, device=dev), q_woff, t_woff
+        lib = L.lib()
+        n_words = C.c_uint64(0)
+
+        def call(p):
+            self._order_after_torch(stream, dev)  # (the fills ran on torch's current stream)
+            return lib.wfahip_pack_pairs_device(self._ctx, blob.data_ptr() if blob.numel() else None, blob.numel(), q_off.data_ptr(),
+                                                q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n, p.data_ptr() if p is not None else None,
+                                                p.numel() - 4 if p is not None else 0, q_woff.data_ptr(), t_woff.data_ptr(),
+                                                C.byref(n_words), stream.cuda_stream)
+        rc = call(None)  # the sizing call: every pair takes two words at least, so it ends in ERR_OOM with the total, or in an error
+        packed = None
+        if rc == L.ERR_OOM:
+            packed = torch.zeros(n_words.value + 4, dtype=torch.int32, device=dev)
+            rc = call(packed)
+        L.check(rc, "wfahip_pack_pairs_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return packed, q_woff, t_woff
+
+    def align_tensors_packed(self, packed, q_woff, q_len, t_woff, t_len, q_rc=None, max_score: int = 0, stream=None):
+        """align_tensors over 2-bit words that live on the aligner's GPU (include/wfa_hip.h: wfahip_align_batch_packed_device): packed
+        int32 with at least four words of slack behind the words the offsets name (pack_tensors' output has them), q_woff / t_woff
+        int64, q_len / t_len int32, q_rc an optional uint8 tensor of one flag per pair (non-zero: the pair aligns the reverse
+        complement of its query, made on the GPU from the same words).  Returns (rec, ops) as align_tensors does -- every record
+        field and every op equals align_arrays_packed_rc's on the same words, and with max_score > 0 align_arrays(max_score=)'s on
+        the bytes -- and they go into cigar_tensors unchanged.  The inputs are never written.  Op-capacity retry, stream and
+        ValueErrors as align_tensors."""
+        import torch
+        dev = self._want_tensor("packed", packed, torch.int32)
+        for name, t, dtype in (("q_woff", q_woff, torch.int64), ("q_len", q_len, torch.int32), ("t_woff", t_woff, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(q_len.numel())
+        if q_woff.numel() != n or t_woff.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors differ in length")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        if packed.numel() < 4:
+            raise ValueError("packed must hold four words of slack behind its words")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        stream = self._want_stream(stream, dev)
+        rec = torch.zeros((n, L.REC_WORDS), dtype=torch.int32, device=dev)
+        if n == 0:
+            return rec, torch.zeros(0, dtype=torch.int64, device=dev)
+        n_words = int(packed.numel()) - 4
+        # CIGAR ops are merged runs: the host entry's first guess of (n + m) / 4 + 8 per pair
+        ops_cap = (int(q_len.sum(dtype=torch.int64)) + int(t_len.sum(dtype=torch.int64))) // 4 + 8 * n + 1024
+        prm = self._params()
+        lib = L.lib()
+        for _attempt in range(6):
+            ops = torch.zeros(ops_cap, dtype=torch.int64, device=dev)
+            self._order_after_torch(stream, dev)  # (the fills above ran on torch's current stream)
+            needed = C.c_uint64(0)
+            rc = lib.wfahip_align_batch_packed_device(self._ctx, C.byref(prm), packed.data_ptr(), n_words, q_woff.data_ptr(), q_len.data_ptr(),
+                                                      t_woff.data_ptr(), t_len.data_ptr(), q_rc.data_ptr() if q_rc is not None else None, n, 0,
+                                                      int(max_score), rec.data_ptr(), ops.data_ptr(), ops_cap, C.byref(needed),
+                                                      stream.cuda_stream)
+            if rc == L.ERR_OOM and needed.value > ops_cap:
+                ops_cap = needed.value + needed.value // 3 + 1024
+                continue
+            break
+        L.check(rc, "wfahip_align_batch_packed_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return rec, ops
+
     def alignment_text_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, out=None, stream=None):
         """AlignmentResult.AlignmentText(q, t, only_aligned) of every pair of (rec, ops) -- align_tensors' output -- over the blob
         and the four tensors that call was given, rendered on the aligner's GPU (include/wfa_hip.h: wfahip_alignment_text_device):

@@ -2,12 +2,13 @@
 // macros of the C-ABI, and the declarations of the functions one unit defines for the others.
 //   wfa_host.hip   the router: context life cycle, options, wfahip_align_batch_device -- the sub-wave passes and the
 //                  long-pair ladder behind it (align_device; the plan of a ladder job is host-only arithmetic: wfa_ladder.hpp)
-//   wfa_entry.hip  the host entries: wfahip_align_batch (sliced upload / alignment / download), packed input,
+//   wfa_entry.hip  the host entries: wfahip_align_batch (sliced upload / alignment / download), packed input (host and device-resident),
 //                  wfahip_align_pair, submit / collect, the results cache
 //   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_packed, wfahip_score_batch_device, wfahip_score_matrix -- a
 //                  router each over the launch section, the geometry and the full-path fallback they share
 //   wfa_cigar.hip  CIGAR text: the three rendering kernels, wfahip_cigar_text_device, the host renderer wfahip_cigar_text, wfahip_align_batch_text;
 //                  the display rows on the same scan: wfahip_alignment_text_device, the host renderer wfahip_alignment_text
+//   wfa_packdev.hip  the 2-bit packer as kernels: wfahip_pack_pairs_device (its consumer wfahip_align_batch_packed_device is wfa_entry.hip's)
 //   wfa_debug.hip  parity and measurement aids: wavefront dumps, the compact arenas, the device-side generator, the clock probe,
 //                  the read-back behind a launch of the team kernels
 #pragma once
@@ -187,6 +188,8 @@ struct wfahip_ctx {
     uint64_t      sd_n_words = 0, sd_n_listed = 0;   // ... what its last call left in mx_words / mx_seq (wfahip_debug_score_device_list)
     DevBuf        cig;                            // wfahip_cigar_text_device, wfahip_alignment_text_device (wfa_cigar.hip): its counters, the scan's block sums, the trimmed op range of every pair
     DevBuf        cig_text, cig_off;              // wfahip_align_batch_text: the batch's text and its offsets, until they are downloaded
+    DevBuf        pkd;                            // wfahip_pack_pairs_device (wfa_packdev.hip): its counters and the scan's block sums; wfahip_align_batch_packed_device
+                                                  // (wfa_entry.hip): the verdicts of its check kernel
     DevBuf        mx_out;                         // ... {status, score} of two tiles (double-buffered: tile c downloads while tile c + 1 runs)
     uint2        *mx_pin       = nullptr;         // ... their page-locked host copies
     size_t        mx_pin_bytes = 0;

@@ -835,6 +835,117 @@ extern "C" int wfahip_align_batch_packed(wfahip_ctx *ctx, const wfahip_params *p
     return wfahip_align_batch_packed_rc(ctx, p, packed, n_words, q_woff, q_len, t_woff, t_len, nullptr, n_pairs, out);
 }
 
+// ---- pre-packed input that already lives on the device: wfahip_align_batch_packed_device.  The host entry above uploads the caller's
+// words and arrays and scales its own copies of the offsets in place; here the caller's arrays are device memory that is only read.
+// ONE small kernel, a lane per pair, does what the host entry's loop over the pairs and wfa_scale_offsets_kernel do together: the
+// bounds check of every pair that is neither empty nor too long (woff + wfahip_packed_words(len) <= n_words, compared without a sum
+// that could wrap), the longest read of those pairs, whether any flag is set, and the byte offsets -- a flagged query's in the mirror
+// (wfa_rc.hpp) -- into scratch of the context.  Its verdicts come to the host in one 64-byte fetch, before any kernel reads a word.
+namespace {
+enum { PDC_BAD_RANGE = 0, PDC_MAX_LEN = 1, PDC_ANY_RC = 2, PDC_WORDS = 16 };  // u32 counters: 64 bytes
+static_assert(PDC_WORDS <= HPIN_REDO, "the counters fit the head of the pinned block");
+}  // namespace
+
+__global__ __launch_bounds__(256) void wfa_packed_check_kernel(const uint64_t *__restrict__ q_woff, const uint64_t *__restrict__ t_woff,
+                                                               const uint32_t *__restrict__ q_len, const uint32_t *__restrict__ t_len,
+                                                               const uint8_t *__restrict__ rc, uint64_t n, uint64_t n_words, uint64_t top,
+                                                               uint64_t *__restrict__ q_off, uint64_t *__restrict__ t_off, uint32_t *ctl) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t       longest = 0u, bad = 0u, flag = 0u;
+    if (i < n) {
+        const uint32_t ql = q_len[i], tl = t_len[i];
+        const uint64_t qw = q_woff[i], tw = t_woff[i];
+        const bool     v  = ql != 0u && tl != 0u && ql <= WFAHIP_MAX_SEQ_LEN && tl <= WFAHIP_MAX_SEQ_LEN;
+        flag = rc != nullptr && rc[i] != 0;
+        if (v) {  // (an empty or too long pair's offsets are never looked at: what is written for them is never read)
+            const uint64_t nq = ((uint64_t)ql + 15u) / 16u + 1u, nt = ((uint64_t)tl + 15u) / 16u + 1u;
+            bad     = qw > n_words || nq > n_words - qw || tw > n_words || nt > n_words - tw;
+            longest = ql > tl ? ql : tl;
+        }
+        t_off[i] = tw * 16u;
+        q_off[i] = v && flag ? rc_mirror_off(top, qw, ql) : qw * 16u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t m = (uint32_t)__shfl_xor((int)longest, o, 64);
+        longest          = m > longest ? m : longest;
+    }
+    if ((threadIdx.x & 63u) == 0u && longest != 0u) atomicMax(&ctl[PDC_MAX_LEN], longest);
+    if (bad) atomicOr(&ctl[PDC_BAD_RANGE], 1u);
+    if (flag) atomicOr(&ctl[PDC_ANY_RC], 1u);
+}
+
+static int align_packed_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words, const void *d_q_woff,
+                                    const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n_pairs,
+                                    uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, hipStream_t st) {
+    // (the entry below has refused null pointers, bad params and the empty batch)
+    int rc = WFAHIP_OK;
+    if (ops_needed) *ops_needed = 0;
+    if (n_pairs >0xFFFFFFF0ull || n_words > (1ull << 58)) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit; 16 n_words is a byte count)
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    struct PkGuard {  // the caller's words are the alignment's input for the duration of this call only
+        wfahip_ctx *c;
+        ~PkGuard() { c->pk_words = nullptr, c->pk_rc = nullptr, c->pk_top = 0; }
+    } pk_guard{ctx};
+    if ((rc = ensure(ctx, ctx->in_qoff, n_pairs * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->in_toff, n_pairs * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->pkd, PDC_WORDS * 4))) return rc;
+    uint32_t *const d_ctl  = static_cast<uint32_t *>(ctx->pkd.p);
+    const uint64_t  rc_top = rc_mirror_top(n_words);
+    HIP_TRY(hipMemsetAsync(d_ctl, 0, PDC_WORDS * 4, st));
+    hipLaunchKernelGGL(wfa_packed_check_kernel, dim3((uint32_t)((n_pairs + 255) / 256)), dim3(256), 0, st, static_cast<const uint64_t *>(d_q_woff),
+                       static_cast<const uint64_t *>(d_t_woff), static_cast<const uint32_t *>(d_q_len), static_cast<const uint32_t *>(d_t_len),
+                       static_cast<const uint8_t *>(d_q_rc), n_pairs, n_words, rc_top, static_cast<uint64_t *>(ctx->in_qoff.p),
+                       static_cast<uint64_t *>(ctx->in_toff.p), d_ctl);
+    HIP_TRY(hipGetLastError());
+    // (through the context's pinned block: a pageable copy of 64 bytes costs 0.3 ms)
+    HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, d_ctl, PDC_WORDS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t hc[PDC_WORDS];
+    std::memcpy(hc, ctx->hpin + HPIN_CTRL, sizeof hc);
+    if (hc[PDC_BAD_RANGE] != 0u) return WFAHIP_ERR_BAD_ARG;  // (no word has been read, d_rec and d_ops are untouched)
+    if (max_len == 0) max_len = std::max(1u, hc[PDC_MAX_LEN]);  // (the host entry's bound: the longest read of the pairs that will be aligned)
+    // a call whose flags are all zero is the call without flags: the same route, no mirror
+    const bool     any_rc     = hc[PDC_ANY_RC] != 0u;
+    const uint64_t blob_bytes = n_words * 16;
+    // the blob the byte-reading passes expand their pairs into (+ the mirror, where the flagged queries' reverse complements are read)
+    if ((rc = ensure(ctx, ctx->in_blob, any_rc ? rc_mirror_bytes(n_words) : blob_bytes + 32))) return rc;
+    if (any_rc) ctx->pk_rc = static_cast<const uint8_t *>(d_q_rc), ctx->pk_top = rc_top;
+    // (n_words == 0: every pair is empty or too long and no word is read -- the kernels still get an address)
+    const uint32_t *const words = d_packed ? static_cast<const uint32_t *>(d_packed) : static_cast<const uint32_t *>(ctx->in_blob.p);
+    if (ctx->opt_unpack_all == 0) {
+        ctx->pk_words = words;
+    } else if (n_words) {  // option "unpack_all": everything, and with flags its mirror, expanded up front
+        hipLaunchKernelGGL(wfa_unpack_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, st, words, static_cast<uint4 *>(ctx->in_blob.p),
+                           (uint64_t)0, n_words);
+        if (any_rc)
+            hipLaunchKernelGGL(wfa_unpack_mirror_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, st, words,
+                               static_cast<uint8_t *>(ctx->in_blob.p), rc_top, (uint64_t)0, n_words);
+        HIP_TRY(hipGetLastError());
+    }
+    return align_device(ctx, p, ctx->in_blob.p, blob_bytes, ctx->in_qoff.p, d_q_len, ctx->in_toff.p, d_t_len, n_pairs, max_len, d_rec, d_ops,
+                        ops_cap, ops_needed, st, false);
+}
+
+extern "C" int wfahip_align_batch_packed_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words,
+                                                const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len,
+                                                const void *d_q_rc, uint64_t n_pairs, uint32_t max_len, uint32_t max_score, void *d_rec,
+                                                void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, void *stream) {
+    if (!ctx || !p) return WFAHIP_ERR_BAD_ARG;  // (before the context is touched)
+    if (n_pairs && (!d_q_woff || !d_q_len || !d_t_woff || !d_t_len || !d_rec)) return WFAHIP_ERR_BAD_ARG;
+    if ((!d_packed && n_words) || (!d_ops && ops_cap)) return WFAHIP_ERR_BAD_ARG;
+    const int rc = check_params(p);
+    if (rc) return rc;
+    if (n_pairs == 0) {
+        if (ops_needed) *ops_needed = 0;
+        return WFAHIP_OK;
+    }
+    BoundScope bound(ctx, max_score);  // (the bound align_device stops and filters by, on every retry)
+    WFAHIP_GUARD(align_packed_device_impl(ctx, p, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc, n_pairs, max_len, d_rec, d_ops,
+                                          ops_cap, ops_needed, static_cast<hipStream_t>(stream)))
+}
+
 extern "C" uint64_t wfahip_packed_words(uint32_t len) { return ((uint64_t)len + 15) / 16 + 1; }  // (+1: the pad word the kernels' 16-base windows may read)
 
 // Host-side packer: n_pairs (query, target) byte sequences -> 2-bit words, every sequence at a word boundary, in pair
