@@ -105,6 +105,22 @@ static WFA_DEV unsigned long long duo_lanes(bool b) {
 }
 static WFA_DEV bool duo_lane_of(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }  // the lane's bit: no instruction
 
+// The kernel's arguments, read again where cold code needs them (WFA_DUO_SCALAR, wfa_duo_cfg.hpp).  KParams is the kernel's one argument, so it
+// lies at the start of the kernel-argument segment; a field read through this pointer is a scalar load from constant memory.  The empty asm makes
+// the address opaque at the place of the call: the load cannot be hoisted out of the cold block that asks for it, and the field takes no scalar
+// register while the score steps run.
+template <bool ON>
+static WFA_DEV uint32_t duo_uniform(uint32_t x) {
+    if constexpr (ON) return (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+    else return x;
+}
+using DuoArgs = const __attribute__((address_space(4))) KParams;
+static WFA_DEV DuoArgs *duo_cold_args() {
+    DuoArgs *p = (DuoArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 // DX / DOE: the penalty shape, as in wfa_blk_kernel (R = max(DX, DOE) rows in the M ring)
 // PK: the rings as 16-bit pairs -- a lane's diagonals (p0, p1) in one register and (p2, p3) in another, the lower diagonal in the
 // low half -- and WF_NEXT's rejection-free path two diagonals per instruction (wide_next2()); wfa_duo_kernel runs this form.
@@ -118,6 +134,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     // the uniform tests as scalar code and the lane constants of set_derived() (wfa_duo_cfg.hpp).  The packed kernel only: the 32-bit-ring
     // reference with three ring rows needs two more scalar registers in this form, and stays as it was
     constexpr bool UNI = WFA_DUO_UNIFORM != 0 && PK;
+    // wave-uniform state and cold arguments off the step's path (wfa_duo_cfg.hpp): the packed kernel in its uniform form only
+    constexpr int  SCA = WFA_DUO_SCALAR != 0 && UNI ? WFA_DUO_SCALAR_ITEMS : 0;
+    constexpr bool SC_ARGS = (SCA & 1) != 0, SC_UNI = (SCA & 2) != 0, SC_SLOW = (SCA & 4) != 0, SC_NZ = (SCA & 8) != 0, SC_SI = (SCA & 16) != 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int  lane = threadIdx.x, l7 = lane & 7, l15 = lane & 15;
     const bool hi_half = (lane & 8) != 0;
@@ -145,6 +164,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     // read the masks -- `run &&` is a scalar AND, the free halves are ~run_m, DuoRed's fourth stage takes wide_m as it is -- and compare neither
     // st nor wide again.  Between a change and its set_derived() the lane values are the truth, and the code there reads those.
     unsigned long long run_m = 0ull, wide_m = 0ull;
+    // (SCA: and the lanes with `slow`.  Written by set_derived() like the other two, and by the step's rare branch that sets the flag; the lane value
+    // stays the truth for the park records and for the lanes that join a widening neighbour)
+    unsigned long long slow_m = 0ull;
     // ---- per-lane values derived from them
     int             j = l7, k0 = 0;
     // (UNI: what the step would otherwise form again every time, kept in registers -- the kernel has sixteen to spare under the 128 of four waves per
@@ -200,8 +222,8 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     uint32_t pf_next = P.duo_claim > 1u ? blockIdx.x * 8u : 0u;
     uint32_t pf_end  = P.duo_claim > 1u ? umin2(pf_next + 8u, P.chunk_n) : 0u;
     const auto claim_base = [&]() { return ((pf >> PF_CLAIM_SHIFT) & 15u) > 1u ? (pf >> PF_GRID_SHIFT) * 8u : 0u; };
-    const auto claim_fetches = [&]() {
-        const uint32_t rem = P.chunk_n > pf_next ? P.chunk_n - pf_next : 0u;
+    const auto claim_fetches = [&](uint32_t chunk_n) {
+        const uint32_t rem = chunk_n > pf_next ? chunk_n - pf_next : 0u;
         return umax2(1u, umin2((pf >> PF_CLAIM_SHIFT) & 15u, rem / (2u * (pf >> PF_GRID_SHIFT) * FP)));
     };
     uint4    pf_w = make_uint4(0u, 0u, 0u, 0u);  // (a slot is at most 256 words: one 16-byte load per lane)
@@ -213,7 +235,21 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                                                             // WF_EXTEND's continuation, its outer rounds (a candidate per lane), its inner rounds (windows)
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
 #endif
-    const auto pair_of = [&](uint32_t idx) { return P.work ? P.work[idx] : P.chunk_first + idx; };
+    // The arguments that only cold code reads -- arena, pair_meta, the redo list, work, chunk_first, queue_head, chunk_n, prepack, g, census --
+    // SCA: from the kernel-argument segment at the point of use, once per pair or less; else from the registers they occupy all along
+    const auto args = [&]() {
+        if constexpr (SC_ARGS) return duo_cold_args();
+        else return &P;
+    };
+    const auto pair_of = [&](const auto *A, uint32_t idx) { return A->work ? A->work[idx] : A->chunk_first + idx; };
+    const auto redo = [&](const auto *A, uint32_t pair, uint32_t status) {  // (push_redo(), wfa_device.hpp)
+        const uint32_t i = atomicAdd(A->redo_count, 1u);
+        A->redo_list[2u * i]      = pair;
+        A->redo_list[2u * i + 1u] = status;
+    };
+    // SCA: a wave-uniform value said to be so where it is written (fill(), the evict loop, the hand-on branch, the prefetch stages, the finish:
+    // all cold or once per fetch), not at the head of every refill()
+    const auto uni = [](uint32_t x) __attribute__((always_inline)) { return duo_uniform<SC_UNI>(x); };
     const auto dn1 = [&](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true) & mdn; };
     const auto up1 = [&](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x101, 0xf, 0xf, true) & mup; };
     const auto other_half = [&](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, true); };  // row_ror:8
@@ -221,6 +257,9 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
     const auto kx = [&](int p) { return UNI && p != 0 ? kp[p] : k0 + p; };
     const auto set_derived = [&]() {
         if constexpr (UNI) run_m = duo_lanes(st == 1), wide_m = duo_lanes(wide);
+        if constexpr (SC_SLOW) slow_m = duo_lanes(slow);
+        const auto *const A = args();
+        const uint64_t acap = A->arena_words;
         j   = wide ? l15 : l7;
         mdn = j == 0 ? 0u : ~0u;
         mup = j == (wide ? 15 : 7) ? 0u : ~0u;
@@ -242,11 +281,11 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         lq   = lds + sbuf * PW + 4u;
         lt   = lq + SW;
         if constexpr (DUO_ARENA_FMT == 10u)  // [pair of groups][score / 8][group & 1][score & 7]: the lane's base; the score's part is added at the store
-            rowp = P.arena + (uint64_t)pidx * cap + (((uint32_t)k0 & 56u) >> 3) * (uint32_t)(rows_cap * 4) + (((uint32_t)k0 >> 2) & 1u) * 16u;
+            rowp = A->arena + (uint64_t)pidx * acap + (((uint32_t)k0 & 56u) >> 3) * (uint32_t)(rows_cap * 4) + (((uint32_t)k0 >> 2) & 1u) * 16u;
         else if constexpr (DUO_ARENA_FMT == 9u)  // [group of four diagonals][score]: the lane's group, then 8 bytes per score
-            rowp = P.arena + (uint64_t)pidx * cap + (((uint32_t)k0 & 60u) >> 2) * (uint32_t)(rows_cap * 2) + si * 2u;
+            rowp = A->arena + (uint64_t)pidx * acap + (((uint32_t)k0 & 60u) >> 2) * (uint32_t)(rows_cap * 2) + si * 2u;
         else
-            rowp = P.arena + (uint64_t)pidx * cap + (uint64_t)(si >> 3) * 256u + (si & 7u) * 2u;
+            rowp = A->arena + (uint64_t)pidx * acap + (uint64_t)(si >> 3) * 256u + (si & 7u) * 2u;
     };
     const auto clear_rings = [&]() {
 #pragma unroll
@@ -279,7 +318,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             const bool     mine = ((uint32_t)lane >> 3) == oct;
             if (park_used != 0u) {
                 const uint32_t rec = (uint32_t)__builtin_ctz(park_used);
-                park_used &= park_used - 1u;
+                park_used = uni(park_used & (park_used - 1u));
                 WFA_EVT(4, 1);
                 const uint32_t *const pr = park0 + rec * DUO_PARK_WORDS;
                 if (mine) {
@@ -315,21 +354,22 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             }
             // the next staged pair: header {n, m, status, -} + packed words, in the lowest buffer of st_mask
             pf_buf   = (uint32_t)__builtin_ctz(st_mask);
-            st_mask &= st_mask - 1u;
+            st_mask = uni(st_mask & (st_mask - 1u));
             const uint32_t this_idx = pf_idx;
-            pf_idx += 1u;
+            pf_idx = uni(pf_idx + 1u);
             const uint32_t *const hb = lds + pf_buf * PW;
             // (readfirstlane: an LDS load counts as divergent, and a branch on it would turn this wave-uniform loop and
             // every scalar it updates -- the prefetch flags, the buffer masks -- into per-lane values)
             const uint32_t nq = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[0]), mt = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[1]);
             const uint32_t status = (uint32_t)__builtin_amdgcn_readfirstlane((int)hb[2]);
-            if (st_mask == 0u) pf &= ~PF_STAGED;
+            if (st_mask == 0u) pf = uni(pf & ~PF_STAGED);
             if (status != ST_PENDING) {  // empty / too long / does not fit / a byte outside ACGT: no alignment here
                 if (lane == 0) {
-                    P.pair_meta[this_idx] = make_uint4(status, 0u, 0u, 0u);
-                    if (status >= ST_REDO_BYTES) push_redo(P, pair_of(this_idx), status);
+                    const auto *const A = args();
+                    A->pair_meta[this_idx] = make_uint4(status, 0u, 0u, 0u);
+                    if (status >= ST_REDO_BYTES) redo(A, pair_of(A, this_idx), status);
                 }
-                buf_free |= 1u << pf_buf;
+                buf_free = uni(buf_free | (1u << pf_buf));
                 continue;  // (the half stays free; the next staged pair will take it)
             }
             WFA_EVT(5, 1);
@@ -354,12 +394,14 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         constexpr int NEW = (ph + R - 1) % R;  // ring slot of the newest row; M[ph] is the oldest (replaced by the next step)
         // ---------------------------------------------------------------- prefetch of the next pair, one stage per call
         // (wave-uniform by construction; said so explicitly, or hipcc keeps them in vector registers)
-        pf        = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf);
-        park_used = (uint32_t)__builtin_amdgcn_readfirstlane((int)park_used);
-        buf_free  = (uint32_t)__builtin_amdgcn_readfirstlane((int)buf_free);
-        st_mask   = (uint32_t)__builtin_amdgcn_readfirstlane((int)st_mask);
-        pf_next   = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_next);
-        pf_end    = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_end);
+        if constexpr (!SC_UNI) {
+            pf        = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf);
+            park_used = (uint32_t)__builtin_amdgcn_readfirstlane((int)park_used);
+            buf_free  = (uint32_t)__builtin_amdgcn_readfirstlane((int)buf_free);
+            st_mask   = (uint32_t)__builtin_amdgcn_readfirstlane((int)st_mask);
+            pf_next   = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_next);
+            pf_end    = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_end);
+        }
         if ((pf & (PF_LD | PF_STAGED)) == PF_LD) {  // the words loaded an iteration ago go to spare LDS buffers, one per pair
             // pairs this fetch really holds: the stage below moved pf_next past them an iteration ago, and nothing has moved it since
             const uint32_t cnt = pf_next - pf_ld_idx;
@@ -369,7 +411,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 uint32_t f = buf_free;
                 for (uint32_t c = 0; c < cnt; c++) st_mask |= f & (0u - f), f &= f - 1u;
             }
-            buf_free &= ~st_mask;
+            st_mask = uni(st_mask), buf_free = uni(buf_free & ~st_mask);
             const uint32_t w0 = (uint32_t)lane * 4u, slot = w0 / PW;  // (a slot is a whole number of 16-byte pieces)
             if (slot < cnt) {
                 uint32_t f = st_mask;
@@ -377,23 +419,26 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                 const uint32_t b = (uint32_t)__builtin_ctz(f);
                 *reinterpret_cast<uint4 *>(lds + b * PW + (w0 - slot * PW)) = pf_w;
             }
-            pf_idx = pf_ld_idx, pf = (pf | PF_STAGED) & ~PF_LD;
+            pf_idx = uni(pf_ld_idx), pf = uni((pf | PF_STAGED) & ~PF_LD);
         }
         if ((pf & (PF_TOK | PF_LD)) == PF_TOK) {  // the queue entry claimed an iteration ago: its slot's words into registers
+            const auto *const A = args();
             if (pf_next >= pf_end) {  // (the wave's range was empty: the token is an atomic's result, the start of a new range)
+                const uint32_t chunk_n = A->chunk_n;
                 const uint32_t tok = (uint32_t)__builtin_amdgcn_readfirstlane((int)pf_tok) + claim_base();
-                const uint32_t blk = claim_fetches() * FP;  // (what the atomic added: pf_next has not moved since)
-                pf_next = tok, pf_end = tok < P.chunk_n ? umin2(tok + blk, P.chunk_n) : tok;
+                const uint32_t blk = claim_fetches(chunk_n) * FP;  // (what the atomic added: pf_next has not moved since)
+                pf_next = tok, pf_end = uni(tok < chunk_n ? umin2(tok + blk, chunk_n) : tok);
             }
-            pf_ld_idx = pf_next;
+            pf_ld_idx = uni(pf_next);
             const bool have = pf_next < pf_end;  // (an empty range: the token was at or past chunk_n)
             if (have) {
-                const uint32_t *const slot = P.prepack + (uint64_t)pf_ld_idx * PW;
+                const uint32_t *const slot = A->prepack + (uint64_t)pf_ld_idx * PW;
                 const uint32_t cnt = umin2(FP, pf_end - pf_next);  // (the last fetch of a range or of the chunk may be partial)
                 pf_next += cnt;
                 if ((uint32_t)lane * 4u < cnt * PW) pf_w = *reinterpret_cast<const uint4 *>(slot + lane * 4);
             }
-            pf = (pf & ~PF_TOK) | (have ? PF_LD : PF_DRY);
+            pf_next = uni(pf_next);
+            pf = uni((pf & ~PF_TOK) | (have ? PF_LD : PF_DRY));
         }
         if ((pf & (PF_TOK | PF_DRY)) == 0u) {
             // The next fetch: from the wave's range when it has entries left -- no memory operation, the token is pf_next -- else
@@ -405,10 +450,11 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             // does not know the result is outstanding, and a register copy or a spill of it before the wait would read
             // garbage.  Correct either way with this form; the flag only buys the overlap.)
             if (pf_next >= pf_end) {
-                const uint32_t blk = claim_fetches() * FP;
-                if (lane == 0) pf_tok = atomicAdd(P.queue_head, blk);
+                const auto *const A = args();
+                const uint32_t blk = claim_fetches(A->chunk_n) * FP;
+                if (lane == 0) pf_tok = atomicAdd(A->queue_head, blk);
             }
-            pf |= PF_TOK;
+            pf = uni(pf | PF_TOK);
         }
         // ---------------------------------------------------------------- does anything have to change?
         // (a loop: a parked pair that had asked to widen itself asks again as soon as it has resumed, before it steps)
@@ -480,7 +526,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
                     continue;
                 }
                 const uint32_t rec = (uint32_t)__builtin_ctz(~park_used);
-                park_used |= 1u << rec;
+                park_used = uni(park_used | (1u << rec));
                 WFA_EVT(3, 1);
                 uint32_t *const pr = park0 + rec * DUO_PARK_WORDS;
                 if (mine) {
@@ -522,10 +568,11 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             if (__ballot(act == 4) != 0ull) {
                 WFA_EVT(7, __builtin_popcountll(__ballot(act == 4 && j == 0)));
                 if (act == 4 && j == 0) {
-                    P.pair_meta[pidx] = make_uint4(ST_REDO_BAND, 0u, 0u, 0u);
-                    push_redo(P, pair_of(pidx), ST_REDO_BAND);
+                    const auto *const A = args();
+                    A->pair_meta[pidx] = make_uint4(ST_REDO_BAND, 0u, 0u, 0u);
+                    redo(A, pair_of(A, pidx), ST_REDO_BAND);
                 }
-                buf_free |= or_halves(act == 4 ? (1u << sbuf) : 0u);
+                buf_free = uni(or_halves(act == 4 ? (1u << sbuf) : 0u) | buf_free);
                 if (act == 4) {
                     st = 0, wide = false;
                     clear_rings();
@@ -634,7 +681,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         // register, k+1 of its last the low half of the upper lane's first)
         const uint32_t a_edge = dn1(Mo[RW - 1]), b_edge = dn1(I[RW - 1]);
         const uint32_t c_edge = up1(Mo[0]), d_edge = up1(D[0]);
-        const bool     slow_any = any_run(slow);
+        const bool     slow_any = SC_SLOW ? (slow_m & run_m) != 0ull : any_run(slow);  // (SCA: the stored flag's mask, no compare of it)
         // the path with rejections near a sequence end: 32-bit sources in, 32-bit cells out
         const auto next_slow = [&](const uint32_t(&Mo4)[PP], const uint32_t(&I4)[PP], const uint32_t(&D4)[PP], const uint32_t(&Mx4)[PP],
                                    uint32_t ae, uint32_t be, uint32_t ce, uint32_t de, uint32_t(&nI4)[PP], uint32_t(&nD4)[PP],
@@ -738,13 +785,23 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         // (UNI: read again at the finish -- the mask, not a second compare)
         const unsigned long long room_m = UNI ? run_m & duo_lanes((int)si >= rows_cap) : 0ull;
         const bool no_room = UNI ? duo_lane_of(room_m) : run && (int)si >= rows_cap;
+        // (SCA: the lanes whose cell p exists, the four compares WF_EXTEND and the band need anyway, made before the store: "has the lane a cell to
+        // store" is their OR on the scalar unit, not an OR of the four offsets and a fifth compare)
+        unsigned long long nz_m[PP] = {0ull, 0ull, 0ull, 0ull};
+        if constexpr (SC_NZ) {
+#pragma unroll
+            for (int p = 0; p < PP; p++) nz_m[p] = duo_lanes(nM[p] != 0u);
+        }
         {
             uint32_t anyc = 0u;
+            if constexpr (!SC_NZ) {
 #pragma unroll
-            for (int p = 0; p < PP; p++) anyc |= nM[p];
+                for (int p = 0; p < PP; p++) anyc |= nM[p];
+            }
             // (fmt 10: score index si -> word (si & ~7) * 4 + (si & 7) * 2 = 2 (si + (si & ~7)) behind the lane's base)
             const uint32_t row_off = DUO_ARENA_FMT == 10u ? 2u * (si + (si & ~7u)) : DUO_ARENA_FMT == 9u ? 0u : (((uint32_t)k0 & 60u) << 2);
-            if (run && !no_room && anyc != 0u) {
+            const bool     stored  = SC_NZ ? duo_lane_of(run_m & ~room_m & (nz_m[0] | nz_m[1] | nz_m[2] | nz_m[3])) : run && !no_room && anyc != 0u;
+            if (stored) {
                 if constexpr (PK) *reinterpret_cast<uint2 *>(rowp + row_off) = make_uint2(wd[0], wd[1]);
                 else *reinterpret_cast<uint2 *>(rowp + row_off) = make_uint2(wd[0] | (wd[1] << 16), wd[2] | (wd[3] << 16));
             }
@@ -800,7 +857,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
 #pragma unroll
             for (int p = 0; p < PP; p++) {
                 int h = (int)nM[p];
-                nz[p] = h != 0;
+                nz[p] = SC_NZ ? duo_lane_of(nz_m[p]) : h != 0;
                 // (hides from the compiler that h is below 65 536: knowing it, it forms the text's word address as shift, mask and add;
                 // for a value it knows nothing about as shift and shift-add, as it does for the query's)
                 asm("" : "+v"(h));
@@ -868,6 +925,7 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             const int r = DuoRed::or1((hitl ? 1 : 0) | (tl ? 2 : 0), wm);
             ghit = (r & 1) != 0;
             slow |= ghit;
+            if constexpr (SC_SLOW) slow_m |= duo_lanes((r & 1) != 0);
             if constexpr (UNI) term_m = duo_lanes((r & 2) != 0) & run_m, term = duo_lane_of(term_m);
             else term = run && (r & 2) != 0;
         }
@@ -994,15 +1052,20 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
         const bool fin = UNI ? duo_lane_of(fin_m) : run && (term || no_room);
         // (WFA_DUO_FILL: the score index moves on before the finish, not after it -- a pair that finishes keeps its own for pair_meta, and
         // the set_derived() behind the fill forms the row pointer of arena formats 7 and 9 from the index of the next step)
-        if constexpr (WFA_DUO_FILL != 0)
-            if (run && !fin) si += 1u;
+        if constexpr (WFA_DUO_FILL != 0) {
+            if constexpr (SC_SI) {  // (one add with the lanes that move on as its carry-in, not a select of 0 / 1 and an add)
+                unsigned long long co;
+                asm("v_addc_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(si), "=s"(co) : "s"(run_m & ~fin_m));
+            } else if (run && !fin) si += 1u;
+        }
         // (WFA_DUO_FILL: the branch now holds the fill, and is marked as the cold side so that the step's own path keeps its layout and its
         // registers -- 0.05 ms of a 14 ms step.  Not on the 32-bit rings: at their 124 .. 128 registers the hint costs wfa_duo32_kernel<false, 2, 4>
         // eight spilled ones)
         constexpr bool cold    = WFA_DUO_FILL != 0 && PK;
         const bool     any_fin = UNI ? fin_m != 0ull : __ballot(fin) != 0ull;
         if (cold ? __builtin_expect(any_fin, 0) : any_fin) {
-            const int ctot = (CENSUS && P.census) ? (int)cells : 0;
+            const auto *const A = args();
+            const int ctot = (CENSUS && A->census) ? (int)cells : 0;
             int hf   = 0;  // extended offset of the end cell M[s][Ak]: where the backtrace starts
 #pragma unroll
             for (int p = 0; p < PP; p++)
@@ -1010,13 +1073,15 @@ __device__ __attribute__((always_inline)) inline void duo_run(const KParams &P) 
             hf = DuoRed::max1(hf, wm);
             if (fin && j == 0) {
                 if (no_room) {
-                    P.pair_meta[pidx] = make_uint4(ST_REDO_ARENA, 0u, 0u, 0u);
-                    push_redo(P, pair_of(pidx), ST_REDO_ARENA);
+                    A->pair_meta[pidx] = make_uint4(ST_REDO_ARENA, 0u, 0u, 0u);
+                    redo(A, pair_of(A, pidx), ST_REDO_ARENA);
                 } else {
-                    P.pair_meta[pidx] = make_uint4(ST_OK, si * P.g, (uint32_t)hf, (uint32_t)ctot);
+                    A->pair_meta[pidx] = make_uint4(ST_OK, si * A->g, (uint32_t)hf, (uint32_t)ctot);
                 }
             }
-            buf_free |= or_halves(fin ? (1u << sbuf) : 0u);
+            // (or_halves() first, buf_free second, as `buf_free |= or_halves(..)` reads them: the other order moved the register allocation of the whole
+            // loop -- six vector instructions more on the step's path, profiles/r15_duo_scalar.txt)
+            buf_free = uni(or_halves(fin ? (1u << sbuf) : 0u) | buf_free);
             if (fin) {
                 st = 0, wide = false;
                 clear_rings();

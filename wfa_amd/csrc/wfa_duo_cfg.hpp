@@ -51,6 +51,20 @@ namespace wfa {
 #ifndef WFA_DUO_UNIFORM
 #define WFA_DUO_UNIFORM 1
 #endif
+// Where the score step keeps its wave-uniform state and the kernel its cold arguments (wfa_duo.hpp): 1 = the arguments that only cold code reads
+// (arena, pair_meta, the redo list, work, chunk_first, queue_head, chunk_n, prepack, g, census) are loaded from the kernel-argument segment where
+// they are used and hold no scalar register while the steps run; the prefetch's flags and buffer masks are said to be uniform where they are
+// written, not at the head of every step; `slow` has a lane mask like `run` and `wide`; the row store's "has the lane a cell" is the OR of the four
+// cell masks; the score index moves on with one add-with-carry (the default).  0 = the form before, kept for A/B builds:
+// scripts/mkvariant.sh <name> -DWFA_DUO_SCALAR=0.  (wfa_duo_kernel in its WFA_DUO_UNIFORM form only -- profiles/r15_duo_scalar.txt)
+#ifndef WFA_DUO_SCALAR
+#define WFA_DUO_SCALAR 1
+#endif
+// ... and which of its five items, one bit each, for A/B builds of a single item: 1 the reloaded arguments, 2 the uniform state, 4 slow_m, 8 the
+// store's test from the cell masks, 16 the add-with-carry (31 = all, the default; vector instructions each takes off a step: 0, 3, 2, 3, 1)
+#ifndef WFA_DUO_SCALAR_ITEMS
+#define WFA_DUO_SCALAR_ITEMS 31
+#endif
 // Arena layout of wfa_duo_kernel (16-bit words; a lane's four diagonals of a score are one 8-byte store, and 8 scores of them
 // one 64-byte piece, in every one of the three):
 //   0  CompactView fmt 7 (round 3) -- tiles of 8 scores x 64 diagonals (1 KB), inside a tile [diagonal / 4][score & 7][diagonal & 3]:
