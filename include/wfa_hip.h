@@ -447,6 +447,59 @@ int  wfahip_align_batch_packed_device(wfahip_ctx *ctx, const wfahip_params *p, c
                                       const void *d_q_rc, uint64_t n_pairs, uint32_t max_len, uint32_t max_score, void *d_rec,
                                       void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, void *stream);
 
+/* wfahip_score_batch_packed_device: the screen of the pipeline on device-resident words -- wfahip_score_batch_packed_rc for words,
+ * offsets, lengths and flags that live in HBM, the results left there.  With it the chain pack (wfahip_pack_pairs_device) -> score
+ * both strands under a bound -> survivors (wfahip_select_pairs_device) -> align (wfahip_align_batch_packed_device) -> text
+ * (wfahip_cigar_text_device) runs with only counters crossing the bus.
+ * Inputs as wfahip_align_batch_packed_device's: device pointers that stay the caller's and are never written; u64 word offsets, u32
+ * lengths; d_q_rc a u8 per pair, NULL = none set; d_packed readable for 16 bytes behind its n_words words; max_len = 0 lets the
+ * library find the longest read; stream = NULL is the context's own; synchronous.  Outputs as wfahip_score_batch_device's: d_status
+ * (int32) and d_score (uint32) receive exactly n_pairs elements each and nothing beyond.
+ * For every pair, status and score equal what wfahip_score_batch_packed_rc returns for the same words, offsets, lengths, flags,
+ * params and max_score -- wfahip_score_batch on the bytes (revcomp(query) if flagged else query, target) -- and everything that entry
+ * promises holds: offsets in any order, repeated, naming a prefix of a longer sequence; anything in the bits of a last word beyond
+ * the last base and in the pad word; the offsets of an empty or too long pair never looked at, whatever its flag; a call whose flags
+ * are all zero takes the route of the call with d_q_rc = NULL.
+ *   WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx or p; with n_pairs > 0 a null offset, length or output pointer;
+ *     a null d_packed with n_words > 0; n_pairs beyond 0xFFFFFFF0; n_words beyond 2^58.  Then the params as wfahip_align_batch checks
+ *     them; n_pairs == 0 returns WFAHIP_OK and touches nothing.
+ *   WFAHIP_ERR_BAD_ARG with the outputs untouched, before any kernel that reads a packed word is launched: a pair, neither empty nor
+ *     too long, has a sequence with woff + wfahip_packed_words(len) > n_words (compared without a sum that could wrap).
+ * The router is wfahip_score_batch_device's, on words (wfa_amd/csrc/wfa_score_dev.hpp): wfa_score_pkplan_kernel finds the bounds
+ * verdict, the longest read, whether a flag is set and the long global pairs, and -- when there are at least "score_long_min" of them
+ * -- writes wfa_score_long_kernel's table in batch order with offsets pointing INTO the caller's words; the packed pair-list
+ * instances of the score kernels read the caller's arrays as they are.  A flagged long query is reverse-complemented into scratch of
+ * the context by wfa_score_rcq_kernel and read from there.  Unlike the host entry there is no dedup by {offset, length}: one reverse
+ * complement per flagged long pair, device memory of a quarter of a byte per base of every flagged long pair.  The pairs the kernels
+ * hand back are listed in pair order, exactly their words are gathered into a buffer of the context (wfa_score_gather_kernel: a
+ * flagged query through the same word function, tail bits and pad words cleared) and aligned by the full path of
+ * wfahip_align_batch_packed_device under the bound, in chunks.  Apart from the kernel arguments, two fetches of 64 bytes of counters
+ * per call cross PCIe, plus what the full path itself fetches when pairs take it.
+ * wfahip_last_timing: main_kernel_kind (19 / 23 / 20) and n_retried_pairs are wfahip_score_batch_packed_rc's on the same input, and
+ * arena_bytes is 0 exactly when that entry's is. */
+int  wfahip_score_batch_packed_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words,
+                                      const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len,
+                                      const void *d_q_rc, uint64_t n_pairs, uint32_t max_len, uint32_t max_score,
+                                      void *d_status, void *d_score, void *stream);
+
+/* wfahip_select_pairs_device: the survivors of a screen as the next stage's arrays -- a stable compaction, in pair order, of the
+ * pairs with d_status[i] == WFAHIP_PAIR_OK (under a max_score the score entries have turned the others into WFAHIP_PAIR_OVER_MAX).
+ * Every pointer but n_selected is a device address on the context's GPU and stays the caller's; the inputs are never written.
+ * d_idx (u32, may be NULL) receives the selected indices; d_q_off_out / d_q_len_out / d_t_off_out / d_t_len_out / d_q_rc_out
+ * (u64 / u32 / u64 / u32 / u8) the selected elements of the five input arrays.  Each has capacity n_pairs; only the first
+ * *n_selected elements are written.  d_q_rc and d_q_rc_out are both NULL or both non-NULL.  The offsets are opaque u64 -- word
+ * offsets and byte offsets both work --, so the output feeds wfahip_align_batch_packed_device or wfahip_align_batch_device unchanged.
+ *   WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx or n_selected; with n_pairs > 0 a null d_status, input or _out
+ *     array; d_q_rc without d_q_rc_out or the reverse; n_pairs beyond 0xFFFFFFF0.  n_pairs == 0 returns WFAHIP_OK with
+ *     *n_selected = 0 and touches nothing else.
+ * Two launches of wfa_score_select_kernel with the scan of wfahip_score_batch_device's router between them; scratch lives in the
+ * context; one fetch of 64 bytes brings the count.  stream = hipStream_t (NULL = the context's own).  Synchronous.
+ * wfahip_last_timing is not touched. */
+int  wfahip_select_pairs_device(wfahip_ctx *ctx, const void *d_status, uint64_t n_pairs,
+                                const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, const void *d_q_rc,
+                                void *d_idx, void *d_q_off_out, void *d_q_len_out, void *d_t_off_out, void *d_t_len_out, void *d_q_rc_out,
+                                uint64_t *n_selected, void *stream);
+
 /* CIGAR text, rendered where the ops are.  AlignmentResult.CIGAR(onlyAlignedRegion) (wfa_cigar.go:217-255) of every pair of a
  * batch as bytes: what a SAM / PAF writer puts into a file.  The rule (wfa_amd/csrc/wfa_cigar.hpp, one source for the kernels and
  * the host renderer): every op renders as the decimal of op & 0xFFFFFFFF -- a full u32, one to ten digits, no leading zero, a

@@ -34,6 +34,7 @@ EXPORTS = [
     "wfahip_cigar_text_device", "wfahip_cigar_text", "wfahip_cigars_free", "wfahip_align_batch_text",
     "wfahip_alignment_text_device", "wfahip_alignment_text", "wfahip_align_texts_free",
     "wfahip_pack_pairs_device", "wfahip_align_batch_packed_device",
+    "wfahip_score_batch_packed_device", "wfahip_select_pairs_device",
 ]
 
 
@@ -182,6 +183,10 @@ def lib():
         L.wfahip_align_batch_packed_device.restype = C.c_int
         L.wfahip_align_batch_packed_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, vp, u64, u32, u32, vp, vp,
                                                        u64, C.POINTER(u64), vp]
+        L.wfahip_score_batch_packed_device.restype = C.c_int
+        L.wfahip_score_batch_packed_device.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, vp, u64, u32, u32, vp, vp, vp]
+        L.wfahip_select_pairs_device.restype = C.c_int
+        L.wfahip_select_pairs_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), vp]
         L.wfahip_submit.restype = C.c_int
         L.wfahip_submit.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32, C.POINTER(u64)]
         L.wfahip_pending.restype = u64

@@ -680,6 +680,88 @@ class Aligner:
         L.check(rc, "wfahip_align_batch_packed_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return rec, ops
 
+    # -- new: the screen on device-resident words and its survivors (include/wfa_hip.h: wfahip_score_batch_packed_device, wfahip_select_pairs_device)
+    def score_tensors_packed(self, packed, q_woff, q_len, t_woff, t_len, q_rc=None, max_score: int = 0, out=None, stream=None):
+        """score_arrays_packed_rc over 2-bit words that live on the aligner's GPU (include/wfa_hip.h: wfahip_score_batch_packed_device):
+        the tensors align_tensors_packed takes -- packed int32 with at least four words of slack behind the words the offsets name,
+        q_woff / t_woff int64, q_len / t_len int32, q_rc an optional uint8 tensor of one flag per pair (non-zero: the pair scores the
+        reverse complement of its query) -- in, a pair of int32 tensors (status, score) on the same device out, as score_tensors
+        returns them: they equal score_arrays_packed_rc's on the same words, flags and max_score.  Only counters cross PCIe, and the
+        inputs are never written.  out: an optional pair of contiguous int32 tensors of at least n elements each; elements beyond n
+        keep their contents.  stream and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("packed", packed, torch.int32)
+        for name, t, dtype in (("q_woff", q_woff, torch.int64), ("q_len", q_len, torch.int32), ("t_woff", t_woff, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(q_len.numel())
+        if q_woff.numel() != n or t_woff.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors differ in length")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        if packed.numel() < 4:
+            raise ValueError("packed must hold four words of slack behind its words")
+        if not 0 <= int(max_score) < 1 << 32:
+            raise ValueError("max_score must fit in 32 bits")
+        if out is None:
+            status = torch.zeros(n, dtype=torch.int32, device=dev)
+            score = torch.zeros(n, dtype=torch.int32, device=dev)
+        else:
+            try:
+                status, score = out
+            except (TypeError, ValueError):
+                raise ValueError("out must be a pair (status, score) of tensors") from None
+            self._want_tensor("out status", status, torch.int32, dev), self._want_tensor("out score", score, torch.int32, dev)
+            if status.numel() < n or score.numel() < n:
+                raise ValueError(f"out tensors must hold at least {n} elements")
+        stream = self._want_stream(stream, dev)
+        if n == 0:
+            return status, score
+        self._order_after_torch(stream, dev)  # (the fills above, and whatever made the inputs, ran on torch's current stream)
+        prm = self._params()
+        lib = L.lib()
+        rc = lib.wfahip_score_batch_packed_device(self._ctx, C.byref(prm), packed.data_ptr(), int(packed.numel()) - 4, q_woff.data_ptr(),
+                                                  q_len.data_ptr(), t_woff.data_ptr(), t_len.data_ptr(),
+                                                  q_rc.data_ptr() if q_rc is not None else None, n, 0, int(max_score), status.data_ptr(),
+                                                  score.data_ptr(), stream.cuda_stream)
+        L.check(rc, "wfahip_score_batch_packed_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return status, score
+
+    def select_tensors(self, status, q_off, q_len, t_off, t_len, q_rc=None, stream=None):
+        """The pairs whose status is PAIR_OK, in pair order, as the next stage's tensors (include/wfa_hip.h: wfahip_select_pairs_device):
+        status int32 -- score_tensors' or score_tensors_packed's, under a max_score the screen's verdict --, q_off / t_off int64 (word
+        or byte offsets: they are only copied), q_len / t_len int32, q_rc an optional uint8 tensor.  Returns
+        (idx int32, q_off, q_len, t_off, t_len, q_rc) on the same device, each sliced to the number of selected pairs (q_rc None when
+        none was given); idx holds the selected pairs' indices, the C-ABI's uint32 bit for bit.  They go into align_tensors_packed or
+        align_tensors unchanged.  Only the count crosses PCIe.  stream and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("status", status, torch.int32)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(status.numel())
+        if q_off.numel() != n or q_len.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("status, offset and length tensors differ in length")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        stream = self._want_stream(stream, dev)
+        outs = [torch.empty(n, dtype=dt, device=dev) for dt in (torch.int32, torch.int64, torch.int32, torch.int64, torch.int32)]
+        outs.append(torch.empty(n, dtype=torch.uint8, device=dev) if q_rc is not None else None)
+        if n == 0:
+            return tuple(outs)
+        self._order_after_torch(stream, dev)  # (whatever made the inputs ran on torch's current stream)
+        lib = L.lib()
+        cnt = C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = lib.wfahip_select_pairs_device(self._ctx, status.data_ptr(), n, q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(),
+                                            ptr(q_rc), *[ptr(t) for t in outs], C.byref(cnt), stream.cuda_stream)
+        L.check(rc, "wfahip_select_pairs_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return tuple(t[:cnt.value] if t is not None else None for t in outs)
+
     def alignment_text_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, out=None, stream=None):
         """AlignmentResult.AlignmentText(q, t, only_aligned) of every pair of (rec, ops) -- align_tensors' output -- over the blob
         and the four tensors that call was given, rendered on the aligner's GPU (include/wfa_hip.h: wfahip_alignment_text_device):

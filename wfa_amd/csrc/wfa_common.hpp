@@ -152,6 +152,10 @@ struct KParams {
     uint64_t        rc_top;          // TOP of the blob's mirror (wfa_rc.hpp: rc_mirror_top), 0 = the call has no flag set.  q_off of a pair whose q_rc
                                      // flag is set is then the MIRROR address of its query's reverse complement: the passes that read bytes read it
                                      // like any other offset, the three that read words recover the forward word offset from it (rc_mirror_word)
+    // ---- reverse-strand scoring of device-resident words (wfahip_score_batch_packed_device; appended last for the same reason)
+    const uint32_t *mx_rc_words;     // wfa_score_long_kernel's list form: the base a query entry's offset counts from when its pair's TARGET entry carries
+                                     // .w != 0 -- the reverse complements wfa_score_rcq_kernel wrote into scratch of the context, the caller's words
+                                     // (mx_words) being read-only; every other entry writes 0 there and never reads this
 };
 
 }  // namespace wfa

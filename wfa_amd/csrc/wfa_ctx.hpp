@@ -4,7 +4,8 @@
 //                  long-pair ladder behind it (align_device; the plan of a ladder job is host-only arithmetic: wfa_ladder.hpp)
 //   wfa_entry.hip  the host entries: wfahip_align_batch (sliced upload / alignment / download), packed input (host and device-resident),
 //                  wfahip_align_pair, submit / collect, the results cache
-//   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_packed, wfahip_score_batch_device, wfahip_score_matrix -- a
+//   wfa_score_entry.hip  the score-only entries: wfahip_score_batch, wfahip_score_batch_packed, wfahip_score_batch_device, wfahip_score_batch_packed_device
+//                  (and wfahip_select_pairs_device behind it), wfahip_score_matrix -- a
 //                  router each over the launch section, the geometry and the full-path fallback they share
 //   wfa_cigar.hip  CIGAR text: the three rendering kernels, wfahip_cigar_text_device, the host renderer wfahip_cigar_text, wfahip_align_batch_text;
 //                  the display rows on the same scan: wfahip_alignment_text_device, the host renderer wfahip_alignment_text
@@ -186,6 +187,8 @@ struct wfahip_ctx {
                                                   // words lie in mx_words, behind the uploaded ones)
     DevBuf        sd_ctl, sd_blk, sd_list, sd_redo;  // wfahip_score_batch_device (wfa_score_dev.hpp): control words, tile sums, the long pairs, the pairs of the full path
     uint64_t      sd_n_words = 0, sd_n_listed = 0;   // ... what its last call left in mx_words / mx_seq (wfahip_debug_score_device_list)
+    DevBuf        sd_words;                          // wfahip_score_batch_packed_device: the gathered words of the pairs of the full path (apart from what
+                                                     // align_packed_device_impl takes for itself: in_qoff, in_toff, pkd, in_blob)
     DevBuf        cig;                            // wfahip_cigar_text_device, wfahip_alignment_text_device (wfa_cigar.hip): its counters, the scan's block sums, the trimmed op range of every pair
     DevBuf        cig_text, cig_off;              // wfahip_align_batch_text: the batch's text and its offsets, until they are downloaded
     DevBuf        pkd;                            // wfahip_pack_pairs_device (wfa_packdev.hip): its counters and the scan's block sums; wfahip_align_batch_packed_device
@@ -360,6 +363,11 @@ int align_batch_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *se
 int align_batch_packed_entry(wfahip_ctx *ctx, const wfahip_params *p, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
                              const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, uint64_t n_pairs, wfahip_results *out,
                              const uint8_t *q_rc = nullptr);
+// wfahip_align_batch_packed_device behind its argument checks (the caller has refused null pointers, bad params and the empty batch, and
+// holds the BoundScope): the full path of wfahip_score_batch_packed_device, over the words that entry gathered
+int align_packed_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words, const void *d_q_woff,
+                             const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n_pairs,
+                             uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, hipStream_t st);
 // the flags of a call as the kernels take them: nullptr when none of the n is set (they then run as without flags)
 inline const uint8_t *any_flag(const uint8_t *f, uint64_t n) {
     if (f)

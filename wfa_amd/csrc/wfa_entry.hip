@@ -875,9 +875,9 @@ __global__ __launch_bounds__(256) void wfa_packed_check_kernel(const uint64_t *_
     if (flag) atomicOr(&ctl[PDC_ANY_RC], 1u);
 }
 
-static int align_packed_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words, const void *d_q_woff,
-                                    const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n_pairs,
-                                    uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, hipStream_t st) {
+int align_packed_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words, const void *d_q_woff,
+                             const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n_pairs,
+                             uint32_t max_len, void *d_rec, void *d_ops, uint64_t ops_cap, uint64_t *ops_needed, hipStream_t st) {
     // (the entry below has refused null pointers, bad params and the empty batch)
     int rc = WFAHIP_OK;
     if (ops_needed) *ops_needed = 0;

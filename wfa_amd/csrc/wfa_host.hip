@@ -329,7 +329,7 @@ extern "C" void wfahip_destroy(wfahip_ctx *ctx) {
     }
     for (DevBuf *b : {&ctx->arena, &ctx->fin, &ctx->team_ctl, &ctx->arena2, &ctx->meta2, &ctx->doneq, &ctx->ctrl, &ctx->redo, &ctx->work, &ctx->meta, &ctx->in_blob, &ctx->in_qoff, &ctx->in_qlen,
                       &ctx->in_toff, &ctx->in_tlen, &ctx->out_rec, &ctx->out_ops, &ctx->in_packed, &ctx->in_small, &ctx->prepack, &ctx->one_ctl, &ctx->page_ctl, &ctx->xbuf, &ctx->wide_ckpt, &ctx->score_out,
-                      &ctx->mx_seq, &ctx->mx_words, &ctx->mx_out, &ctx->sd_ctl, &ctx->sd_blk, &ctx->sd_list, &ctx->sd_redo, &ctx->wide_ids, &ctx->wide_blk,
+                      &ctx->mx_seq, &ctx->mx_words, &ctx->mx_out, &ctx->sd_ctl, &ctx->sd_blk, &ctx->sd_list, &ctx->sd_redo, &ctx->sd_words, &ctx->wide_ids, &ctx->wide_blk,
                       &ctx->wide_ctl, &ctx->in_rc, &ctx->rc_jobs, &ctx->cig, &ctx->cig_text, &ctx->cig_off, &ctx->pkd})
         release(*b);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

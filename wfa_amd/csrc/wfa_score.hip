@@ -1,7 +1,7 @@
 // wfa_score.hip -- translation unit of the score-only kernels behind wfahip_score_batch: wfa_score_kernel (global pairs, any
 // penalty shape score_shape_ok() takes; wfa_score_long_kernel for reads beyond its 2 047 bases) and the score instances of wfa_wide_kernel (semi-global pairs, the shapes of
 // wfa_fwd_shape.inc), their matrix instances behind wfahip_score_matrix and their packed pair-list instances behind
-// wfahip_score_batch_packed; and the routing kernels of wfahip_score_batch_device
+// wfahip_score_batch_packed; and the routing kernels of wfahip_score_batch_device, wfahip_score_batch_packed_device and wfahip_select_pairs_device
 // (wfa_score_dev.hpp).  The routers are wfa_score_entry.hip (score_batch_impl, score_batch_device_impl, score_matrix_impl); the
 // launches below are declared for them in wfa_ctx.hpp.
 #define WFA_NO_AUX_KERNELS 1
@@ -84,7 +84,7 @@ hipError_t wfa_launch_wide_score(int stage, int shape, int phase, int waves, con
     return hipErrorInvalidValue;
 }
 
-// the routing kernels of wfahip_score_batch_device (wfa_score_dev.hpp): kernel `k` (SDK_*) over `grid` workgroups of SD_BLOCK threads
+// the routing kernels of wfahip_score_batch_device, wfahip_score_batch_packed_device and wfahip_select_pairs_device (wfa_score_dev.hpp): kernel `k` (SDK_*) over `grid` workgroups of SD_BLOCK threads
 hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStream_t st) {
     const dim3 g(grid), b(SD_BLOCK);
     switch (k) {
@@ -97,6 +97,14 @@ hipError_t wfa_launch_score_dev(int k, const SDParams &S, uint32_t grid, hipStre
     case SDK_REDO_COUNT: hipLaunchKernelGGL(wfa_score_redo_kernel<false>, g, b, 0, st, S); break;
     case SDK_REDO_WRITE: hipLaunchKernelGGL(wfa_score_redo_kernel<true>, g, b, 0, st, S); break;
     case SDK_FINISH: hipLaunchKernelGGL(wfa_score_finish_kernel, g, b, 0, st, S); break;
+    case SDK_PK_PLAN_COUNT: hipLaunchKernelGGL(wfa_score_pkplan_kernel<false>, g, b, 0, st, S); break;
+    case SDK_PK_PLAN_WRITE: hipLaunchKernelGGL(wfa_score_pkplan_kernel<true>, g, b, 0, st, S); break;
+    case SDK_PK_RCQ: hipLaunchKernelGGL(wfa_score_rcq_kernel, g, b, 0, st, S); break;
+    case SDK_PK_REDO_COUNT: hipLaunchKernelGGL(wfa_score_pkredo_kernel<false>, g, b, 0, st, S); break;
+    case SDK_PK_REDO_WRITE: hipLaunchKernelGGL(wfa_score_pkredo_kernel<true>, g, b, 0, st, S); break;
+    case SDK_PK_GATHER: hipLaunchKernelGGL(wfa_score_gather_kernel, g, b, 0, st, S); break;
+    case SDK_SELECT_COUNT: hipLaunchKernelGGL(wfa_score_select_kernel<false>, g, b, 0, st, S); break;
+    case SDK_SELECT_WRITE: hipLaunchKernelGGL(wfa_score_select_kernel<true>, g, b, 0, st, S); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

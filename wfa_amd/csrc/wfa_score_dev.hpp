@@ -32,7 +32,14 @@ constexpr uint32_t SD_BLOCK = 256, SD_ITEMS = 4, SD_TILE = SD_BLOCK * SD_ITEMS;
 constexpr uint32_t SD_MAX_SEQ_LEN = 0x1FFFFFFFu;  // WFAHIP_MAX_SEQ_LEN (wfa.go:186-193), as the kernels spell it
 // the control words (uint64 each): one 64-byte fetch shows the host all of them
 enum { SDC_BOUNDS = 0, SDC_MAX_LEN, SDC_N_LONG, SDC_N_WORDS, SDC_N_LISTED, SDC_N_REDO, SDC_REDO_SUM, SDC_REDO_MAX, SDC_WORDS };
-enum { SDK_PLAN_COUNT = 0, SDK_PLAN_WRITE, SDK_SCAN, SDK_PACK, SDK_LIST_COUNT, SDK_LIST_WRITE, SDK_REDO_COUNT, SDK_REDO_WRITE, SDK_FINISH };
+// (wfahip_score_batch_packed_device lists nothing in a second step: that word carries "a flag is set"; its SDC_N_WORDS counts the words of
+// the flagged long queries' reverse complements, its SDC_REDO_SUM the words of the pairs of the full path)
+enum { SDC_ANY_RC = SDC_N_LISTED };
+enum { SDK_PLAN_COUNT = 0, SDK_PLAN_WRITE, SDK_SCAN, SDK_PACK, SDK_LIST_COUNT, SDK_LIST_WRITE, SDK_REDO_COUNT, SDK_REDO_WRITE, SDK_FINISH,
+       // wfahip_score_batch_packed_device (at the end of this header)
+       SDK_PK_PLAN_COUNT, SDK_PK_PLAN_WRITE, SDK_PK_RCQ, SDK_PK_REDO_COUNT, SDK_PK_REDO_WRITE, SDK_PK_GATHER,
+       // wfahip_select_pairs_device
+       SDK_SELECT_COUNT, SDK_SELECT_WRITE };
 
 struct SDSum {
     unsigned long long cnt, wt;  // selected items of a tile; their weight (plan: packed words, redo: bases)
@@ -67,6 +74,15 @@ struct SDParams {
     const uint32_t *rec;        // nullptr: from score_out; else the records of pairs r_id[first ..] of the full path
     uint64_t        first;
     uint32_t        max_score;  // (the call's bound; the full path gets it through the context)
+    // wfahip_score_batch_packed_device: q_off / t_off count words of pk_words
+    const uint32_t *pk_words;   // the caller's 2-bit words (never written)
+    uint64_t        n_words;
+    const uint8_t  *q_rc;       // a flag per pair, nullptr = none set (wfahip_select_pairs_device: the flags to compact)
+    uint32_t       *rc_words;   // the reverse complements of the flagged long queries (KParams::mx_rc_words)
+    uint32_t       *g_words;    // the words of the pairs of the full path, as wfahip_pack_pairs lays them out; r_qoff / r_toff count its words
+    uint8_t        *r_rc;       // (the full path gets no flags: the gather has applied them.  wfahip_select_pairs_device: the compacted flags)
+    // wfahip_select_pairs_device: the statuses it selects by; its outputs are r_id (may be nullptr), r_qoff, r_toff, r_qlen, r_tlen, r_rc
+    const int32_t  *sel_status;
 };
 
 #ifdef WFA_SCORE_UNIT
@@ -277,6 +293,127 @@ __global__ __launch_bounds__(SD_BLOCK) void wfa_score_finish_kernel(const SDPara
     // (unpack_results' rule; the full path ran under the call's bound and has said ST_OVER_MAX itself)
     if (!(st == (uint32_t)ST_OK || st == (uint32_t)ST_EMPTY || st == (uint32_t)ST_TOO_LONG || st == (uint32_t)ST_OVER_MAX)) st = ST_NO_MEMORY;
     S.d_status[i] = (int32_t)st, S.d_score[i] = st == (uint32_t)ST_OK ? sc : 0u;
+}
+
+// ---- wfahip_score_batch_packed_device: the same routing for a batch of caller-packed words in HBM with a reverse-complement flag per
+// pair (wfa_score_entry.hip: score_batch_packed_device_impl).  Packed input has no byte outside ACGT, so there is neither a pack nor a
+// list stage: the plan's write launch emits wfa_score_long_kernel's table directly, its offsets pointing INTO the caller's words.
+//   wfa_score_pkplan_kernel  the bounds check in WORDS (wfa_packed_check_kernel's comparison: no sum that can wrap), the longest read,
+//                            whether a flag is set, and the long pairs of a global call -- each weighs wfahip_packed_words(q_len) when it
+//                            is flagged, else nothing: the scan then places the reverse complements in S.rc_words
+//   wfa_score_rcq_kernel     writes them: a workgroup per listed pair (an unflagged one leaves at once), a lane per word through rc_word,
+//                            a zero pad word.  One reverse complement per flagged long pair: no dedup by {offset, length}
+//   wfa_score_pkredo_kernel  the pairs handed back, weighing the words wfahip_pack_pairs would give them (an empty or too long pair: one
+//                            zero word per sequence); its write launch emits fresh word offsets, the lengths and the flag
+//   wfa_score_gather_kernel  copies exactly those pairs' words to the fresh offsets, a wave per sequence: a flagged query through rc_word,
+//                            the bits beyond the last base and the pad word CLEARED (KERNELS.md 4l)
+template <bool WRITE>
+__global__ __launch_bounds__(SD_BLOCK) void wfa_score_pkplan_kernel(const SDParams S) {
+    uint32_t mx = 0u, oob = 0u, any = 0u;
+    sd_select<WRITE>(
+        S,
+        [&](uint64_t i, uint32_t &sel, uint64_t &wt) {
+            const uint32_t ql = S.q_len[i], tl = S.t_len[i];
+            const bool     fl = S.q_rc != nullptr && S.q_rc[i] != 0;
+            if constexpr (!WRITE) any |= fl ? 1u : 0u;
+            if (!sd_valid(ql, tl)) return;  // (empty or too long: its offsets are never looked at, whatever its flag)
+            if constexpr (!WRITE) {
+                const uint64_t qo = S.q_off[i], to = S.t_off[i], nw = S.n_words;
+                if (qo > nw || sd_words(ql) > nw - qo || to > nw || sd_words(tl) > nw - to) oob = 1u;
+                mx = umax2(mx, umax2(ql, tl));
+            }
+            if (S.want_long != 0u && umax2(ql, tl) > SCORE_MAX_LEN) sel = 1u, wt = fl ? sd_words(ql) : 0ull;
+        },
+        [&](uint64_t i, uint64_t r, uint64_t wo) {
+            const bool     fl = S.q_rc != nullptr && S.q_rc[i] != 0;
+            const uint64_t qw = fl ? wo : S.q_off[i], tw = S.t_off[i];
+            S.table[2ull * r]        = make_uint4((uint32_t)qw, (uint32_t)(qw >> 32), S.q_len[i], (uint32_t)i);
+            S.table[2ull * r + 1ull] = make_uint4((uint32_t)tw, (uint32_t)(tw >> 32), S.t_len[i], fl ? 1u : 0u);
+        });
+    if constexpr (!WRITE) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) mx = umax2(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+        if ((threadIdx.x & 63u) == 0u && mx != 0u) atomicMax(&S.ctl[SDC_MAX_LEN], (unsigned long long)mx);
+        if (oob) atomicOr(&S.ctl[SDC_BOUNDS], 1ull);
+        if (any) atomicOr(&S.ctl[SDC_ANY_RC], 1ull);
+    }
+}
+
+// S.n = listed long pairs; workgroup j takes pair j of S.table.  A wave writes 64 consecutive words
+__global__ __launch_bounds__(SD_BLOCK) void wfa_score_rcq_kernel(const SDParams S) {
+    const uint64_t j = blockIdx.x;
+    if (j >= S.n) return;
+    const uint4 q = S.table[2ull * j], t = S.table[2ull * j + 1ull];
+    if (t.w == 0u) return;
+    const uint32_t *const src = S.pk_words + S.q_off[q.w];
+    uint32_t *const       dst = S.rc_words + ((uint64_t)q.y << 32 | q.x);
+    const uint32_t        nw  = (q.z + 15u) >> 4;
+    for (uint32_t w = threadIdx.x; w < nw; w += SD_BLOCK) dst[w] = rc_word(src, q.z, w);
+    if (threadIdx.x == 0) dst[nw] = 0u;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(SD_BLOCK) void wfa_score_pkredo_kernel(const SDParams S) {
+    uint32_t mx = 0u;
+    sd_select<WRITE>(
+        S,
+        [&](uint64_t i, uint32_t &sel, uint64_t &wt) {
+            sel = (S.all != 0u || S.score_out[i].x >= (uint32_t)ST_REDO_BYTES) ? 1u : 0u;
+            if (!sel) return;
+            const uint32_t ql = S.q_len[i], tl = S.t_len[i];
+            wt = 2ull;
+            if (sd_valid(ql, tl)) wt = sd_words(ql) + sd_words(tl), mx = umax2(mx, umax2(ql, tl));
+        },
+        [&](uint64_t i, uint64_t r, uint64_t wo) {
+            const uint32_t ql = S.q_len[i], tl = S.t_len[i];
+            S.r_id[r] = (uint32_t)i, S.r_qoff[r] = wo, S.r_toff[r] = wo + (sd_valid(ql, tl) ? sd_words(ql) : 1ull), S.r_qlen[r] = ql, S.r_tlen[r] = tl;
+            S.r_rc[r] = (S.q_rc != nullptr && S.q_rc[i] != 0) ? 1 : 0;
+        });
+    if constexpr (!WRITE) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) mx = umax2(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+        if ((threadIdx.x & 63u) == 0u && mx != 0u) atomicMax(&S.ctl[SDC_REDO_MAX], (unsigned long long)mx);
+    }
+}
+
+// S.n = pairs of the full path; sequence s of the launch is the query (s even) or the target (s odd) of pair s / 2.  A wave per sequence
+// (a batch on a shape without an instance may be 1e6 sequences of a few words), the waves of the grid striding over them; a wave
+// writes 64 consecutive words a round
+__global__ __launch_bounds__(SD_BLOCK) void wfa_score_gather_kernel(const SDParams S) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * (SD_BLOCK / 64) + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * (SD_BLOCK / 64);
+    for (uint64_t s = wave; s < 2ull * S.n; s += n_waves) {
+        const uint64_t  j   = s >> 1;
+        const bool      tgt = (s & 1ull) != 0ull;
+        const uint32_t  ql = S.r_qlen[j], tl = S.r_tlen[j];
+        uint32_t *const dst = S.g_words + (tgt ? S.r_toff[j] : S.r_qoff[j]);
+        if (!sd_valid(ql, tl)) {  // (one zero word, and the offsets of the pair are never looked at)
+            if (lane == 0u) dst[0] = 0u;
+            continue;
+        }
+        const uint32_t        i   = S.r_id[j];
+        const uint32_t        len = tgt ? tl : ql, nw = (len + 15u) >> 4, tail = len & 15u;
+        const uint32_t *const src = S.pk_words + (tgt ? S.t_off[i] : S.q_off[i]);
+        const bool            rc  = !tgt && S.r_rc[j] != 0;
+        for (uint32_t w = lane; w < nw; w += 64u) {
+            uint32_t v = rc ? rc_word(src, len, w) : src[w];
+            if (w == nw - 1u && tail != 0u) v &= (1u << (2u * tail)) - 1u;
+            dst[w] = v;
+        }
+        if (lane == 0u) dst[nw] = 0u;
+    }
+}
+
+// ---- wfahip_select_pairs_device: the pairs with status WFAHIP_PAIR_OK, in pair order, as the next stage's arrays
+template <bool WRITE>
+__global__ __launch_bounds__(SD_BLOCK) void wfa_score_select_kernel(const SDParams S) {
+    sd_select<WRITE>(
+        S, [&](uint64_t i, uint32_t &sel, uint64_t &wt) { sel = S.sel_status[i] == (int32_t)ST_OK ? 1u : 0u, wt = 0ull; },
+        [&](uint64_t i, uint64_t r, uint64_t) {
+            if (S.r_id != nullptr) S.r_id[r] = (uint32_t)i;
+            S.r_qoff[r] = S.q_off[i], S.r_toff[r] = S.t_off[i], S.r_qlen[r] = S.q_len[i], S.r_tlen[r] = S.t_len[i];
+            if (S.r_rc != nullptr) S.r_rc[r] = S.q_rc[i];
+        });
 }
 #endif  // WFA_SCORE_UNIT
 

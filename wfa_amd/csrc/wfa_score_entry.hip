@@ -1,5 +1,6 @@
 // wfa_score_entry.hip -- the score-only entries of the C-ABI (include/wfa_hip.h): wfahip_score_batch (host arrays),
-// wfahip_score_batch_packed (host arrays over caller-packed 2-bit words), wfahip_score_batch_device (device-resident input) and
+// wfahip_score_batch_packed (host arrays over caller-packed 2-bit words), wfahip_score_batch_device (device-resident input),
+// wfahip_score_batch_packed_device (device-resident words, with flags; wfahip_select_pairs_device compacts its survivors) and
 // wfahip_score_matrix (every query against every target); wfahip_score_batch_packed_rc and wfahip_score_matrix_rc, which are the packed and
 // the matrix entry with a reverse-complement flag per pair / per query row (wfa_rc.hpp), and wfahip_revcomp_packed.  The forward pass
 // without arena or backtrace: wfa_score_kernel for global pairs, wfa_score_long_kernel for global reads beyond its length, the score
@@ -228,7 +229,9 @@ static int score_launch(wfahip_ctx *ctx, int stage, KParams &P, const ScoreRoute
     long_main = n_listed > n_pairs - n_long;  // it took more pairs of the call than the short kernel
     if (n_listed) {
         KParams PL = P;
-        PL.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
+        // (the words the table points into: ctx->mx_words, where the byte entries packed them and the host packed entry uploaded them --
+        // or, the call naming words that are not the context's, wfahip_score_batch_packed_device's: the caller's own)
+        if (stage != STAGE_PACKED) PL.mx_words = static_cast<const uint32_t *>(ctx->mx_words.p);
         PL.lds_seq_words = score_long_window(ctx->opt_score_long_window);
         const size_t lds_l = (size_t)score_long_lds_words(PL.lds_seq_words) * 4;
         for (uint64_t c0 = 0; c0 < n_listed; c0 += chunk) {
@@ -725,6 +728,210 @@ extern "C" int wfahip_debug_score_device_list(wfahip_ctx *ctx, uint32_t **words,
     }
     *words = w, *n_words = nw, *table = t, *n_listed = nl;
     return WFAHIP_OK;
+}
+
+// ---- score only on device-resident packed input, both strands (wfahip_score_batch_packed_device): score_batch_packed_impl with
+// everything it does on the host done by the kernels at the end of wfa_score_dev.hpp, a sibling of score_batch_device_impl.  The host
+// sees two blocks of SDC_WORDS counters -- after the plan (bounds verdict, longest read, whether a flag is set, long pairs, the words
+// of the flagged long queries' reverse complements), after the redo count (pairs of the full path, their words, their longest read).
+// Packed input has no byte outside ACGT: the plan's write launch emits wfa_score_long_kernel's table itself, pointing into the caller's
+// words; a flagged long query is read from ctx->mx_words, where wfa_score_rcq_kernel has written its reverse complement (the caller's
+// buffer cannot be written behind).  The pairs handed back have their words gathered into ctx->sd_words, flags applied, and take
+// align_packed_device_impl without flags.
+static int score_batch_packed_device_impl(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words, const void *d_q_woff,
+                                          const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n_pairs,
+                                          uint32_t max_len, uint32_t max_score, void *d_status, void *d_score, hipStream_t st) {
+    // (none of these checks dereferences ctx)
+    if (!ctx || !p) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs && (!d_q_woff || !d_q_len || !d_t_woff || !d_t_len || !d_status || !d_score)) return WFAHIP_ERR_BAD_ARG;
+    if (!d_packed && n_words) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs > 0xFFFFFFF0ull || n_words > (1ull << 58)) return WFAHIP_ERR_BAD_ARG;  // (align_packed_device_impl's limits)
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (n_pairs == 0) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    const auto    t_start = std::chrono::steady_clock::now();
+    wfahip_timing tm{};
+    ctx->sd_n_words = ctx->sd_n_listed = 0;  // (what wfahip_score_batch_device left in mx_words / mx_seq is gone)
+    KParams          P{};
+    const ScoreRoute R = score_route(P, p);
+
+    const uint64_t n_tiles = (n_pairs + SD_TILE - 1) / SD_TILE;
+    if ((rc = ensure(ctx, ctx->sd_ctl, SDC_WORDS * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->sd_blk, n_tiles * sizeof(SDSum)))) return rc;
+    SDParams S{};
+    // (n_words == 0: every pair is empty or too long and no word is read -- the kernels still get an address)
+    S.pk_words = d_packed ? static_cast<const uint32_t *>(d_packed) : reinterpret_cast<const uint32_t *>(ctx->sd_ctl.p);
+    S.n_words = n_words, S.q_rc = static_cast<const uint8_t *>(d_q_rc);
+    S.q_off = static_cast<const uint64_t *>(d_q_woff), S.t_off = static_cast<const uint64_t *>(d_t_woff);
+    S.q_len = static_cast<const uint32_t *>(d_q_len), S.t_len = static_cast<const uint32_t *>(d_t_len);
+    S.ctl = static_cast<unsigned long long *>(ctx->sd_ctl.p), S.blk = static_cast<SDSum *>(ctx->sd_blk.p);
+    S.d_status = static_cast<int32_t *>(d_status), S.d_score = static_cast<uint32_t *>(d_score), S.max_score = max_score;
+    const auto count_and_scan = [&](int k, uint64_t items, uint32_t c_cnt, uint32_t c_wt) -> int {
+        const uint64_t tiles = (items + SD_TILE - 1) / SD_TILE;
+        SDParams       T = S;
+        T.n = items;
+        HIP_TRY(wfa_launch_score_dev(k, T, (uint32_t)tiles, st));
+        T.n = tiles, T.c_cnt = c_cnt, T.c_wt = c_wt;
+        HIP_TRY(wfa_launch_score_dev(SDK_SCAN, T, 1, st));
+        return WFAHIP_OK;
+    };
+    const auto launch = [&](int k, uint64_t items, uint64_t groups) -> int {
+        SDParams T = S;
+        T.n = items;
+        HIP_TRY(wfa_launch_score_dev(k, T, (uint32_t)groups, st));
+        return WFAHIP_OK;
+    };
+    uint64_t   hc[SDC_WORDS];
+    const auto fetch_ctl = [&]() -> int {  // (through the context's pinned block: a pageable copy of 64 bytes costs 0.3 ms)
+        HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, S.ctl, SDC_WORDS * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(hc, ctx->hpin + HPIN_CTRL, SDC_WORDS * 8);
+        return WFAHIP_OK;
+    };
+
+    // ---- plan: bounds in words, the longest read, whether a flag is set, the long pairs.  No kernel that reads a packed word runs
+    // before its verdict is in
+    HIP_TRY(hipMemsetAsync(S.ctl, 0, SDC_WORDS * 8, st));
+    S.want_long = (R.on_kernel && R.glob) ? 1u : 0u;
+    if ((rc = count_and_scan(SDK_PK_PLAN_COUNT, n_pairs, SDC_N_LONG, SDC_N_WORDS))) return rc;
+    if ((rc = fetch_ctl())) return rc;
+    if (hc[SDC_BOUNDS] != 0) return WFAHIP_ERR_BAD_ARG;
+    if (max_len == 0) max_len = (uint32_t)std::max<uint64_t>(1, hc[SDC_MAX_LEN]);
+    if (hc[SDC_ANY_RC] == 0) S.q_rc = nullptr;  // a call whose flags are all zero is the call without flags: the same route
+    const uint64_t n_long = hc[SDC_N_LONG], rc_words = hc[SDC_N_WORDS];
+    const bool     use_long = n_long != 0 && (int64_t)n_long >= ctx->opt_score_long_min;
+    if (R.on_kernel) {
+        if ((rc = ensure(ctx, ctx->score_out, n_pairs * 8))) return rc;
+        S.score_out = static_cast<uint2 *>(ctx->score_out.p);
+        if (use_long) {
+            // ---- the long pairs: tabled where they lie in the caller's words; the flagged ones' queries reverse-complemented into
+            // scratch, one per flagged long pair
+            if ((rc = ensure(ctx, ctx->mx_seq, n_long * 32))) return rc;
+            if ((rc = ensure(ctx, ctx->mx_words, (size_t)(rc_words + 4) * 4))) return rc;
+            S.table = static_cast<uint4 *>(ctx->mx_seq.p), S.rc_words = static_cast<uint32_t *>(ctx->mx_words.p);
+            if ((rc = launch(SDK_PK_PLAN_WRITE, n_pairs, n_tiles))) return rc;
+            if (rc_words && (rc = launch(SDK_PK_RCQ, n_long, n_long))) return rc;
+            if (rc_words) tm.n_launches++;
+        }
+        // ---- the score kernels, as wfahip_score_batch_packed launches them
+        const bool skip_short = use_long && n_long == n_pairs;
+        P.mx_words = S.pk_words, P.mx_rc_words = static_cast<const uint32_t *>(ctx->mx_words.p);
+        P.q_off = S.q_off, P.t_off = S.t_off, P.q_len = S.q_len, P.t_len = S.t_len, P.q_rc = S.q_rc;
+        P.score_out = S.score_out, P.max_score = max_score;
+        bool long_main = false;
+        if ((rc = score_launch(ctx, STAGE_PACKED, P, R, n_pairs, max_len, skip_short, use_long ? n_long : 0, n_long, st, tm, long_main, 0))) return rc;
+        tm.main_kernel_kind = R.glob ? (long_main ? K_SCORE_LONG : K_SCORE) : K_SCORE_WIDE;
+    }
+    // ---- what they handed back (every pair, for a shape without an instance): counted, then gathered in pair order
+    S.all = R.on_kernel ? 0u : 1u;
+    if ((rc = count_and_scan(SDK_PK_REDO_COUNT, n_pairs, SDC_N_REDO, SDC_REDO_SUM))) return rc;
+    if (R.on_kernel && (rc = launch(SDK_FINISH, n_pairs, (n_pairs + SD_BLOCK - 1) / SD_BLOCK))) return rc;
+    if ((rc = fetch_ctl())) return rc;
+    if (R.on_kernel) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        tm.kernel_ms = tm.main_kernel_ms = ms;
+    }
+    const uint64_t n_redo = hc[SDC_N_REDO], g_words = hc[SDC_REDO_SUM];
+    const uint32_t fb_max = (uint32_t)std::max<uint64_t>(1, hc[SDC_REDO_MAX]);
+    if (n_redo) {
+        // r_qoff | r_toff | r_id | r_qlen | r_tlen | r_rc
+        if ((rc = ensure(ctx, ctx->sd_redo, n_redo * 29))) return rc;
+        if ((rc = ensure(ctx, ctx->sd_words, (size_t)(g_words + 4) * 4))) return rc;  // (+16 bytes, as the entry asks of its caller)
+        S.r_qoff = static_cast<uint64_t *>(ctx->sd_redo.p), S.r_toff = S.r_qoff + n_redo;
+        S.r_id = reinterpret_cast<uint32_t *>(S.r_toff + n_redo), S.r_qlen = S.r_id + n_redo, S.r_tlen = S.r_qlen + n_redo;
+        S.r_rc = reinterpret_cast<uint8_t *>(S.r_tlen + n_redo), S.g_words = static_cast<uint32_t *>(ctx->sd_words.p);
+        if ((rc = launch(SDK_PK_REDO_WRITE, n_pairs, n_tiles))) return rc;
+        if ((rc = launch(SDK_PK_GATHER, n_redo, std::min<uint64_t>((2 * n_redo + SD_BLOCK / 64 - 1) / (SD_BLOCK / 64), 1u << 16)))) return rc;
+        for (uint64_t a = 0; a < n_redo; a += SD_FB_PAIRS) {
+            const uint64_t nb = std::min(SD_FB_PAIRS, n_redo - a);
+            if ((rc = ensure(ctx, ctx->out_rec, nb * REC_WORDS * 4))) return rc;
+            // CIGAR ops are merged runs: the host entry's first guess, (n+m)/4 + 8 per pair, run again once with what was needed
+            uint64_t ops_cap = std::min<uint64_t>(16 * g_words, 2ull * fb_max * nb) / 4 + 8 * nb + 1024;
+            for (int attempt = 0;; attempt++) {
+                if ((rc = ensure(ctx, ctx->out_ops, ops_cap * 8))) return rc;
+                uint64_t   needed = 0;
+                BoundScope bound(ctx, max_score);  // (the full path stops and filters by it)
+                rc = align_packed_device_impl(ctx, p, S.g_words, g_words, S.r_qoff + a, S.r_qlen + a, S.r_toff + a, S.r_tlen + a, nullptr, nb, fb_max,
+                                              ctx->out_rec.p, ctx->out_ops.p, ops_cap, &needed, st);
+                if (rc == WFAHIP_ERR_OOM && needed > ops_cap && attempt == 0) {
+                    ops_cap = needed;
+                    continue;
+                }
+                break;
+            }
+            if (rc) return rc;
+            const wfahip_timing &f = ctx->timing;
+            tm.kernel_ms += f.kernel_ms, tm.n_launches += f.n_launches, tm.arena_bytes = std::max(tm.arena_bytes, f.arena_bytes);
+            if (!R.on_kernel && a == 0) tm.main_kernel_ms = f.main_kernel_ms, tm.n_main_launches = f.n_main_launches, tm.main_kernel_kind = f.main_kernel_kind;
+            SDParams T = S;
+            T.n = nb, T.first = a, T.rec = static_cast<const uint32_t *>(ctx->out_rec.p);
+            HIP_TRY(wfa_launch_score_dev(SDK_FINISH, T, (uint32_t)((nb + SD_BLOCK - 1) / SD_BLOCK), st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    tm.n_retried_pairs = (uint32_t)std::min<uint64_t>(n_redo, UINT32_MAX);
+    tm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    ctx->timing = tm;
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_score_batch_packed_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_packed, uint64_t n_words,
+                                                const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len,
+                                                const void *d_q_rc, uint64_t n_pairs, uint32_t max_len, uint32_t max_score, void *d_status,
+                                                void *d_score, void *stream) {
+    WFAHIP_GUARD(score_batch_packed_device_impl(ctx, p, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc, n_pairs, max_len, max_score,
+                                                d_status, d_score, static_cast<hipStream_t>(stream)))
+}
+
+// ---- the survivors of a screen as the next stage's arrays (wfahip_select_pairs_device): a stable compaction of the pairs whose status is
+// WFAHIP_PAIR_OK -- two launches of wfa_score_select_kernel with the scan between them, one fetch of the count.  The offsets are
+// opaque: what comes out feeds wfahip_align_batch_packed_device or wfahip_align_batch_device as it is.
+static int select_pairs_device_impl(wfahip_ctx *ctx, const void *d_status, uint64_t n_pairs, const void *d_q_off, const void *d_q_len,
+                                    const void *d_t_off, const void *d_t_len, const void *d_q_rc, void *d_idx, void *d_q_off_out, void *d_q_len_out,
+                                    void *d_t_off_out, void *d_t_len_out, void *d_q_rc_out, uint64_t *n_selected, hipStream_t st) {
+    // (none of these checks dereferences ctx)
+    if (!ctx || !n_selected) return WFAHIP_ERR_BAD_ARG;
+    if (n_pairs && (!d_status || !d_q_off || !d_q_len || !d_t_off || !d_t_len || !d_q_off_out || !d_q_len_out || !d_t_off_out || !d_t_len_out))
+        return WFAHIP_ERR_BAD_ARG;
+    if ((d_q_rc == nullptr) != (d_q_rc_out == nullptr) || n_pairs > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;
+    *n_selected = 0;
+    if (n_pairs == 0) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    const uint64_t n_tiles = (n_pairs + SD_TILE - 1) / SD_TILE;
+    int            rc;
+    if ((rc = ensure(ctx, ctx->sd_ctl, SDC_WORDS * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->sd_blk, n_tiles * sizeof(SDSum)))) return rc;
+    SDParams S{};
+    S.sel_status = static_cast<const int32_t *>(d_status), S.n = n_pairs;
+    S.q_off = static_cast<const uint64_t *>(d_q_off), S.t_off = static_cast<const uint64_t *>(d_t_off);
+    S.q_len = static_cast<const uint32_t *>(d_q_len), S.t_len = static_cast<const uint32_t *>(d_t_len), S.q_rc = static_cast<const uint8_t *>(d_q_rc);
+    S.r_id = static_cast<uint32_t *>(d_idx), S.r_qoff = static_cast<uint64_t *>(d_q_off_out), S.r_toff = static_cast<uint64_t *>(d_t_off_out);
+    S.r_qlen = static_cast<uint32_t *>(d_q_len_out), S.r_tlen = static_cast<uint32_t *>(d_t_len_out), S.r_rc = static_cast<uint8_t *>(d_q_rc_out);
+    S.ctl = static_cast<unsigned long long *>(ctx->sd_ctl.p), S.blk = static_cast<SDSum *>(ctx->sd_blk.p);
+    HIP_TRY(wfa_launch_score_dev(SDK_SELECT_COUNT, S, (uint32_t)n_tiles, st));
+    SDParams T = S;
+    T.n = n_tiles, T.c_cnt = SDC_N_REDO, T.c_wt = SDC_REDO_SUM;
+    HIP_TRY(wfa_launch_score_dev(SDK_SCAN, T, 1, st));
+    HIP_TRY(wfa_launch_score_dev(SDK_SELECT_WRITE, S, (uint32_t)n_tiles, st));
+    // (through the context's pinned block: a pageable copy of 64 bytes costs 0.3 ms)
+    HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, S.ctl, SDC_WORDS * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t hc[SDC_WORDS];
+    std::memcpy(hc, ctx->hpin + HPIN_CTRL, SDC_WORDS * 8);
+    *n_selected = hc[SDC_N_REDO];
+    return WFAHIP_OK;
+}
+
+extern "C" int wfahip_select_pairs_device(wfahip_ctx *ctx, const void *d_status, uint64_t n_pairs, const void *d_q_off, const void *d_q_len,
+                                          const void *d_t_off, const void *d_t_len, const void *d_q_rc, void *d_idx, void *d_q_off_out,
+                                          void *d_q_len_out, void *d_t_off_out, void *d_t_len_out, void *d_q_rc_out, uint64_t *n_selected,
+                                          void *stream) {
+    WFAHIP_GUARD(select_pairs_device_impl(ctx, d_status, n_pairs, d_q_off, d_q_len, d_t_off, d_t_len, d_q_rc, d_idx, d_q_off_out, d_q_len_out,
+                                          d_t_off_out, d_t_len_out, d_q_rc_out, n_selected, static_cast<hipStream_t>(stream)))
 }
 
 // ---- score matrix (wfahip_score_matrix): every query against every target, score only.  The n_q + n_t sequences are packed and

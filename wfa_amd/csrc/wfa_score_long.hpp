@@ -11,7 +11,8 @@
 //     group from the window when both its words are inside, and from global memory when not: results never depend on the
 //     window's size or position, and a match run longer than the window simply finishes on global loads.
 // A wave per pair, a lane per diagonal, tiles of 64 diagonals.  The pairs are a list: entry 2i / 2i + 1 of P.mx_seq name the query
-// / the target of pair i ({word offset lo, hi, length, -} into P.mx_words; the query's .w is the pair's slot of P.score_out).
+// / the target of pair i ({word offset lo, hi, length, -} into P.mx_words; the query's .w is the pair's slot of P.score_out; the target's
+// .w != 0: the query's offset counts from P.mx_rc_words instead -- wfahip_score_batch_packed_device's flagged queries).
 // MATRIX: the pair is a cell of a tile (wfa_matrix.hpp) and the kernel takes the cells with a sequence flagged MXF_LONG only --
 // the others belong to wfa_score_kernel<MATRIX>, launched over the same tile.
 // A query flagged for its reverse complement (wfahip_score_batch_packed_rc, wfahip_score_matrix_rc) is read from words wfa_rc_words_kernel
@@ -88,9 +89,18 @@ __global__ __launch_bounds__(64) void wfa_score_long_kernel(const KParams P) {
     const auto emit = [&](uint32_t st, uint32_t sc) {
         if (lane == 0) P.score_out[slot] = make_uint2(st, sc);
     };
-    // (a flagged query row of the matrix: the words wfa_rc_words_kernel wrote; the list's entry of a flagged pair names them itself)
-    const uint32_t *const gq = P.mx_words + ((uint64_t)qd.y << 32 | qd.x) + ((MATRIX && (qd.w & MXF_RC) != 0u) ? P.mx_rc_shift : 0ull);
+    // (a flagged query row of the matrix: the words wfa_rc_words_kernel wrote; the list's entry of a flagged pair names them itself --
+    // in P.mx_words, or, the pair's target entry carrying .w != 0, in P.mx_rc_words: wfahip_score_batch_packed_device, whose words
+    // are the caller's and cannot be written behind)
+    const uint32_t *const gq = ((!MATRIX && td.w != 0u) ? P.mx_rc_words : P.mx_words) + ((uint64_t)qd.y << 32 | qd.x) +
+                               ((MATRIX && (qd.w & MXF_RC) != 0u) ? P.mx_rc_shift : 0ull);
     const uint32_t *const gt = P.mx_words + ((uint64_t)td.y << 32 | td.x);
+    // (the select above is 20 bytes of scalar code; 44 more, run once per pair, put the row loop's instructions back where they lay in
+    // their 64-byte lines before it existed -- 20 bytes off them 2e4 x 50 kbp pairs took 129.7 ms in place of 127.6: KERNELS.md 4s)
+    if constexpr (!MATRIX) {
+#pragma unroll
+        for (int k = 0; k < 11; k++) asm volatile("s_nop 0");
+    }
     const int      n = (int)qd.z, m = (int)td.z, Ak = m - n;
     const uint32_t nwq = (qd.z + 15u) >> 4, nwt = (td.z + 15u) >> 4;  // index of each sequence's pad word
 
