@@ -611,6 +611,54 @@ int  wfahip_alignment_text(const wfahip_results *r, const uint8_t *seq_blob, uin
                            int n_threads, wfahip_align_texts *out);
 void wfahip_align_texts_free(wfahip_align_texts *t);
 
+/* The display rows from 2-bit packed words, both strands: the last product of the chain pack (wfahip_pack_pairs_device) -> score ->
+ * select -> align (wfahip_align_batch_packed_device) -> text, with no sequence byte anywhere.  For a flagged pair (q_rc[i] != 0) the
+ * record's QBEGIN / QEND and every op are coordinates on the reverse-complemented query, bytes that exist nowhere a caller can point
+ * to: the rows are rendered straight from the words, a flagged query reverse-complemented as it is read.  The decoding rule
+ * (wfa_amd/csrc/wfa_altext_pk.hpp, one source for the kernels and the host renderer): the letter of a code is "ACTG"[code]; base p of
+ * a forward sequence is bits 2 (p % 16) .. of word p / 16; base p of a flagged query of len bases is the complement (code ^ 2) of
+ * forward base len - 1 - p.  The rows equal, byte for byte, what wfahip_alignment_text_device writes for the same records and ops
+ * over a byte blob in which pair i's query is the letters of its words, reverse-complemented if flagged, and its target the letters
+ * of its words.
+ *
+ * wfahip_alignment_text_packed_device: d_rec / d_ops as wfahip_align_batch_packed_device left them, or any records and ops of that
+ * layout; the words, the offsets (u64), lengths (u32) and flags (u8 per pair, NULL = none set) are the ones that call was given.
+ * Offsets may come in any order, repeat, and name one offset under different lengths and flags; the offsets of a pair that renders
+ * nothing (status not OK, OPS_LEN 0, no column, no 'M' op under only_aligned) are never looked at.  Of a sequence that renders only
+ * words in [woff, woff + wfahip_packed_words(len)) are read; no result depends on the bits of its last word beyond its last base or
+ * on its pad word; d_packed needs NO readable memory behind its n_words words for this entry.
+ * Planes, d_row_off, *row_needed, row_cap, WFAHIP_ERR_OOM (planes untouched, d_row_off filled: size with null planes and row_cap = 0,
+ * call again), n_pairs == 0, stream, synchrony and wfahip_last_timing (untouched) are wfahip_alignment_text_device's, word for word;
+ * no input is written.  The checks, made for every OK pair with an op that renders, are that entry's with the blob check replaced:
+ * the ops lie in [0, ops_cap); for both sequences woff <= n_words and wfahip_packed_words(len) <= n_words - woff (compared without a
+ * sum that could wrap); trimmed, 1 <= BEGIN, BEGIN - 1 <= END and END <= the sequence's length; the query and target bases the ops
+ * consume, as 64-bit sums, do not exceed the window.  A failed check: WFAHIP_ERR_BAD_ARG with the planes untouched, before the kernel
+ * that reads ops or words to write rows is launched.  The wf-adaptive pair whose ops consume one base more than the sequences hold
+ * is refused untrimmed and renders trimmed, as there.  WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx; with
+ * n_pairs > 0 a null d_rec, d_row_off, d_q_woff, d_q_len, d_t_woff or d_t_len; a null d_ops with ops_cap > 0; a null d_packed with
+ * n_words > 0; a null plane with row_cap > 0; n_pairs beyond 0xFFFFFFF0.
+ * Three passes (wfa_cigar.hip): wfa_altext_pk_len_kernel, the byte entry's length kernel with the window check on words; the same
+ * scan; wfa_altext_pk_write_kernel, the byte entry's rounds, groups and stores, a group of four columns inside one op taking its
+ * letters from two words by a funnel shift and one v_perm_b32, a flagged query's from the four bases that end at len - 1 - p
+ * (KERNELS.md 4t).  1e6 x 1 kbp pairs, every second one flagged, 3 x 1 014 bytes each: 4.9 ms for the three passes against 4.3 ms for
+ * wfahip_alignment_text_device on the same records over bytes -- the decoding costs 0.6 ms of the write pass.  WFAHIP_DEBUG_TIMING=1
+ * prints the passes' times to stderr. */
+int  wfahip_alignment_text_packed_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                         const void *d_packed, uint64_t n_words, const void *d_q_woff, const void *d_q_len,
+                                         const void *d_t_woff, const void *d_t_len, const void *d_q_rc /* u8 per pair, NULL = none */,
+                                         uint64_t n_pairs, int only_aligned, void *d_q_row, void *d_a_row, void *d_t_row,
+                                         uint64_t row_cap, void *d_row_off /* u64[n_pairs + 1] */, uint64_t *row_needed, void *stream);
+
+/* Host only, no device, no context: the same bytes and offsets for a wfahip_results in host memory -- wfahip_align_batch_packed_rc's,
+ * or wfahip_align_batch_packed's with q_rc = NULL -- and the words, offsets, lengths and flags it was aligned from.  Everything else
+ * as wfahip_alignment_text: the same out, released with wfahip_align_texts_free and zeroed on an error; n_threads host threads; the
+ * same header functions as the kernels; WFAHIP_ERR_BAD_ARG for a null r or out, with r->n > 0 a null status, ops_off, ops_len,
+ * offset or length array, under only_aligned a null qbegin, qend, tbegin or tend, a null ops with n_ops > 0, a null packed with
+ * n_words > 0, and a pair that fails a check of the device entry (with n_ops as ops_cap). */
+int  wfahip_alignment_text_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                                  const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                  const uint8_t *q_rc /* NULL = none */, int only_aligned, int n_threads, wfahip_align_texts *out);
+
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns
  * at once with the pair's ticket (0, 1, 2, ... since the last collect) -- and collects all results with ONE batch

@@ -8,4 +8,5 @@ from .aligner import (  # noqa: F401
     DefaultPenalties, ErrEmptySeq, ErrOverMaxScore, ErrSeqTooLong, MaskLower32, MaxSeqLen, New, Op, OpD, OpH, OpI, OpM, OpX,
     Options, Penalties, RecycleAligner, RecycleAlignmentResult, RecycleAlignmentText, WfaError, generate_pairs,
     make_blob, plot_component, trimOps, wide_class_bounds, revcomp_packed, best_strand, cigar_text, alignment_text,
+    alignment_text_packed,
 )

@@ -35,6 +35,7 @@ EXPORTS = [
     "wfahip_alignment_text_device", "wfahip_alignment_text", "wfahip_align_texts_free",
     "wfahip_pack_pairs_device", "wfahip_align_batch_packed_device",
     "wfahip_score_batch_packed_device", "wfahip_select_pairs_device",
+    "wfahip_alignment_text_packed_device", "wfahip_alignment_text_packed",
 ]
 
 
@@ -153,6 +154,11 @@ def lib():
         L.wfahip_alignment_text.restype = C.c_int
         L.wfahip_alignment_text.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(AlignTexts)]
         L.wfahip_align_texts_free.argtypes = [C.POINTER(AlignTexts)]
+        L.wfahip_alignment_text_packed_device.restype = C.c_int
+        L.wfahip_alignment_text_packed_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, C.c_int, vp, vp, vp, u64, vp,
+                                                          C.POINTER(u64), vp]
+        L.wfahip_alignment_text_packed.restype = C.c_int
+        L.wfahip_alignment_text_packed.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(AlignTexts)]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

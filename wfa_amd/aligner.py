@@ -784,6 +784,52 @@ class Aligner:
         n = int(rec.shape[0])
         if q_off.numel() != n or q_len.numel() != n or t_off.numel() != n or t_len.numel() != n:
             raise ValueError("offset and length tensors must hold one element per record")
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+
+        def entry(rows, cap, off, needed, stream):
+            return L.lib().wfahip_alignment_text_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(blob), blob.numel(),
+                                                    q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n,
+                                                    1 if only_aligned else 0, *rows, cap, off.data_ptr(), C.byref(needed),
+                                                    stream.cuda_stream)
+        return self._render_rows(n, dev, out, stream, entry, "wfahip_alignment_text_device")
+
+    def alignment_text_tensors_packed(self, rec, ops, packed, q_woff, q_len, t_woff, t_len, q_rc=None, only_aligned: bool = False,
+                                      out=None, stream=None):
+        """alignment_text_tensors over 2-bit words, both strands (include/wfa_hip.h: wfahip_alignment_text_packed_device): (rec, ops)
+        are align_tensors_packed's output, packed / q_woff / q_len / t_woff / t_len / q_rc the tensors that call was given -- packed
+        int32 (every word of the tensor counts: this entry needs no slack, and slack does no harm), q_woff / t_woff int64, q_len /
+        t_len int32, q_rc an optional uint8 tensor of one flag per pair.  The query row of a flagged pair holds the reverse
+        complement of its query, the strand its record and ops speak of.  Returns, out=, errors, stream and ValueErrors as
+        alignment_text_tensors; the rows equal that method's over the corresponding bytes."""
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        self._want_tensor("packed", packed, torch.int32, dev)
+        for name, t, dtype in (("q_woff", q_woff, torch.int64), ("q_len", q_len, torch.int32), ("t_woff", t_woff, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(rec.shape[0])
+        if q_woff.numel() != n or q_len.numel() != n or t_woff.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors must hold one element per record")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+
+        def entry(rows, cap, off, needed, stream):
+            return L.lib().wfahip_alignment_text_packed_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(packed), packed.numel(),
+                                                           q_woff.data_ptr(), q_len.data_ptr(), t_woff.data_ptr(), t_len.data_ptr(),
+                                                           ptr(q_rc), n, 1 if only_aligned else 0, *rows, cap, off.data_ptr(),
+                                                           C.byref(needed), stream.cuda_stream)
+        return self._render_rows(n, dev, out, stream, entry, "wfahip_alignment_text_packed_device")
+
+    def _render_rows(self, n, dev, out, stream, entry, what):
+        """what the row methods share: out= checked, one sizing call and one that writes (or one into out), the error raised.
+        entry(rows, cap, off, needed, stream) is the C call with three plane pointers of capacity cap."""
+        import torch
         if out is not None:
             try:
                 q_row, a_row, t_row, off = out
@@ -806,17 +852,12 @@ class Aligner:
                 off[:1] = 0
                 return q_row, a_row, t_row, off
             return empty(), empty(), empty(), off
-        lib = L.lib()
         needed = C.c_uint64(0)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
 
         def call(planes):
             cap = planes[0].numel() if planes else 0
-            rows = [ptr(p) for p in planes] if cap else [None] * 3
-            return lib.wfahip_alignment_text_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(blob), blob.numel(),
-                                                    q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n,
-                                                    1 if only_aligned else 0, *rows, cap, off.data_ptr(), C.byref(needed),
-                                                    stream.cuda_stream)
+            rows = [p.data_ptr() for p in planes] if cap else [None] * 3
+            return entry(rows, cap, off, needed, stream)
         if out is None:
             rc = call(None)  # the sizing call
             if rc == L.ERR_OOM:
@@ -826,7 +867,7 @@ class Aligner:
                 q_row, a_row, t_row = empty(), empty(), empty()
         else:
             rc = call((q_row, a_row, t_row))
-        L.check(rc, "wfahip_alignment_text_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        L.check(rc, what + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return q_row, a_row, t_row, off
 
     def align_arrays_text(self, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False):
@@ -1154,22 +1195,49 @@ def alignment_text(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len
     np.uint8, t_row np.uint8, off np.uint64 [n + 1]); pair i's rows are the three arrays' [off[i]:off[i + 1]], empty for a pair
     that is not OK and, under only_aligned, for one without an M op.  ValueError for arrays of the wrong shape; WfaHipError
     (ERR_BAD_ARG) when an OK pair's ops lie outside batch_result.ops, or its ops or windows leave the sequences."""
-    br = batch_result
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    return _host_rows(batch_result, blob, "blob", q_off, q_len, t_off, t_len, None, n_threads,
+                      lambda res, q_off, q_len, t_off, t_len, q_rc, txt: L.lib().wfahip_alignment_text(
+                          C.byref(res), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len), 1 if only_aligned else 0,
+                          int(n_threads), C.byref(txt)), "wfahip_alignment_text")
+
+
+def alignment_text_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_woff, t_len, q_rc=None, only_aligned: bool = False,
+                          n_threads: int = 8):
+    """alignment_text over 2-bit words, both strands (include/wfa_hip.h: wfahip_alignment_text_packed; no GPU, no Aligner): the rows
+    of a BatchResult of align_arrays_packed_rc (or align_arrays_packed, q_rc=None) from the words, offsets, lengths and flags it was
+    aligned from.  The query row of a flagged pair holds the reverse complement of its query, the strand its record and ops speak
+    of.  Returns and errors as alignment_text."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    return _host_rows(batch_result, packed, "packed", q_woff, q_len, t_woff, t_len, q_rc, n_threads,
+                      lambda res, q_woff, q_len, t_woff, t_len, q_rc, txt: L.lib().wfahip_alignment_text_packed(
+                          C.byref(res), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff), vp(t_len), vp(q_rc),
+                          1 if only_aligned else 0, int(n_threads), C.byref(txt)), "wfahip_alignment_text_packed")
+
+
+def _host_rows(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, n_threads, call, what):
+    """what the host row renderers share: the arrays made contiguous and checked, the wfahip_results view of the BatchResult,
+    call(res, q_off, q_len, t_off, t_len, q_rc, txt) -- the C entry --, and the rows copied out of its struct"""
     status = np.ascontiguousarray(br.status, dtype=np.int32)
     ops_off = np.ascontiguousarray(br.ops_off, dtype=np.uint64)
     ops_len = np.ascontiguousarray(br.ops_len, dtype=np.uint32)
     ops = np.ascontiguousarray(br.ops, dtype=np.uint64)
     windows = [np.ascontiguousarray(getattr(br, f), dtype=np.int32) for f in ("qbegin", "qend", "tbegin", "tend")]
-    blob = np.ascontiguousarray(blob, dtype=np.uint8)
     q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
     t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
     q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
     t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
     n = int(status.size)
-    if status.ndim != 1 or ops.ndim != 1 or blob.ndim != 1:
-        raise ValueError("status, ops and blob must be one-dimensional")
+    if status.ndim != 1 or ops.ndim != 1 or seqs.ndim != 1:
+        raise ValueError(f"status, ops and {seqs_name} must be one-dimensional")
     if any(a.shape != (n,) for a in [ops_off, ops_len, q_off, q_len, t_off, t_len] + windows):
         raise ValueError("ops_off, ops_len, qbegin, qend, tbegin, tend and the offset and length arrays must hold one element per pair")
+    if q_rc is not None:
+        q_rc = np.ascontiguousarray(q_rc, dtype=np.uint8)
+        if q_rc.shape != (n,):
+            raise ValueError("q_rc must hold one flag per pair")
     if int(n_threads) < 1:
         raise ValueError("n_threads must be at least 1")
     res = L.Results()
@@ -1179,10 +1247,8 @@ def alignment_text(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len
     res.ops_len = ops_len.ctypes.data_as(C.POINTER(C.c_uint32))
     res.ops = ops.ctypes.data_as(C.POINTER(C.c_uint64))
     res.qbegin, res.qend, res.tbegin, res.tend = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in windows)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     txt = L.AlignTexts()
-    L.check(L.lib().wfahip_alignment_text(C.byref(res), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len),
-                                          1 if only_aligned else 0, int(n_threads), C.byref(txt)), "wfahip_alignment_text")
+    L.check(call(res, q_off, q_len, t_off, t_len, q_rc, txt), what)
     try:
         nb = int(txt.n_bytes)
         rows = [np.ctypeslib.as_array(p, shape=(nb,)).copy() if nb else np.zeros(0, dtype=np.uint8) for p in (txt.q_row, txt.a_row, txt.t_row)]

@@ -17,10 +17,16 @@
 // wfa_altext.hpp's) are the same three passes with the same scan kernels: wfa_altext_len_kernel adds the columns and the bases a
 // pair's ops consume and checks them against the windows of its sequences, wfa_altext_write_kernel expands the runs -- a wave per
 // pair in rounds of 64 ops, the round's table of starts in LDS, the lanes sweeping the round's columns four to a lane.
+//
+// The rows from 2-bit packed words, both strands (wfahip_alignment_text_packed_device, wfahip_alignment_text_packed; the decoding
+// rule is wfa_altext_pk.hpp's): the same passes again, wfa_altext_pk_len_kernel with the window check on words and
+// wfa_altext_pk_write_kernel, whose lanes take four letters out of two words by a funnel shift where the byte kernel loads four
+// bytes, a flagged query's from the far end of its words, reversed and complemented (KERNELS.md 4t).
 #include "wfa_ctx.hpp"
 #include "wfa_hostpack.hpp"
 #include "wfa_cigar.hpp"
 #include "wfa_altext.hpp"
+#include "wfa_altext_pk.hpp"
 
 using namespace wfa;
 
@@ -53,6 +59,18 @@ struct AltParams {
     const uint32_t *q_len, *t_len;  // [n]
     uint8_t        *q_row, *a_row, *t_row;
     uint32_t        dwords;  // != 0: the three planes are 4-byte aligned, four columns go out as one store
+};
+
+// the display rows from packed words: AltParams with the words in place of the blob, word offsets, and a flag per pair
+struct AltPkParams {
+    CigParams       C;
+    const uint32_t *words;
+    uint64_t        n_words;
+    const uint64_t *q_woff, *t_woff;  // [n]
+    const uint32_t *q_len, *t_len;    // [n]
+    const uint8_t  *q_rc;             // [n] or null: != 0, the query is read reverse-complemented
+    uint8_t        *q_row, *a_row, *t_row;
+    uint32_t        dwords;
 };
 
 }  // namespace
@@ -205,11 +223,13 @@ __device__ __forceinline__ uint32_t alt_load4(const uint8_t *p) {  // four bytes
 }
 
 // rows, pass 1: the range of each pair's ops that renders, its columns, and every check that keeps pass 3 inside the op buffer,
-// the blob and the windows.  A pair that fails one raises CIG_BAD_RANGE; pass 3 is then not launched.
-__global__ __launch_bounds__(256) void wfa_altext_len_kernel(const AltParams A) {
-    const CigParams &C    = A.C;
-    const uint64_t   i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t   lane = threadIdx.x & 63;
+// the sequences and the windows -- window(i, &w) gives pair i's windows, false where they fail.  A pair that fails a check raises
+// CIG_BAD_RANGE; pass 3 is then not launched.  The byte entry checks the windows of every pair with an op in its range; the packed
+// entry (COLUMNS_ONLY) only those of a pair with a column, so that the offsets of a pair that renders nothing are never looked at.
+template <bool COLUMNS_ONLY, class Window>
+__device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window) {
+    const uint64_t i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
     if (i >= C.n) return;
     const uint64_t *ops;
     uint32_t        first, end;
@@ -225,10 +245,10 @@ __global__ __launch_bounds__(256) void wfa_altext_len_kernel(const AltParams A) 
     }
     if (lane == 0) {
         uint32_t count = end - first;
-        if (count != 0u) {
+        if (COLUMNS_ONLY ? cols != 0ull : count != 0u) {
             const AltSums all = {cols, qb, tb};
             AltWindow     w;
-            if (!alt_pair_window(A, i, &w) || !alt_fits(all, w)) {
+            if (!window(i, &w) || !alt_fits(all, w)) {
                 atomicOr(&C.ctl[CIG_BAD_RANGE], 1ull);
                 cols = 0ull;
             }
@@ -239,13 +259,32 @@ __global__ __launch_bounds__(256) void wfa_altext_len_kernel(const AltParams A) 
     }
 }
 
+__global__ __launch_bounds__(256) void wfa_altext_len_kernel(const AltParams A) {
+    alt_len_pass<false>(A.C, [&](uint64_t i, AltWindow *w) { return alt_pair_window(A, i, w); });
+}
+
+// the windows of pair i's packed sequences, in bases of each sequence (the offsets of a pair that renders nothing are not looked at:
+// only a pair with an op that renders gets here)
+__device__ __forceinline__ bool alt_pk_pair_window(const AltPkParams &A, uint64_t i, AltWindow *w) {
+    const uint32_t *r = A.C.rec + i * REC_WORDS;
+    return alt_pk_window(A.C.only_aligned != 0u, A.n_words, A.q_woff[i], A.q_len[i], A.t_woff[i], A.t_len[i], (int32_t)r[REC_QBEGIN],
+                         (int32_t)r[REC_QEND], (int32_t)r[REC_TBEGIN], (int32_t)r[REC_TEND], w);
+}
+
+__global__ __launch_bounds__(256) void wfa_altext_pk_len_kernel(const AltPkParams A) {
+    alt_len_pass<true>(A.C, [&](uint64_t i, AltWindow *w) { return alt_pk_pair_window(A, i, w); });
+}
+
 // rows, pass 3.  A round is 64 ops: a wave prefix sum gives every op its first column of the round and its first query and target
 // byte of the windows, and the table goes to the wave's LDS.  The lanes then sweep the round's columns in groups of four that are
 // aligned in the PLANE (not in the pair), consecutive lanes taking consecutive groups: a lane finds the op of its first column by a
 // search over the 64 starts and walks on from there.  A group inside one op -- most of them -- is one 4-byte load per sequence
 // and, where the planes are 4-byte aligned, one 4-byte store per plane; a group that crosses an op boundary gathers byte by byte;
 // a group cut by the round's first or last column stores bytes, and the next round stores the rest of it.
-__global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A) {
+// Where the bases come from is the kernel's: seq(i) gives pair i's source once pass 1 has found it valid, with q4(p) / t4(p) the
+// four query / target bases from base p of the window on (base p + j in bits 8 j ..) and q1(p) / t1(p) one base.
+template <class Params, class Seq>
+__device__ __forceinline__ void alt_write_pass(const Params &A, Seq &&seq) {
     __shared__ unsigned long long s_col[4][64];                      // first column of the op, in the round
     __shared__ uint32_t           s_q[4][64], s_t[4][64], s_kind[4][64];  // first query / target byte in the windows; alt_kind | a byte << 8
     const CigParams &C    = A.C;
@@ -254,11 +293,9 @@ __global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A
     if (i >= C.n) return;
     const uint2 rg = C.range[i];
     if (rg.y == 0u) return;
-    AltWindow w;
-    (void)alt_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+    const auto      S   = seq(i);
     const uint32_t *r   = C.rec + i * REC_WORDS;
     const uint64_t *ops = C.ops + ((uint64_t)r[REC_OPS_OFF_LO] | ((uint64_t)r[REC_OPS_OFF_HI] << 32)) + rg.x;
-    const uint8_t  *qs = A.blob + w.q_at, *ts = A.blob + w.t_at;
     uint64_t        g0 = C.text_off[i];  // the round's first column, as an index into the planes
     uint32_t        qc = 0u, tc = 0u;    // bases the rounds before consumed (pass 1: at most the windows' lengths)
     for (uint32_t b = 0; b < rg.y; b += 64u) {
@@ -296,8 +333,8 @@ __global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A
             uint32_t           qv = 0u, av = 0u, tv = 0u;  // the group's bytes, column g + j in bits 8 j ..
             if (j1 - j0 == 4u && c + 4u <= ce) {
                 const uint64_t d = c - cs;
-                qv = (kd & ALT_Q) ? alt_load4(qs + (uint64_t)qb + d) : ALT_GAP * 0x01010101u;
-                tv = (kd & ALT_T) ? alt_load4(ts + (uint64_t)tb + d) : ALT_GAP * 0x01010101u;
+                qv = (kd & ALT_Q) ? S.q4((uint64_t)qb + d) : ALT_GAP * 0x01010101u;
+                tv = (kd & ALT_T) ? S.t4((uint64_t)tb + d) : ALT_GAP * 0x01010101u;
                 av = (kd >> 8) * 0x01010101u;
             } else {
                 for (uint32_t j = j0; j < j1; j++, c++) {
@@ -309,7 +346,7 @@ __global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A
                         kd = s_kind[wv][k], qb = s_q[wv][k], tb = s_t[wv][k];
                     }
                     const uint64_t d  = c - cs;
-                    const uint32_t qx = (kd & ALT_Q) ? qs[(uint64_t)qb + d] : ALT_GAP, tx = (kd & ALT_T) ? ts[(uint64_t)tb + d] : ALT_GAP;
+                    const uint32_t qx = (kd & ALT_Q) ? S.q1((uint64_t)qb + d) : ALT_GAP, tx = (kd & ALT_T) ? S.t1((uint64_t)tb + d) : ALT_GAP;
                     qv |= qx << (8u * j), av |= (kd >> 8) << (8u * j), tv |= tx << (8u * j);
                 }
             }
@@ -328,6 +365,46 @@ __global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A
         g0 = gend;
         qc += __shfl(qi, 63, 64), tc += __shfl(ti, 63, 64);
     }
+}
+
+// the windows' first bytes in the blob
+struct AltByteSeq {
+    const uint8_t *qs, *ts;
+    __device__ __forceinline__ uint32_t q4(uint64_t p) const { return alt_load4(qs + p); }
+    __device__ __forceinline__ uint32_t t4(uint64_t p) const { return alt_load4(ts + p); }
+    __device__ __forceinline__ uint32_t q1(uint64_t p) const { return qs[p]; }
+    __device__ __forceinline__ uint32_t t1(uint64_t p) const { return ts[p]; }
+};
+
+__global__ __launch_bounds__(256) void wfa_altext_write_kernel(const AltParams A) {
+    alt_write_pass(A, [&](uint64_t i) {
+        AltWindow w;
+        (void)alt_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+        return AltByteSeq{A.blob + w.q_at, A.blob + w.t_at};
+    });
+}
+
+// the sequences' words and the windows' first bases.  Base p of a window is base at + p of the sequence (pass 1: at + p < len, so
+// the sums stay below 2^32); a group of four inside one op lies inside the window, which is what alt_pk_letters4 asks for.
+struct AltPkSeq {
+    const uint32_t *qw, *tw;
+    uint32_t        q_len, t_len, q_at, t_at;
+    bool            rc;  // (one pair a wave: uniform)
+    __device__ __forceinline__ uint32_t q4(uint64_t p) const { return alt_pk_letters4(qw, q_len, rc, q_at + (uint32_t)p); }
+    __device__ __forceinline__ uint32_t t4(uint64_t p) const { return alt_pk_letters4(tw, t_len, false, t_at + (uint32_t)p); }
+    __device__ __forceinline__ uint32_t q1(uint64_t p) const { return alt_pk_letter(qw, q_len, rc, q_at + (uint32_t)p); }
+    __device__ __forceinline__ uint32_t t1(uint64_t p) const { return alt_pk_letter(tw, t_len, false, t_at + (uint32_t)p); }
+};
+
+// rows from packed words, pass 3: wfa_altext_write_kernel's rounds, groups and stores.  A group inside one op is a funnel shift over
+// two words per sequence and one v_perm_b32 from codes to letters; a flagged query reads the four bases that END at len - 1 - p.
+__global__ __launch_bounds__(256) void wfa_altext_pk_write_kernel(const AltPkParams A) {
+    alt_write_pass(A, [&](uint64_t i) {
+        AltWindow w;
+        (void)alt_pk_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+        return AltPkSeq{A.words + A.q_woff[i], A.words + A.t_woff[i], A.q_len[i], A.t_len[i], (uint32_t)w.q_at, (uint32_t)w.t_at,
+                        A.q_rc != nullptr && A.q_rc[i] != 0};
+    });
 }
 
 namespace {
@@ -436,13 +513,33 @@ int altext_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, ui
         [&](uint32_t grid) { hipLaunchKernelGGL(wfa_altext_write_kernel, dim3(grid), dim3(256), 0, st, A); });
 }
 
-int altext_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob, uint64_t blob_bytes,
-                        const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n_pairs, int only_aligned,
-                        void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *row_needed,
-                        hipStream_t st) {
-    // (nothing in these checks dereferences the context)
-    if (!ctx || (n_pairs && (!d_rec || !d_row_off || !d_q_off || !d_q_len || !d_t_off || !d_t_len))) return WFAHIP_ERR_BAD_ARG;
-    if ((!d_ops && ops_cap) || (!d_seq_blob && blob_bytes) || ((!d_q_row || !d_a_row || !d_t_row) && row_cap)) return WFAHIP_ERR_BAD_ARG;
+// the rows from packed words: the same three passes over AltPkParams
+int altext_pk_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed, uint64_t n_words,
+                          const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n,
+                          int only_aligned, void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *total,
+                          hipStream_t st) {
+    AltPkParams A{};
+    const int   rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, d_row_off, &A.C);
+    if (rc) return rc;
+    A.words = static_cast<const uint32_t *>(d_packed), A.n_words = n_words;
+    A.q_woff = static_cast<const uint64_t *>(d_q_woff), A.t_woff = static_cast<const uint64_t *>(d_t_woff);
+    A.q_len = static_cast<const uint32_t *>(d_q_len), A.t_len = static_cast<const uint32_t *>(d_t_len);
+    A.q_rc  = static_cast<const uint8_t *>(d_q_rc);
+    A.q_row = static_cast<uint8_t *>(d_q_row), A.a_row = static_cast<uint8_t *>(d_a_row), A.t_row = static_cast<uint8_t *>(d_t_row);
+    A.dwords = ((reinterpret_cast<uintptr_t>(d_q_row) | reinterpret_cast<uintptr_t>(d_a_row) | reinterpret_cast<uintptr_t>(d_t_row)) & 3u) == 0u;
+    return cig_passes(
+        ctx, A.C, row_cap, total, st, "alignment text packed",
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_altext_pk_len_kernel, dim3(grid), dim3(256), 0, st, A); },
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_altext_pk_write_kernel, dim3(grid), dim3(256), 0, st, A); });
+}
+
+// what the two row entries share: seq_args_ok is the verdict on the pointers of the sequences (nothing before impl dereferences the
+// context), impl(st, &total) runs the three passes
+template <class Impl>
+int altext_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, bool seq_args_ok, uint64_t n_pairs, void *d_q_row,
+                 void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *row_needed, hipStream_t st, Impl &&impl) {
+    if (!ctx || (n_pairs && (!d_rec || !d_row_off)) || !seq_args_ok) return WFAHIP_ERR_BAD_ARG;
+    if ((!d_ops && ops_cap) || ((!d_q_row || !d_a_row || !d_t_row) && row_cap)) return WFAHIP_ERR_BAD_ARG;
     if (n_pairs > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit: no entry leaves records of more pairs)
     if (row_needed) *row_needed = 0;
     if (n_pairs == 0 && !d_row_off) return WFAHIP_OK;
@@ -454,10 +551,33 @@ int altext_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, u
         return WFAHIP_OK;
     }
     uint64_t  total = 0;
-    const int rc    = altext_device_impl(ctx, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs,
-                                         only_aligned, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, &total, st);
+    const int rc    = impl(st, &total);
     if (row_needed && (rc == WFAHIP_OK || rc == WFAHIP_ERR_OOM)) *row_needed = total;
     return rc;
+}
+
+int altext_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob, uint64_t blob_bytes,
+                        const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n_pairs, int only_aligned,
+                        void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off, uint64_t *row_needed,
+                        hipStream_t st) {
+    const bool seq_ok = !(n_pairs && (!d_q_off || !d_q_len || !d_t_off || !d_t_len)) && !(!d_seq_blob && blob_bytes);
+    return altext_entry(ctx, d_rec, d_ops, ops_cap, seq_ok, n_pairs, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, row_needed, st,
+                        [&](hipStream_t s, uint64_t *total) {
+                            return altext_device_impl(ctx, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len,
+                                                      n_pairs, only_aligned, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, total, s);
+                        });
+}
+
+int altext_pk_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed, uint64_t n_words,
+                           const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc,
+                           uint64_t n_pairs, int only_aligned, void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap, void *d_row_off,
+                           uint64_t *row_needed, hipStream_t st) {
+    const bool seq_ok = !(n_pairs && (!d_q_woff || !d_q_len || !d_t_woff || !d_t_len)) && !(!d_packed && n_words);
+    return altext_entry(ctx, d_rec, d_ops, ops_cap, seq_ok, n_pairs, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, row_needed, st,
+                        [&](hipStream_t s, uint64_t *total) {
+                            return altext_pk_device_impl(ctx, d_rec, d_ops, ops_cap, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len,
+                                                         d_q_rc, n_pairs, only_aligned, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, total, s);
+                        });
 }
 
 int cigar_text_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n_pairs, int only_aligned,
@@ -586,14 +706,19 @@ int cigar_text_host(const wfahip_results *r, int only_aligned, int n_threads, wf
 
 void align_texts_zero(wfahip_align_texts *t) { std::memset(t, 0, sizeof *t); }
 
-int alignment_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
-                        const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads, wfahip_align_texts *out) {
+// the host row renderers' plan.  seq_args_ok is the verdict on the pointers of the sequences (with r->n > 0 the four arrays, and the
+// blob or the words); window(i, trim, &w) gives the windows of pair i -- asked only for an OK pair with an op that renders --, false
+// where they fail; rows_write(i, ops, count, w, q_row, a_row, t_row) renders the pair.  columns_only: the windows of a pair whose
+// ops have no column are not asked for (the packed entry; the byte entry checks every pair with an op in its range).
+template <class Window, class RowsWrite>
+int alignment_text_host_impl(const wfahip_results *r, bool seq_args_ok, bool columns_only, int only_aligned, int n_threads,
+                             wfahip_align_texts *out, Window &&window, RowsWrite &&rows_write) {
     if (out) align_texts_zero(out);
     if (!r || !out) return WFAHIP_ERR_BAD_ARG;
     const uint64_t n = r->n;
-    if (n && (!r->status || !r->ops_off || !r->ops_len || !q_off || !q_len || !t_off || !t_len)) return WFAHIP_ERR_BAD_ARG;
+    if (n && (!r->status || !r->ops_off || !r->ops_len)) return WFAHIP_ERR_BAD_ARG;
     if (n && only_aligned && (!r->qbegin || !r->qend || !r->tbegin || !r->tend)) return WFAHIP_ERR_BAD_ARG;
-    if ((!r->ops && r->n_ops) || (!seq_blob && blob_bytes)) return WFAHIP_ERR_BAD_ARG;
+    if ((!r->ops && r->n_ops) || !seq_args_ok) return WFAHIP_ERR_BAD_ARG;
     char      *rows[3] = {nullptr, nullptr, nullptr};
     uint64_t  *off = nullptr, total = 0;
     const bool trim = only_aligned != 0;
@@ -603,10 +728,8 @@ int alignment_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64
         *cols = 0;
         if (*count == 0u) return true;
         const AltSums s = alt_sums(*ops, *count);
-        if (!alt_window(trim, blob_bytes, q_off[i], q_len[i], t_off[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
-                        trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w) ||
-            !alt_fits(s, *w))
-            return false;
+        if (columns_only && s.cols == 0) return true;
+        if (!window(i, trim, w) || !alt_fits(s, *w)) return false;
         *cols = s.cols;
         return true;
     };
@@ -630,8 +753,8 @@ int alignment_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64
             AltWindow       w;
             uint64_t        cols;
             (void)pair(i, &ops, &count, &w, &cols);
-            alt_rows_write(ops, count, seq_blob + w.q_at, seq_blob + w.t_at, reinterpret_cast<uint8_t *>(rows[0]) + at,
-                           reinterpret_cast<uint8_t *>(rows[1]) + at, reinterpret_cast<uint8_t *>(rows[2]) + at);
+            rows_write(i, ops, count, w, reinterpret_cast<uint8_t *>(rows[0]) + at, reinterpret_cast<uint8_t *>(rows[1]) + at,
+                       reinterpret_cast<uint8_t *>(rows[2]) + at);
         });
     if (rc) return rc;
     out->n       = n;
@@ -639,6 +762,36 @@ int alignment_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64
     out->q_row = rows[0], out->a_row = rows[1], out->t_row = rows[2];
     out->off = off;
     return WFAHIP_OK;
+}
+
+int alignment_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                        const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads, wfahip_align_texts *out) {
+    const bool seq_ok = r && !(r->n && (!q_off || !q_len || !t_off || !t_len)) && !(!seq_blob && blob_bytes);
+    return alignment_text_host_impl(
+        r, seq_ok, false, only_aligned, n_threads, out,
+        [&](uint64_t i, bool trim, AltWindow *w) {
+            return alt_window(trim, blob_bytes, q_off[i], q_len[i], t_off[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                              trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w);
+        },
+        [&](uint64_t, const uint64_t *ops, uint32_t count, const AltWindow &w, uint8_t *q_row, uint8_t *a_row, uint8_t *t_row) {
+            alt_rows_write(ops, count, seq_blob + w.q_at, seq_blob + w.t_at, q_row, a_row, t_row);
+        });
+}
+
+int alignment_text_packed_host(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                               const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc, int only_aligned,
+                               int n_threads, wfahip_align_texts *out) {
+    const bool seq_ok = r && !(r->n && (!q_woff || !q_len || !t_woff || !t_len)) && !(!packed && n_words);
+    return alignment_text_host_impl(
+        r, seq_ok, true, only_aligned, n_threads, out,
+        [&](uint64_t i, bool trim, AltWindow *w) {
+            return alt_pk_window(trim, n_words, q_woff[i], q_len[i], t_woff[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                                 trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w);
+        },
+        [&](uint64_t i, const uint64_t *ops, uint32_t count, const AltWindow &w, uint8_t *q_row, uint8_t *a_row, uint8_t *t_row) {
+            alt_pk_rows_write(ops, count, packed + q_woff[i], q_len[i], q_rc != nullptr && q_rc[i] != 0, (uint32_t)w.q_at, packed + t_woff[i],
+                              t_len[i], (uint32_t)w.t_at, q_row, a_row, t_row);
+        });
 }
 
 // wfahip_align_batch_text: the plain path of wfahip_align_batch with the text kernels in place of the result assembly
@@ -789,6 +942,22 @@ extern "C" int wfahip_alignment_text(const wfahip_results *r, const uint8_t *seq
                                      const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads,
                                      wfahip_align_texts *out) {
     WFAHIP_GUARD(alignment_text_host(r, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, only_aligned, n_threads, out))
+}
+
+extern "C" int wfahip_alignment_text_packed_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                                   const void *d_packed, uint64_t n_words, const void *d_q_woff, const void *d_q_len,
+                                                   const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n_pairs,
+                                                   int only_aligned, void *d_q_row, void *d_a_row, void *d_t_row, uint64_t row_cap,
+                                                   void *d_row_off, uint64_t *row_needed, void *stream) {
+    WFAHIP_GUARD(altext_pk_device_entry(ctx, d_rec, d_ops, ops_cap, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc, n_pairs,
+                                        only_aligned, d_q_row, d_a_row, d_t_row, row_cap, d_row_off, row_needed,
+                                        static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_alignment_text_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                                            const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc,
+                                            int only_aligned, int n_threads, wfahip_align_texts *out) {
+    WFAHIP_GUARD(alignment_text_packed_host(r, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, only_aligned, n_threads, out))
 }
 
 extern "C" void wfahip_align_texts_free(wfahip_align_texts *t) {
