@@ -62,7 +62,8 @@ enum {
     WFAHIP_PAIR_EMPTY     = 1, /* ErrEmptySeq,   wfa.go:204-206 */
     WFAHIP_PAIR_TOO_LONG  = 2, /* ErrSeqTooLong, wfa.go:207-209 */
     WFAHIP_PAIR_NO_MEMORY = 4, /* wavefront arena could not be grown enough for this pair */
-    WFAHIP_PAIR_OVER_MAX  = 8  /* the entries that take a max_score (score entries, wfahip_align_batch_bounded): the pair's score exceeds it */
+    WFAHIP_PAIR_OVER_MAX  = 8, /* the entries that take a max_score (score entries, wfahip_align_batch_bounded): the pair's score exceeds it */
+    WFAHIP_PAIR_CHECK_FAILED = 16 /* wfahip_check_alignments*'s pass array only: an OK pair with a flag of the caller's mask */
 };
 
 /* wfa.go:190 MaxSeqLen */
@@ -569,7 +570,8 @@ int  wfahip_align_batch_text(wfahip_ctx *ctx, const wfahip_params *p, const uint
  * window's length.  The library's results meet them with equality, with one exception that is the reference's own: under
  * wf-adaptive its ops now and then consume one base more than both sequences hold (pair 61 309 of the 1 kbp benchmark batch ends
  * ..5M1X3I over a query of 1 000 bases; the CPU oracle returns the same ops).  Untrimmed, a batch with such a pair is refused;
- * trimmed it renders, the windows being the record's.  A caller sets the pair aside (scripts/alignment_text_bench.py does).
+ * trimmed it renders, the windows being the record's.  A caller sets the pair aside: wfahip_check_alignments_device under the mask
+ * WFAHIP_CHK_NO_ROWS names it (scripts/alignment_text_bench.py does that).
  *
  * wfahip_alignment_text_device: d_rec / d_ops as wfahip_align_batch_device (or _bounded_device) left them, or any records and ops
  * of that layout; the blob and the four arrays (offsets u64, lengths u32) are the ones that call was given.  Only bytes inside the
@@ -658,6 +660,100 @@ int  wfahip_alignment_text_packed_device(wfahip_ctx *ctx, const void *d_rec, con
 int  wfahip_alignment_text_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
                                   const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                                   const uint8_t *q_rc /* NULL = none */, int only_aligned, int n_threads, wfahip_align_texts *out);
+
+/* The check: is each alignment consistent with its sequences, what does it cost, and which pairs are not?  One pass over records,
+ * ops and sequences where they lie; per pair WFAHIP_CHK_WORDS = 8 u32 words -- FLAGS, COST, Q_USED, T_USED, N_BAD, FIRST_BAD, 0, 0 --
+ * and, if asked for, a status for the stages behind.  The flags state what IS, not what is wrong: the reference's own results raise
+ * NO_M, Q_OVER / T_OVER, COST_UNDER and M_DIFFERS now and then (short noisy pairs under an aggressive wf-adaptive; KERNELS.md 4u), and
+ * this library returns what the reference returns.  A caller picks the flags it minds with flag_mask.
+ * The rule (wfa_amd/csrc/wfa_check.hpp, one source for the kernels and the host entries), in this order:
+ *  1. status not WFAHIP_PAIR_OK: all eight words 0; nothing else of the pair is read -- its record may hold stale words, its offsets
+ *     are never looked at;
+ *  2. OPS_RANGE: OPS_LEN > ops_cap or OPS_OFF > ops_cap - OPS_LEN.  FLAGS = OPS_RANGE | NO_ROWS | NO_ROWS_TRIMMED, the other words 0,
+ *     no op is read;
+ *  3. over all ops: LETTER, an op letter outside M X I D H; ZERO, an op with count 0; UNMERGED, two neighbouring ops of one letter;
+ *     NO_M, no 'M' op (an empty op list has none);
+ *  4. Q_USED / T_USED: the query / target bases the ops consume (M X: both, I: target, D H: query, any other letter: none).  COST:
+ *     x * count for X, o + e * count for I, D and H, 0 for everything else.  Each word is min(true value, 0xFFFFFFFF); the true values
+ *     are carried wide enough that a count of 0xFFFFFFFF under a penalty of 0xFFFFFFFF does not wrap;
+ *  5. SEQ_RANGE: a sequence with off > blob_bytes or len > blob_bytes - off (words: woff > n_words or wfahip_packed_words(len) >
+ *     n_words - woff).  No sequence byte of the pair is read; N_BAD = 0, FIRST_BAD = 0xFFFFFFFF;
+ *  6. Q_OVER / Q_UNDER / T_OVER / T_UNDER: the bases consumed against the sequence's length;
+ *  7. only the M and X columns whose query index is < q_len and whose target index is < t_len are compared, byte with byte as the
+ *     reference compares them (packed input: code with code; base p of a flagged query is code ^ 2 of forward base len - 1 - p).
+ *     M_DIFFERS: an M column whose two bytes differ.  X_EQUAL: an X column whose bytes are equal.  N_BAD counts such columns
+ *     (saturating); FIRST_BAD is min(index of the first among all columns of the untrimmed rows, 0xFFFFFFFE), 0xFFFFFFFF without one;
+ *  8. NO_ROWS / NO_ROWS_TRIMMED: the checks of wfahip_alignment_text_device (packed: of wfahip_alignment_text_packed_device) with
+ *     only_aligned = 0 / 1 fail for this pair -- decided by the functions those entries call;
+ *  9. only when p->global_alignment != 0: COST_OVER, the true cost > SCORE; COST_UNDER, the true cost < SCORE (the reference's merge of
+ *     two separately opened gaps into one op);
+ * 10. STAT_ALIGN_LEN / STAT_MATCHES / STAT_GAPS / STAT_GAP_REGIONS: the record's field differs from process() recomputed over the ops
+ *     (wfa_cigar.go:171-211): u32 wrapping sums from the first M op to the last -- without an M op over op 0 alone, as the Go loop
+ *     behaves --, H counted in the length and not in the gaps. */
+#define WFAHIP_CHK_WORDS 8
+enum { WFAHIP_CHK_W_FLAGS = 0, WFAHIP_CHK_W_COST, WFAHIP_CHK_W_Q_USED, WFAHIP_CHK_W_T_USED, WFAHIP_CHK_W_N_BAD, WFAHIP_CHK_W_FIRST_BAD };
+#define WFAHIP_CHK_OPS_RANGE        (1u << 0)
+#define WFAHIP_CHK_LETTER           (1u << 1)
+#define WFAHIP_CHK_ZERO             (1u << 2)
+#define WFAHIP_CHK_UNMERGED         (1u << 3)
+#define WFAHIP_CHK_NO_M             (1u << 4)
+#define WFAHIP_CHK_SEQ_RANGE        (1u << 5)
+#define WFAHIP_CHK_Q_OVER           (1u << 6)
+#define WFAHIP_CHK_Q_UNDER          (1u << 7)
+#define WFAHIP_CHK_T_OVER           (1u << 8)
+#define WFAHIP_CHK_T_UNDER          (1u << 9)
+#define WFAHIP_CHK_M_DIFFERS        (1u << 10)
+#define WFAHIP_CHK_X_EQUAL          (1u << 11)
+#define WFAHIP_CHK_NO_ROWS          (1u << 12)
+#define WFAHIP_CHK_NO_ROWS_TRIMMED  (1u << 13)
+#define WFAHIP_CHK_COST_OVER        (1u << 14)
+#define WFAHIP_CHK_COST_UNDER       (1u << 15)
+#define WFAHIP_CHK_STAT_ALIGN_LEN   (1u << 16)
+#define WFAHIP_CHK_STAT_MATCHES     (1u << 17)
+#define WFAHIP_CHK_STAT_GAPS        (1u << 18)
+#define WFAHIP_CHK_STAT_GAP_REGIONS (1u << 19)
+#define WFAHIP_CHK_ALL              ((1u << 20) - 1u)
+
+/* wfahip_check_alignments_device: records, ops, blob and the four arrays as wfahip_alignment_text_device takes them, all device
+ * addresses on the context's GPU that stay the caller's; no input is written.  d_chk receives 8 n_pairs u32 words (two 16-byte stores
+ * a pair where d_chk is 16-byte aligned), d_pass -- if non-NULL -- n_pairs int32: the record's status when that is not OK, else
+ * WFAHIP_PAIR_OK when FLAGS & flag_mask == 0, else WFAHIP_PAIR_CHECK_FAILED.  wfahip_select_pairs_device takes d_pass as its d_status
+ * unchanged; copied over the status column of a copy of the records it makes the text entries render the remaining pairs.  Nothing
+ * beyond those words and statuses is written.  *n_flagged (if non-NULL) receives the number of OK pairs with FLAGS & flag_mask != 0:
+ * one 64-byte fetch of a counter in the context, the only thing that crosses PCIe.  A bad pair is never a call error here: it is a
+ * flag.  Only bytes (words) inside the sequences are read: d_seq_blob and d_packed need no readable memory behind their
+ * ends.  WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx, p or d_chk; with n_pairs > 0 a null
+ * d_rec, offset or length array; a null d_ops with ops_cap > 0; a null blob (words) with a non-zero size; n_pairs beyond 0xFFFFFFF0.
+ * Then the params are checked as wfahip_align_batch checks them.  n_pairs == 0 returns WFAHIP_OK with *n_flagged = 0 and touches
+ * nothing.  stream = hipStream_t (NULL = the context's own).  Synchronous.  wfahip_last_timing is not touched.
+ * One kernel (wfa_cigar.hip: wfa_check_kernel, wfa_check_pk_kernel): a wave per pair in rounds of 64 ops, the flags from ballots and a
+ * neighbour compare, the display-row kernels' prefix sums and column sweep with a compare where they store; no scan, nothing
+ * variable-length is written; one atomic a wave feeds the counter (KERNELS.md 4u).  WFAHIP_DEBUG_TIMING=1 prints the kernel's time. */
+int  wfahip_check_alignments_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                    const void *d_seq_blob, uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
+                                    const void *d_t_off, const void *d_t_len, uint64_t n_pairs, uint32_t flag_mask,
+                                    void *d_chk /* u32[8 n_pairs] */, void *d_pass /* int32[n_pairs], may be NULL */,
+                                    uint64_t *n_flagged /* may be NULL */, void *stream);
+/* The same over 2-bit packed words, both strands: inputs as wfahip_alignment_text_packed_device takes them (d_q_rc: u8 per pair, NULL
+ * = none set). */
+int  wfahip_check_alignments_packed_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                           const void *d_packed, uint64_t n_words, const void *d_q_woff, const void *d_q_len,
+                                           const void *d_t_woff, const void *d_t_len, const void *d_q_rc /* NULL = none */,
+                                           uint64_t n_pairs, uint32_t flag_mask, void *d_chk, void *d_pass, uint64_t *n_flagged,
+                                           void *stream);
+/* Host only, no device, no context: the same words, statuses and count for a wfahip_results in host memory (n_ops as ops_cap; the
+ * record's fields are r's arrays) and the blob (words) and arrays it was aligned from, n_threads host threads over contiguous ranges
+ * of pairs, the same header functions as the kernels.  chk is the caller's, 8 r->n words; pass (r->n statuses) and n_flagged may be
+ * NULL.  WFAHIP_ERR_BAD_ARG: a null r, p or chk; with r->n > 0 a null field array of r, offset or length array; a null ops with
+ * n_ops > 0; a null blob (words) with a non-zero size; r->n beyond 0xFFFFFFF0.  Then the params as wfahip_align_batch checks them. */
+int  wfahip_check_alignments(const wfahip_results *r, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
+                             const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
+                             uint32_t flag_mask, int n_threads, uint32_t *chk /* 8 r->n */, int32_t *pass /* may be NULL */,
+                             uint64_t *n_flagged /* may be NULL */);
+int  wfahip_check_alignments_packed(const wfahip_results *r, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                    const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                    const uint8_t *q_rc /* NULL = none */, uint32_t flag_mask, int n_threads, uint32_t *chk,
+                                    int32_t *pass, uint64_t *n_flagged);
 
 /* One pair at a time behind the batch: a caller that loops over pairs like the reference's CLI
  * (wfa-go/wfa-go.go:166-178: one Align per ">"/"<" record) submits each pair -- the bytes are copied, the call returns

@@ -28,27 +28,21 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from cigar_text_bench import StderrCapture, clock, med  # noqa: E402
 
 
-def set_aside(torch, L, rec, ops, q_len, t_len):
-    """(records, indices): a copy of rec in which the OK pairs whose ops consume more query or target bases than the sequence holds
-    are marked not OK, and their indices.  Under wf-adaptive the reference itself returns such ops now and then (KERNELS.md 4q: one
-    pair of this batch), the entry refuses a batch that holds one -- the reference would index out of range -- and a caller
-    that wants the other pairs' rows sets the pair aside like this, on the device."""
-    letter, count = ops >> 32, ops & 0xFFFFFFFF
-    zero = torch.zeros(1, dtype=torch.int64, device=ops.device)
-    u32 = lambda col: rec[:, col].to(torch.int64) & 0xFFFFFFFF
-    ok = rec[:, L.REC_STATUS] == 0
-    first = torch.where(ok, u32(L.REC_OPS_OFF_LO) | (u32(L.REC_OPS_OFF_HI) << 32), zero)
-    last = first + torch.where(ok, u32(L.REC_OPS_LEN), zero)
-    over = torch.zeros_like(ok)
-    for letters, length in (("MXDH", q_len), ("MXI", t_len)):
-        mine = torch.zeros_like(letter, dtype=torch.bool)
-        for c in letters:
-            mine |= letter == ord(c)
-        run = torch.cat([zero, torch.cumsum(count * mine, 0)])
-        over |= ok & (run[last] - run[first] > (length.to(torch.int64) & 0xFFFFFFFF))
-    idx = torch.nonzero(over).flatten()
+def set_aside(al, L, rec, ops, seqs, q_off, q_len, t_off, t_len, q_rc=None):
+    """(records, indices): a copy of rec in which the OK pairs the untrimmed rows cannot be rendered for are marked not OK, and their
+    indices.  Under wf-adaptive the reference itself returns ops that consume a base more than a sequence holds now and then
+    (KERNELS.md 4q: one pair of this batch), the text entries refuse a batch that holds one -- the reference would index out of
+    range -- and a caller that wants the other pairs' rows sets the pair aside like this, on the device: the check under the mask
+    NO_ROWS names the pairs (wfahip_check_alignments_device; seqs the blob, or with q_rc the packed words), its pass array goes over
+    the records' status column."""
+    if q_rc is None:
+        _chk, passed, n_flagged = al.check_tensors(rec, ops, seqs, q_off, q_len, t_off, t_len, mask=L.CHK_NO_ROWS)
+    else:
+        _chk, passed, n_flagged = al.check_tensors_packed(rec, ops, seqs, q_off, q_len, t_off, t_len, q_rc=q_rc, mask=L.CHK_NO_ROWS)
+    idx = (passed == L.PAIR_CHECK_FAILED).nonzero().flatten()
+    assert idx.numel() == n_flagged
     rec = rec.clone()
-    rec[idx, L.REC_STATUS] = L.PAIR_NO_MEMORY  # (any status but OK: the pair's rows are empty)
+    rec[:, L.REC_STATUS] = passed  # (any status but OK: the pair's rows are empty)
     return rec, [int(i) for i in idx.cpu()]
 
 
@@ -159,7 +153,7 @@ def main():
     d = w.generate_pairs_device(al, 3, args.pairs, 1000, 0.05)
     with StderrCapture():
         rec, ops = al.align_tensors(*d)
-    rec, aside = set_aside(torch, L, rec, ops, d[2], d[4])
+    rec, aside = set_aside(al, L, rec, ops, *d)
     print(json.dumps({"part": "input", "pairs": args.pairs, "pairs_set_aside_because_their_ops_overrun_a_sequence": aside}), flush=True)
     ins = (rec, ops, *d)
     if "device" in parts:

@@ -84,7 +84,7 @@ def main():
     del stored
     with StderrCapture():
         rec, ops = al.align_tensors_packed(packed, q_woff, q_len, t_woff, t_len, q_rc=q_rc)
-    rec, aside = set_aside(torch, L, rec, ops, q_len, t_len)
+    rec, aside = set_aside(al, L, rec, ops, packed, q_woff, q_len, t_woff, t_len, q_rc=q_rc)
     print(json.dumps({"part": "input", "pairs": args.pairs, "flagged": int(q_rc.sum()), "packed_words": int(packed.numel()) - 4,
                       "blob_bytes": int(blob.numel()), "pairs_not_ok": int((rec[:, L.REC_STATUS] != 0).sum()),
                       "pairs_set_aside_because_their_ops_overrun_a_sequence": aside, **clock(al, L)}), flush=True)

@@ -12,6 +12,17 @@ LIB_PATH = os.path.join(_HERE, "lib", "libwfahip.so")
 OK, ERR_NO_DEVICE, ERR_BAD_ARG, ERR_OOM, ERR_HIP, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 PAIR_OK, PAIR_EMPTY, PAIR_TOO_LONG, PAIR_NO_MEMORY = 0, 1, 2, 4
 PAIR_OVER_MAX = 8  # the entries that take a max_score: the pair's score exceeds it
+PAIR_CHECK_FAILED = 16  # wfahip_check_alignments*'s pass array: an OK pair with a flag of the caller's mask
+# wfahip_check_alignments*: the words of a pair's verdict and the bits of its FLAGS word
+CHK_WORDS = 8
+CHK_W_FLAGS, CHK_W_COST, CHK_W_Q_USED, CHK_W_T_USED, CHK_W_N_BAD, CHK_W_FIRST_BAD = range(6)
+CHK_NAMES = ("OPS_RANGE", "LETTER", "ZERO", "UNMERGED", "NO_M", "SEQ_RANGE", "Q_OVER", "Q_UNDER", "T_OVER", "T_UNDER", "M_DIFFERS",
+             "X_EQUAL", "NO_ROWS", "NO_ROWS_TRIMMED", "COST_OVER", "COST_UNDER", "STAT_ALIGN_LEN", "STAT_MATCHES", "STAT_GAPS",
+             "STAT_GAP_REGIONS")
+(CHK_OPS_RANGE, CHK_LETTER, CHK_ZERO, CHK_UNMERGED, CHK_NO_M, CHK_SEQ_RANGE, CHK_Q_OVER, CHK_Q_UNDER, CHK_T_OVER, CHK_T_UNDER,
+ CHK_M_DIFFERS, CHK_X_EQUAL, CHK_NO_ROWS, CHK_NO_ROWS_TRIMMED, CHK_COST_OVER, CHK_COST_UNDER, CHK_STAT_ALIGN_LEN, CHK_STAT_MATCHES,
+ CHK_STAT_GAPS, CHK_STAT_GAP_REGIONS) = (1 << k for k in range(20))
+CHK_ALL = (1 << 20) - 1
 MAX_SEQ_LEN = (1 << 29) - 1
 REC_WORDS = 16
 (REC_STATUS, REC_SCORE, REC_TBEGIN, REC_TEND, REC_QBEGIN, REC_QEND, REC_ALIGN_LEN, REC_MATCHES, REC_GAPS,
@@ -36,6 +47,8 @@ EXPORTS = [
     "wfahip_pack_pairs_device", "wfahip_align_batch_packed_device",
     "wfahip_score_batch_packed_device", "wfahip_select_pairs_device",
     "wfahip_alignment_text_packed_device", "wfahip_alignment_text_packed",
+    "wfahip_check_alignments_device", "wfahip_check_alignments_packed_device", "wfahip_check_alignments",
+    "wfahip_check_alignments_packed",
 ]
 
 
@@ -159,6 +172,18 @@ def lib():
                                                           C.POINTER(u64), vp]
         L.wfahip_alignment_text_packed.restype = C.c_int
         L.wfahip_alignment_text_packed.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(AlignTexts)]
+        L.wfahip_check_alignments_device.restype = C.c_int
+        L.wfahip_check_alignments_device.argtypes = [vp, C.POINTER(Params), vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, u32, vp, vp,
+                                                     C.POINTER(u64), vp]
+        L.wfahip_check_alignments_packed_device.restype = C.c_int
+        L.wfahip_check_alignments_packed_device.argtypes = [vp, C.POINTER(Params), vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, u32, vp, vp,
+                                                            C.POINTER(u64), vp]
+        L.wfahip_check_alignments.restype = C.c_int
+        L.wfahip_check_alignments.argtypes = [C.POINTER(Results), C.POINTER(Params), vp, u64, vp, vp, vp, vp, u32, C.c_int, vp, vp,
+                                              C.POINTER(u64)]
+        L.wfahip_check_alignments_packed.restype = C.c_int
+        L.wfahip_check_alignments_packed.argtypes = [C.POINTER(Results), C.POINTER(Params), vp, u64, vp, vp, vp, vp, vp, u32, C.c_int, vp, vp,
+                                                     C.POINTER(u64)]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

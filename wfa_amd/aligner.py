@@ -762,6 +762,77 @@ class Aligner:
         L.check(rc, "wfahip_select_pairs_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return tuple(t[:cnt.value] if t is not None else None for t in outs)
 
+    # -- the check (include/wfa_hip.h: wfahip_check_alignments_device, wfahip_check_alignments_packed_device)
+    def check_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, mask: int = L.CHK_ALL, out=None, stream=None):
+        """The verdict on every pair of (rec, ops) -- align_tensors' output -- over the blob and the four tensors that call was
+        given, computed on the aligner's GPU under the aligner's penalties and options (include/wfa_hip.h:
+        wfahip_check_alignments_device): returns (chk int32 [n, 8], passed int32 [n], n_flagged int).  chk[i] holds FLAGS, COST,
+        Q_USED, T_USED, N_BAD, FIRST_BAD, 0, 0 of pair i, the C-ABI's uint32 bit for bit (the CHK_* bits of _lib name the flags);
+        passed[i] is the record's status when that is not PAIR_OK, else PAIR_OK when FLAGS & mask == 0, else PAIR_CHECK_FAILED -- it
+        goes into select_tensors as its status unchanged; n_flagged counts the OK pairs with FLAGS & mask != 0, the only number
+        that crosses PCIe.  A bad pair is a flag, never an error.  out=(chk, passed): contiguous tensors on that device of those
+        shapes.  No input is written.  stream and ValueErrors as score_tensors."""
+        return self._check_tensors(False, rec, ops, blob, "blob", q_off, q_len, t_off, t_len, None, mask, out, stream)
+
+    def check_tensors_packed(self, rec, ops, packed, q_woff, q_len, t_woff, t_len, q_rc=None, mask: int = L.CHK_ALL, out=None,
+                             stream=None):
+        """check_tensors over 2-bit words, both strands (include/wfa_hip.h: wfahip_check_alignments_packed_device): (rec, ops) are
+        align_tensors_packed's output, packed (int32, every word of the tensor counts) / q_woff / q_len / t_woff / t_len / q_rc the
+        tensors that call was given.  A flagged pair's columns compare the reverse complement of its query, the strand its record
+        and ops speak of.  Returns, out=, stream and ValueErrors as check_tensors."""
+        return self._check_tensors(True, rec, ops, packed, "packed", q_woff, q_len, t_woff, t_len, q_rc, mask, out, stream)
+
+    def _check_tensors(self, is_packed, rec, ops, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, mask, out, stream):
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        self._want_tensor(seqs_name, seqs, torch.int32 if is_packed else torch.uint8, dev)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(rec.shape[0])
+        if q_off.numel() != n or q_len.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors must hold one element per record")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        if not 0 <= int(mask) <= 0xFFFFFFFF:
+            raise ValueError("mask must fit 32 bits")
+        if out is not None:
+            try:
+                chk, passed = out
+            except (TypeError, ValueError):
+                raise ValueError("out must be (chk, passed), two tensors") from None
+            self._want_tensor("out chk", chk, torch.int32, dev, dim=2)
+            self._want_tensor("out passed", passed, torch.int32, dev)
+            if tuple(chk.shape) != (n, L.CHK_WORDS) or passed.numel() != n:
+                raise ValueError(f"out chk must be [{n}, {L.CHK_WORDS}] and out passed [{n}]")
+        stream = self._want_stream(stream, dev)
+        if out is None:
+            chk = torch.empty((n, L.CHK_WORDS), dtype=torch.int32, device=dev)
+            passed = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return chk, passed, 0
+        self._order_after_torch(stream, dev)  # (whatever made the inputs ran on torch's current stream)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        prm = self._params()
+        cnt = C.c_uint64(0)
+        lib = L.lib()
+        head = (self._ctx, C.byref(prm), rec.data_ptr(), ptr(ops), ops.numel(), ptr(seqs), seqs.numel(), q_off.data_ptr(), q_len.data_ptr(),
+                t_off.data_ptr(), t_len.data_ptr())
+        tail = (n, int(mask), chk.data_ptr(), passed.data_ptr(), C.byref(cnt), stream.cuda_stream)
+        if is_packed:
+            what = "wfahip_check_alignments_packed_device"
+            rc = lib.wfahip_check_alignments_packed_device(*head, ptr(q_rc), *tail)
+        else:
+            what = "wfahip_check_alignments_device"
+            rc = lib.wfahip_check_alignments_device(*head, *tail)
+        L.check(rc, what + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return chk, passed, int(cnt.value)
+
     def alignment_text_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, out=None, stream=None):
         """AlignmentResult.AlignmentText(q, t, only_aligned) of every pair of (rec, ops) -- align_tensors' output -- over the blob
         and the four tensors that call was given, rendered on the aligner's GPU (include/wfa_hip.h: wfahip_alignment_text_device):
@@ -1215,6 +1286,83 @@ def alignment_text_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_
                       lambda res, q_woff, q_len, t_woff, t_len, q_rc, txt: L.lib().wfahip_alignment_text_packed(
                           C.byref(res), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff), vp(t_len), vp(q_rc),
                           1 if only_aligned else 0, int(n_threads), C.byref(txt)), "wfahip_alignment_text_packed")
+
+
+def check_alignments(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len, penalties=None, options=None, adaptive=None,
+                     mask: int = L.CHK_ALL, n_threads: int = 8):
+    """The verdict on every pair of a BatchResult over the blob and arrays it was aligned from, computed by host threads
+    (include/wfa_hip.h: wfahip_check_alignments; no GPU, no Aligner): returns (chk np.uint32 [n, 8], passed np.int32 [n],
+    n_flagged int) -- FLAGS, COST, Q_USED, T_USED, N_BAD, FIRST_BAD, 0, 0 per pair; the record's status, PAIR_OK or
+    PAIR_CHECK_FAILED under mask; the number of OK pairs with a flag of the mask.  penalties / options / adaptive are the ones the
+    batch was aligned under (defaults: DefaultPenalties, DefaultOptions, none); the rule reads the penalties and GlobalAlignment.
+    ValueError for arrays of the wrong shape.  A bad pair is a flag, never an error."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    return _host_check(batch_result, blob, "blob", q_off, q_len, t_off, t_len, None, penalties, options, adaptive, mask, n_threads,
+                       lambda res, prm, q_off, q_len, t_off, t_len, q_rc, tail: L.lib().wfahip_check_alignments(
+                           C.byref(res), C.byref(prm), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len), *tail),
+                       "wfahip_check_alignments")
+
+
+def check_alignments_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_woff, t_len, q_rc=None, penalties=None, options=None,
+                            adaptive=None, mask: int = L.CHK_ALL, n_threads: int = 8):
+    """check_alignments over 2-bit words, both strands (include/wfa_hip.h: wfahip_check_alignments_packed; no GPU, no Aligner): the
+    verdicts on a BatchResult of align_arrays_packed_rc (or align_arrays_packed, q_rc=None) from the words, offsets, lengths and
+    flags it was aligned from.  Returns and errors as check_alignments."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    return _host_check(batch_result, packed, "packed", q_woff, q_len, t_woff, t_len, q_rc, penalties, options, adaptive, mask, n_threads,
+                       lambda res, prm, q_woff, q_len, t_woff, t_len, q_rc, tail: L.lib().wfahip_check_alignments_packed(
+                           C.byref(res), C.byref(prm), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff), vp(t_len), vp(q_rc),
+                           *tail), "wfahip_check_alignments_packed")
+
+
+def _host_check(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, penalties, options, adaptive, mask, n_threads, call, what):
+    """what the host checks share: the arrays made contiguous and checked, the wfahip_results view of the BatchResult, the params,
+    call(res, prm, q_off, q_len, t_off, t_len, q_rc, tail) -- the C entry, tail its last five arguments"""
+    i32 = ("status", "tbegin", "tend", "qbegin", "qend")
+    u32 = ("score", "align_len", "matches", "gaps", "gap_regions", "ops_len")
+    f = {k: np.ascontiguousarray(getattr(br, k), dtype=np.int32) for k in i32}
+    f.update({k: np.ascontiguousarray(getattr(br, k), dtype=np.uint32) for k in u32})
+    f["ops_off"] = np.ascontiguousarray(br.ops_off, dtype=np.uint64)
+    ops = np.ascontiguousarray(br.ops, dtype=np.uint64)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+    n = int(f["status"].size)
+    if f["status"].ndim != 1 or ops.ndim != 1 or seqs.ndim != 1:
+        raise ValueError(f"status, ops and {seqs_name} must be one-dimensional")
+    if any(a.shape != (n,) for a in list(f.values()) + [q_off, q_len, t_off, t_len]):
+        raise ValueError("the fields of the result and the offset and length arrays must hold one element per pair")
+    if q_rc is not None:
+        q_rc = np.ascontiguousarray(q_rc, dtype=np.uint8)
+        if q_rc.shape != (n,):
+            raise ValueError("q_rc must hold one flag per pair")
+    if int(n_threads) < 1:
+        raise ValueError("n_threads must be at least 1")
+    if not 0 <= int(mask) <= 0xFFFFFFFF:
+        raise ValueError("mask must fit 32 bits")
+    pen = penalties if penalties is not None else DefaultPenalties
+    opt = options if options is not None else DefaultOptions
+    prm = L.Params(pen.Mismatch, pen.GapOpen, pen.GapExt, 1 if opt.GlobalAlignment else 0, 0)
+    if adaptive is not None:
+        prm.adaptive = 1
+        prm.min_wf_len, prm.max_dist_diff, prm.cutoff_step = adaptive.MinWFLen, adaptive.MaxDistDiff, adaptive.CutoffStep
+    res = L.Results()
+    res.n, res.n_ops = n, int(ops.size)
+    for k in i32:
+        setattr(res, k, f[k].ctypes.data_as(C.POINTER(C.c_int32)))
+    for k in u32:
+        setattr(res, k, f[k].ctypes.data_as(C.POINTER(C.c_uint32)))
+    res.ops_off = f["ops_off"].ctypes.data_as(C.POINTER(C.c_uint64))
+    res.ops = ops.ctypes.data_as(C.POINTER(C.c_uint64))
+    chk = np.zeros((n, L.CHK_WORDS), dtype=np.uint32)
+    passed = np.zeros(n, dtype=np.int32)
+    cnt = C.c_uint64(0)
+    tail = (int(mask), int(n_threads), chk.ctypes.data_as(C.c_void_p), passed.ctypes.data_as(C.c_void_p), C.byref(cnt))
+    L.check(call(res, prm, q_off, q_len, t_off, t_len, q_rc, tail), what)
+    return chk, passed, int(cnt.value)
 
 
 def _host_rows(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, n_threads, call, what):

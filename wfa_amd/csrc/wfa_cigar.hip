@@ -22,11 +22,17 @@
 // rule is wfa_altext_pk.hpp's): the same passes again, wfa_altext_pk_len_kernel with the window check on words and
 // wfa_altext_pk_write_kernel, whose lanes take four letters out of two words by a funnel shift where the byte kernel loads four
 // bytes, a flagged query's from the far end of its words, reversed and complemented (KERNELS.md 4t).
+//
+// The check (wfahip_check_alignments_device, wfahip_check_alignments_packed_device and their host entries; the rule is
+// wfa_check.hpp's): ONE pass, wfa_check_kernel / wfa_check_pk_kernel, the write kernels' rounds and their column sweep (alt_sweep)
+// with a sink that compares an M or X column's two bases where the write kernels store them; eight words and a status a pair,
+// one counter to the host (KERNELS.md 4u).
 #include "wfa_ctx.hpp"
 #include "wfa_hostpack.hpp"
 #include "wfa_cigar.hpp"
 #include "wfa_altext.hpp"
 #include "wfa_altext_pk.hpp"
+#include "wfa_check.hpp"
 
 using namespace wfa;
 
@@ -72,6 +78,32 @@ struct AltPkParams {
     uint8_t        *q_row, *a_row, *t_row;
     uint32_t        dwords;
 };
+
+// the check (wfa_check.hpp): one struct for bytes and words -- seq is the blob or the words, seq_size blob_bytes or n_words, q_off /
+// t_off byte or word offsets, q_rc only the words'
+struct ChkParams {
+    const uint32_t *rec;
+    const uint64_t *ops;
+    uint64_t        ops_cap, n;
+    ChkRule         rule;
+    uint32_t        mask;
+    const void     *seq;
+    uint64_t        seq_size;
+    const uint64_t *q_off, *t_off;  // [n]
+    const uint32_t *q_len, *t_len;  // [n]
+    const uint8_t  *q_rc;           // [n] or null
+    uint32_t       *chk;            // [n][CHK_WORDS]
+    int32_t        *pass;           // [n] or null
+    uint32_t        vec;            // != 0: chk is 16-byte aligned, a pair's words go out as two stores
+    unsigned long long *ctl;        // [CIG_CTL_WORDS]: [CHK_FLAGGED] the OK pairs with a flag of the mask
+};
+enum { CHK_FLAGGED = 0 };
+static_assert(CHK_WORDS == WFAHIP_CHK_WORDS && CHK_ALL == WFAHIP_CHK_ALL && CHK_PAIR_FAILED == WFAHIP_PAIR_CHECK_FAILED &&
+                  CHK_OPS_RANGE == WFAHIP_CHK_OPS_RANGE && CHK_NO_M == WFAHIP_CHK_NO_M && CHK_SEQ_RANGE == WFAHIP_CHK_SEQ_RANGE &&
+                  CHK_T_UNDER == WFAHIP_CHK_T_UNDER && CHK_X_EQUAL == WFAHIP_CHK_X_EQUAL && CHK_NO_ROWS_TRIMMED == WFAHIP_CHK_NO_ROWS_TRIMMED &&
+                  CHK_COST_UNDER == WFAHIP_CHK_COST_UNDER && CHK_STAT_GAP_REGIONS == WFAHIP_CHK_STAT_GAP_REGIONS,
+              "wfa_check.hpp's flags are the public header's");
+constexpr uint32_t CHK_MAX_GRID = 2048;  // workgroups of four waves, each wave striding over the pairs
 
 }  // namespace
 
@@ -283,6 +315,46 @@ __global__ __launch_bounds__(256) void wfa_altext_pk_len_kernel(const AltPkParam
 // a group cut by the round's first or last column stores bytes, and the next round stores the rest of it.
 // Where the bases come from is the kernel's: seq(i) gives pair i's source once pass 1 has found it valid, with q4(p) / t4(p) the
 // four query / target bases from base p of the window on (base p + j in bits 8 j ..) and q1(p) / t1(p) one base.
+// The sweep of a round's columns [g0, gend) of at most R (the check kernels stop at the last column they compare): tab_* is the
+// wave's table of the round, sink(g, j0, j1, qv, av, tv) takes the columns g + j0 .. g + j1 - 1 of the group at g, column g + j in
+// bits 8 j .. of the three words.  ONE copy for the kernels that write rows and the ones that check them.
+template <class Seq, class Sink>
+__device__ __forceinline__ void alt_sweep(const unsigned long long *tab_col, const uint32_t *tab_q, const uint32_t *tab_t, const uint32_t *tab_kind,
+                                          uint32_t lane, uint64_t g0, uint64_t gend, unsigned long long R, const Seq &S, Sink &&sink) {
+    for (uint64_t g = (g0 & ~3ull) + 4u * lane; g < gend; g += 256u) {
+        const uint64_t lo = g > g0 ? g : g0, hi = g + 4u < gend ? g + 4u : gend;  // the group's columns of this round: lo < hi
+        const uint32_t j0 = (uint32_t)(lo - g), j1 = (uint32_t)(hi - g);
+        unsigned long long c = lo - g0;  // column in the round, < R
+        uint32_t           k = 0u;       // the last op whose first column is <= c: the one with a column there
+#pragma unroll
+        for (uint32_t step = 32u; step != 0u; step >>= 1)
+            if (tab_col[k + step] <= c) k += step;
+        unsigned long long cs = tab_col[k], ce = k < 63u ? tab_col[k + 1u] : R;
+        uint32_t           kd = tab_kind[k], qb = tab_q[k], tb = tab_t[k];
+        uint32_t           qv = 0u, av = 0u, tv = 0u;  // the group's bytes, column g + j in bits 8 j ..
+        if (j1 - j0 == 4u && c + 4u <= ce) {
+            const uint64_t d = c - cs;
+            qv = (kd & ALT_Q) ? S.q4((uint64_t)qb + d) : ALT_GAP * 0x01010101u;
+            tv = (kd & ALT_T) ? S.t4((uint64_t)tb + d) : ALT_GAP * 0x01010101u;
+            av = (kd >> 8) * 0x01010101u;
+        } else {
+            for (uint32_t j = j0; j < j1; j++, c++) {
+                if (c >= ce) {
+                    do {  // (ops without a column have cs == ce; c < R ends the walk at op 63 at the latest)
+                        k++;
+                        cs = ce, ce = k < 63u ? tab_col[k + 1u] : R;
+                    } while (c >= ce);
+                    kd = tab_kind[k], qb = tab_q[k], tb = tab_t[k];
+                }
+                const uint64_t d  = c - cs;
+                const uint32_t qx = (kd & ALT_Q) ? S.q1((uint64_t)qb + d) : ALT_GAP, tx = (kd & ALT_T) ? S.t1((uint64_t)tb + d) : ALT_GAP;
+                qv |= qx << (8u * j), av |= (kd >> 8) << (8u * j), tv |= tx << (8u * j);
+            }
+        }
+        sink(g, j0, j1, qv, av, tv);
+    }
+}
+
 template <class Params, class Seq>
 __device__ __forceinline__ void alt_write_pass(const Params &A, Seq &&seq) {
     __shared__ unsigned long long s_col[4][64];                      // first column of the op, in the round
@@ -320,48 +392,20 @@ __device__ __forceinline__ void alt_write_pass(const Params &A, Seq &&seq) {
         __builtin_amdgcn_wave_barrier();
         const unsigned long long R    = __shfl(ci, 63, 64);  // the round's columns
         const uint64_t           gend = g0 + R;
-        for (uint64_t g = (g0 & ~3ull) + 4u * lane; g < gend; g += 256u) {
-            const uint64_t lo = g > g0 ? g : g0, hi = g + 4u < gend ? g + 4u : gend;  // the group's columns of this round: lo < hi
-            const uint32_t j0 = (uint32_t)(lo - g), j1 = (uint32_t)(hi - g);
-            unsigned long long c = lo - g0;  // column in the round, < R
-            uint32_t           k = 0u;       // the last op whose first column is <= c: the one with a column there
-#pragma unroll
-            for (uint32_t step = 32u; step != 0u; step >>= 1)
-                if (s_col[wv][k + step] <= c) k += step;
-            unsigned long long cs = s_col[wv][k], ce = k < 63u ? s_col[wv][k + 1u] : R;
-            uint32_t           kd = s_kind[wv][k], qb = s_q[wv][k], tb = s_t[wv][k];
-            uint32_t           qv = 0u, av = 0u, tv = 0u;  // the group's bytes, column g + j in bits 8 j ..
-            if (j1 - j0 == 4u && c + 4u <= ce) {
-                const uint64_t d = c - cs;
-                qv = (kd & ALT_Q) ? S.q4((uint64_t)qb + d) : ALT_GAP * 0x01010101u;
-                tv = (kd & ALT_T) ? S.t4((uint64_t)tb + d) : ALT_GAP * 0x01010101u;
-                av = (kd >> 8) * 0x01010101u;
-            } else {
-                for (uint32_t j = j0; j < j1; j++, c++) {
-                    if (c >= ce) {
-                        do {  // (ops without a column have cs == ce; c < R ends the walk at op 63 at the latest)
-                            k++;
-                            cs = ce, ce = k < 63u ? s_col[wv][k + 1u] : R;
-                        } while (c >= ce);
-                        kd = s_kind[wv][k], qb = s_q[wv][k], tb = s_t[wv][k];
-                    }
-                    const uint64_t d  = c - cs;
-                    const uint32_t qx = (kd & ALT_Q) ? S.q1((uint64_t)qb + d) : ALT_GAP, tx = (kd & ALT_T) ? S.t1((uint64_t)tb + d) : ALT_GAP;
-                    qv |= qx << (8u * j), av |= (kd >> 8) << (8u * j), tv |= tx << (8u * j);
-                }
-            }
-            if (j1 - j0 == 4u && A.dwords != 0u) {
-                *reinterpret_cast<uint32_t *>(A.q_row + g) = qv;
-                *reinterpret_cast<uint32_t *>(A.a_row + g) = av;
-                *reinterpret_cast<uint32_t *>(A.t_row + g) = tv;
-            } else {
-                for (uint32_t j = j0; j < j1; j++) {
-                    A.q_row[g + j] = (uint8_t)(qv >> (8u * j));
-                    A.a_row[g + j] = (uint8_t)(av >> (8u * j));
-                    A.t_row[g + j] = (uint8_t)(tv >> (8u * j));
-                }
-            }
-        }
+        alt_sweep(s_col[wv], s_q[wv], s_t[wv], s_kind[wv], lane, g0, gend, R, S,
+                  [&](uint64_t g, uint32_t j0, uint32_t j1, uint32_t qv, uint32_t av, uint32_t tv) {
+                      if (j1 - j0 == 4u && A.dwords != 0u) {
+                          *reinterpret_cast<uint32_t *>(A.q_row + g) = qv;
+                          *reinterpret_cast<uint32_t *>(A.a_row + g) = av;
+                          *reinterpret_cast<uint32_t *>(A.t_row + g) = tv;
+                      } else {
+                          for (uint32_t j = j0; j < j1; j++) {
+                              A.q_row[g + j] = (uint8_t)(qv >> (8u * j));
+                              A.a_row[g + j] = (uint8_t)(av >> (8u * j));
+                              A.t_row[g + j] = (uint8_t)(tv >> (8u * j));
+                          }
+                      }
+                  });
         g0 = gend;
         qc += __shfl(qi, 63, 64), tc += __shfl(ti, 63, 64);
     }
@@ -407,6 +451,177 @@ __global__ __launch_bounds__(256) void wfa_altext_pk_write_kernel(const AltPkPar
     });
 }
 
+// ---- the check (wfa_check.hpp)
+
+// A wave per pair, the waves striding over the pairs so that ONE atomic a wave feeds the counter.  The ops are read twice: ballots
+// over cig_is_m give the first and the last 'M' op (the ranges step 8 and step 10 sum over), then rounds of 64 ops as in
+// alt_write_pass -- a lane an op, step 3's flags from the op and its left neighbour (the round before hands its last letter on),
+// the 64-bit wave prefix sums of columns, query and target bases, the table in LDS -- and alt_sweep over the round's columns up to
+// the last one that step 7 compares.  The table names only 'M' and 'X' ops as reading bases (a byte of 1 / 2), so a gap's columns
+// cost a lane no load and no base outside a sequence is touched; the sink compares where the row kernels store.  Nothing
+// variable-length is written: no scan.  Lane 0 ends in chk_finish, the same as the host's chk_pair.
+template <bool PACKED, class MakeSeq>
+__device__ __forceinline__ void chk_wave_pass(const ChkParams &K, MakeSeq &&make_seq) {
+    __shared__ unsigned long long s_col[4][64];
+    __shared__ uint32_t           s_q[4][64], s_t[4][64], s_kind[4][64];
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t       flagged = 0u;  // (lane 0's)
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + wv; i < K.n; i += (uint64_t)gridDim.x * 4) {
+        const uint32_t *r      = K.rec + i * REC_WORDS;
+        const uint32_t  status = r[REC_STATUS];
+        uint32_t        out[CHK_WORDS];
+        if (status != ST_OK) {
+            chk_unread(false, out);  // (a failed pair's record may hold stale words: none is read)
+        } else {
+            const uint32_t len = r[REC_OPS_LEN];
+            const uint64_t src = (uint64_t)r[REC_OPS_OFF_LO] | ((uint64_t)r[REC_OPS_OFF_HI] << 32);
+            if (chk_ops_range(src, len, K.ops_cap)) {
+                chk_unread(true, out);
+            } else {
+                const uint64_t *ops   = K.ops + (len != 0u ? src : 0ull);
+                const uint32_t  q_len = K.q_len[i], t_len = K.t_len[i];
+                const auto      window = [&](bool trim, AltWindow *w) {
+                    const int32_t qb = (int32_t)r[REC_QBEGIN], qe = (int32_t)r[REC_QEND], tb = (int32_t)r[REC_TBEGIN], te = (int32_t)r[REC_TEND];
+                    return PACKED ? alt_pk_window(trim, K.seq_size, K.q_off[i], q_len, K.t_off[i], t_len, qb, qe, tb, te, w)
+                                  : alt_window(trim, K.seq_size, K.q_off[i], q_len, K.t_off[i], t_len, qb, qe, tb, te, w);
+                };
+                // cig_range(ops, len, true, ..) from ballots
+                uint32_t m_first = 0u, m_end = 0u;
+                for (uint32_t b = 0; b < len; b += 64u) {
+                    const uint64_t m = __ballot(b + lane < len && cig_is_m(ops[b + lane]));
+                    if (m != 0ull) {
+                        if (m_end == 0u) m_first = b + (uint32_t)__builtin_ctzll(m);
+                        m_end = b + 64u - (uint32_t)__builtin_clzll(m);
+                    }
+                }
+                ChkTotals T = {};
+                T.len       = len;
+                T.m_count   = m_end != 0u ? m_end - m_first : 0u;
+                uint32_t s_first, s_count;
+                chk_stat_range(len, m_first, T.m_count, &s_first, &s_count);
+                AltWindow  w0;
+                const bool seq_ok = window(false, &w0);
+                const auto S      = make_seq(i, q_len, t_len);  // (nothing is read through it unless seq_ok)
+                uint32_t   fl = (T.m_count == 0u ? CHK_NO_M : 0u) | (seq_ok ? 0u : CHK_SEQ_RANGE);
+                uint64_t   cost = 0ull, n_bad = 0ull, first_bad = ~0ull;
+                uint64_t   g0 = 0ull, qc = 0ull, tc = 0ull;  // columns and bases of the rounds before
+                uint32_t   prev_last = 0u;                   // the last letter of the round before
+                for (uint32_t b = 0; b < len; b += 64u) {
+                    const uint32_t k      = b + lane;
+                    const bool     have   = k < len;
+                    const uint64_t op     = have ? ops[k] : 0ull;  // (letter 0: no column)
+                    const uint32_t letter = (uint32_t)(op >> 32);
+                    const uint32_t left   = __shfl_up(letter, 1, 64);
+                    if (have) {
+                        fl |= chk_op_flags(op, k != 0u, lane != 0u ? left : prev_last);
+                        cost = chk_sat_add(cost, chk_op_cost(op, K.rule));
+                        if (k - s_first < s_count) chk_stat_add(&T.stats, op);
+                        if (k - m_first < T.m_count) alt_add(&T.trimmed, op);
+                    }
+                    const uint32_t     kind = alt_kind(op), cnt = alt_cols(op);
+                    const uint64_t     myq = (kind & ALT_Q) ? cnt : 0u, myt = (kind & ALT_T) ? cnt : 0u;
+                    unsigned long long ci = cnt, qi = myq, ti = myt;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const unsigned long long c2 = __shfl_up(ci, o, 64), q2 = __shfl_up(qi, o, 64), t2 = __shfl_up(ti, o, 64);
+                        if (lane >= (uint32_t)o) ci += c2, qi += q2, ti += t2;
+                    }
+                    const uint64_t qs = qc + qi - myq, ts = tc + ti - myt;  // the op's first bases, true sums
+                    const bool     cmp = chk_compares(op);
+                    const uint32_t v   = seq_ok && cmp ? chk_valid(cnt, qs, ts, q_len, t_len) : 0u;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the round before has read its table)
+                    __builtin_amdgcn_wave_barrier();
+                    s_col[wv][lane]  = ci - cnt;
+                    s_q[wv][lane]    = (uint32_t)qs;  // (below q_len wherever a column of the op is compared)
+                    s_t[wv][lane]    = (uint32_t)ts;
+                    s_kind[wv][lane] = cmp ? (ALT_Q | ALT_T) | ((cig_is_m(op) ? 1u : 2u) << 8) : 0u;
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    const unsigned long long R  = __shfl(ci, 63, 64);  // the round's columns
+                    const uint64_t           vm = __ballot(v != 0u);
+                    if (vm != 0ull) {
+                        // the compared columns are a prefix of the 'M' / 'X' columns: they end in the last op that has one
+                        const unsigned long long E = __shfl(ci - cnt + v, 63 - __builtin_clzll(vm), 64);
+                        alt_sweep(s_col[wv], s_q[wv], s_t[wv], s_kind[wv], lane, g0, g0 + E, R, S,
+                                  [&](uint64_t g, uint32_t j0, uint32_t j1, uint32_t qv, uint32_t av, uint32_t tv) {
+                                      // bit 7 of byte j: the bytes of column g + j differ; an M column (byte 1) is bad if they do,
+                                      // an X column (byte 2) if they do not; the columns j0 .. j1 - 1 count
+                                      const uint32_t x   = qv ^ tv;
+                                      const uint32_t nz  = (x | ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu)) & 0x80808080u;
+                                      const uint32_t in  = (0xFFFFFFFFu >> (8u * (4u - j1))) & (0xFFFFFFFFu << (8u * j0));
+                                      const uint32_t bad = ((nz & (av << 7)) | (~nz & (av << 6))) & 0x80808080u & in;
+                                      if (bad != 0u) {  // (rare)
+                                          if ((bad & nz) != 0u) fl |= CHK_M_DIFFERS;
+                                          if ((bad & ~nz) != 0u) fl |= CHK_X_EQUAL;
+                                          n_bad += (uint32_t)__builtin_popcount(bad);
+                                          const uint64_t at = g + ((uint32_t)__builtin_ctz(bad) >> 3);
+                                          if (at < first_bad) first_bad = at;
+                                      }
+                                  });
+                    }
+                    g0 += R;
+                    qc += __shfl(qi, 63, 64), tc += __shfl(ti, 63, 64);
+                    prev_last = __shfl(letter, 63, 64);
+                }
+                // the lanes' parts into lane 0 (all lanes, in fact)
+                unsigned long long tq = T.trimmed.q, tt = T.trimmed.t, tcl = T.trimmed.cols, cs = cost, nb = n_bad, fb = first_bad;
+                if (__ballot(n_bad != 0ull) != 0ull) {  // (rare: a pair with a bad column)
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) {
+                        nb += __shfl_xor(nb, o, 64);
+                        const unsigned long long f2 = __shfl_xor(fb, o, 64);
+                        fb = f2 < fb ? f2 : fb;
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    fl |= __shfl_xor(fl, o, 64);
+                    cs = chk_sat_add(cs, __shfl_xor(cs, o, 64));
+                    tq += __shfl_xor(tq, o, 64), tt += __shfl_xor(tt, o, 64), tcl += __shfl_xor(tcl, o, 64);
+                    T.stats.align_len += __shfl_xor(T.stats.align_len, o, 64);
+                    T.stats.matches += __shfl_xor(T.stats.matches, o, 64);
+                    T.stats.gaps += __shfl_xor(T.stats.gaps, o, 64);
+                    T.stats.gap_regions += __shfl_xor(T.stats.gap_regions, o, 64);
+                }
+                if (lane == 0) {
+                    T.flags = fl, T.cost = cs, T.n_bad = nb, T.first_bad = fb;
+                    T.all     = AltSums{g0, qc, tc};
+                    T.trimmed = AltSums{tcl, tq, tt};
+                    const ChkRec rec = {r[REC_SCORE], r[REC_ALIGN_LEN], r[REC_MATCHES], r[REC_GAPS], r[REC_GAP_REGIONS],
+                                        (int32_t)r[REC_QBEGIN], (int32_t)r[REC_QEND], (int32_t)r[REC_TBEGIN], (int32_t)r[REC_TEND]};
+                    chk_finish<PACKED>(K.rule, rec, T, q_len, t_len, window, out);
+                }
+            }
+        }
+        if (lane == 0) {
+            uint32_t *dst = K.chk + i * CHK_WORDS;
+            if (K.vec != 0u) {
+                reinterpret_cast<uint4 *>(dst)[0] = make_uint4(out[0], out[1], out[2], out[3]);
+                reinterpret_cast<uint4 *>(dst)[1] = make_uint4(out[4], out[5], out[6], out[7]);
+            } else {
+                for (uint32_t k = 0; k < CHK_WORDS; k++) dst[k] = out[k];
+            }
+            if (K.pass != nullptr) K.pass[i] = chk_pass((int32_t)status, out[CHK_W_FLAGS], K.mask);
+            if (status == ST_OK && (out[CHK_W_FLAGS] & K.mask) != 0u) flagged++;
+        }
+    }
+    if (lane == 0 && flagged != 0u) atomicAdd(&K.ctl[CHK_FLAGGED], (unsigned long long)flagged);
+}
+
+__global__ __launch_bounds__(256) void wfa_check_kernel(const ChkParams K) {
+    chk_wave_pass<false>(K, [&](uint64_t i, uint32_t, uint32_t) {
+        const uint8_t *blob = static_cast<const uint8_t *>(K.seq);
+        return AltByteSeq{blob + K.q_off[i], blob + K.t_off[i]};
+    });
+}
+
+__global__ __launch_bounds__(256) void wfa_check_pk_kernel(const ChkParams K) {
+    chk_wave_pass<true>(K, [&](uint64_t i, uint32_t q_len, uint32_t t_len) {
+        const uint32_t *words = static_cast<const uint32_t *>(K.seq);
+        return AltPkSeq{words + K.q_off[i], words + K.t_off[i], q_len, t_len, 0u, 0u, K.q_rc != nullptr && K.q_rc[i] != 0};
+    });
+}
+
 namespace {
 
 // what every pass of a call shares, its scratch in ctx->cig included
@@ -428,6 +643,23 @@ int cig_params(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t o
     return WFAHIP_OK;
 }
 
+// WFAHIP_DEBUG_TIMING=1 (diagnostics, as in the host entry): the passes' hipEvent times on stderr
+struct Stamps {
+    hipEvent_t ev[5] = {};
+    bool       on    = std::getenv("WFAHIP_DEBUG_TIMING") != nullptr;
+    ~Stamps() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(int k, hipStream_t s) {
+        if (on && (ev[k] || hipEventCreate(&ev[k]) == hipSuccess)) (void)hipEventRecord(ev[k], s);
+    }
+    float ms(int a, int b) {
+        float v = 0;
+        return ev[a] && ev[b] && hipEventElapsedTime(&v, ev[a], ev[b]) == hipSuccess ? v : -1.f;
+    }
+};
+
 // the three passes on stream st: len(grid) launches the length kernel of a wave per pair, write(grid) the one that writes.
 // Returns WFAHIP_OK with *total set and the bytes written; WFAHIP_ERR_OOM (total > cap) with *total set, the offsets filled and no
 // byte written; WFAHIP_ERR_BAD_ARG when the length kernel raised CIG_BAD_RANGE, no byte written either.
@@ -437,23 +669,7 @@ int cig_passes(wfahip_ctx *ctx, const CigParams &C, uint64_t cap, uint64_t *tota
     const uint64_t n         = C.n;
     const uint32_t n_blocks  = (uint32_t)((n + CIG_PER_BLOCK - 1) / CIG_PER_BLOCK);
     const uint32_t pair_grid = (uint32_t)((n + 3) / 4);
-    // WFAHIP_DEBUG_TIMING=1 (diagnostics, as in the host entry): the passes' hipEvent times on stderr
-    struct Stamps {
-        hipEvent_t ev[5] = {};
-        bool       on    = false;
-        ~Stamps() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-        void mark(int k, hipStream_t s) {
-            if (on && (ev[k] || hipEventCreate(&ev[k]) == hipSuccess)) (void)hipEventRecord(ev[k], s);
-        }
-        float ms(int a, int b) {
-            float v = 0;
-            return ev[a] && ev[b] && hipEventElapsedTime(&v, ev[a], ev[b]) == hipSuccess ? v : -1.f;
-        }
-    } stamps;
-    stamps.on = std::getenv("WFAHIP_DEBUG_TIMING") != nullptr;
+    Stamps stamps;
     HIP_TRY(hipMemsetAsync(C.ctl, 0, CIG_CTL_WORDS * 8, st));
     stamps.mark(0, st);
     len(pair_grid);
@@ -794,6 +1010,111 @@ int alignment_text_packed_host(const wfahip_results *r, const uint32_t *packed, 
         });
 }
 
+// ---- the check (wfa_check.hpp): the device entries and the host entries
+
+// what the four entries refuse before anything is dereferenced but the params (seq: the blob or the words)
+int check_args(const void *ctx_or_results, const wfahip_params *p, const void *chk, uint64_t n, bool per_pair_ok, const void *ops,
+               uint64_t ops_cap, const void *seq, uint64_t seq_size) {
+    if (!ctx_or_results || !p || !chk) return WFAHIP_ERR_BAD_ARG;
+    if (n && !per_pair_ok) return WFAHIP_ERR_BAD_ARG;
+    if ((!ops && ops_cap) || (!seq && seq_size)) return WFAHIP_ERR_BAD_ARG;
+    if (n > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit: no entry leaves records of more pairs)
+    return check_params(p);
+}
+
+int check_device_entry(wfahip_ctx *ctx, const wfahip_params *p, bool packed, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                       const void *d_seq, uint64_t seq_size, const void *d_q_off, const void *d_q_len, const void *d_t_off,
+                       const void *d_t_len, const void *d_q_rc, uint64_t n, uint32_t flag_mask, void *d_chk, void *d_pass,
+                       uint64_t *n_flagged, hipStream_t st) {
+    int rc = check_args(ctx, p, d_chk, n, d_rec && d_q_off && d_q_len && d_t_off && d_t_len, d_ops, ops_cap, d_seq, seq_size);
+    if (rc) return rc;
+    if (n_flagged) *n_flagged = 0;
+    if (n == 0) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    if ((rc = ensure(ctx, ctx->cig, CIG_CTL_WORDS * 8))) return rc;
+    ChkParams K{};
+    K.rec = static_cast<const uint32_t *>(d_rec), K.ops = static_cast<const uint64_t *>(d_ops), K.ops_cap = ops_cap, K.n = n;
+    K.rule = ChkRule{p->mismatch, p->gap_open, p->gap_ext, p->global_alignment != 0};
+    K.mask = flag_mask;
+    K.seq = d_seq, K.seq_size = seq_size;
+    K.q_off = static_cast<const uint64_t *>(d_q_off), K.t_off = static_cast<const uint64_t *>(d_t_off);
+    K.q_len = static_cast<const uint32_t *>(d_q_len), K.t_len = static_cast<const uint32_t *>(d_t_len);
+    K.q_rc = static_cast<const uint8_t *>(d_q_rc);
+    K.chk = static_cast<uint32_t *>(d_chk), K.pass = static_cast<int32_t *>(d_pass);
+    K.vec = (reinterpret_cast<uintptr_t>(d_chk) & 15u) == 0u;
+    K.ctl = static_cast<unsigned long long *>(ctx->cig.p);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 3) / 4, CHK_MAX_GRID);
+    Stamps         stamps;
+    HIP_TRY(hipMemsetAsync(K.ctl, 0, CIG_CTL_WORDS * 8, st));
+    stamps.mark(0, st);
+    if (packed) hipLaunchKernelGGL(wfa_check_pk_kernel, dim3(grid), dim3(256), 0, st, K);
+    else hipLaunchKernelGGL(wfa_check_kernel, dim3(grid), dim3(256), 0, st, K);
+    HIP_TRY(hipGetLastError());
+    stamps.mark(1, st);
+    // (through the context's pinned block, as the text entries fetch their counters)
+    HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, K.ctl, CIG_CTL_WORDS * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t hc[CIG_CTL_WORDS];
+    std::memcpy(hc, ctx->hpin + HPIN_CTRL, sizeof hc);
+    if (n_flagged) *n_flagged = hc[CHK_FLAGGED];
+    if (stamps.on)
+        std::fprintf(stderr, "[wfahip] %s: %llu pairs, %llu flagged: kernel %.4f ms\n", packed ? "check alignments packed" : "check alignments",
+                     (unsigned long long)n, (unsigned long long)hc[CHK_FLAGGED], stamps.ms(0, 1));
+    return WFAHIP_OK;
+}
+
+int check_host_entry(const wfahip_results *r, const wfahip_params *p, bool packed, const void *seq, uint64_t seq_size, const uint64_t *q_off,
+                     const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, const uint8_t *q_rc, uint32_t flag_mask,
+                     int n_threads, uint32_t *chk, int32_t *pass, uint64_t *n_flagged) {
+    const uint64_t n  = r ? r->n : 0;
+    const bool     ok = r && r->status && r->score && r->tbegin && r->tend && r->qbegin && r->qend && r->align_len && r->matches && r->gaps &&
+                    r->gap_regions && r->ops_off && r->ops_len && q_off && q_len && t_off && t_len;
+    const int rc = check_args(r, p, chk, n, ok, r ? r->ops : nullptr, r ? r->n_ops : 0, seq, seq_size);
+    if (rc) return rc;
+    if (n_flagged) *n_flagged = 0;
+    if (n == 0) return WFAHIP_OK;
+    const ChkRule         R = {p->mismatch, p->gap_open, p->gap_ext, p->global_alignment != 0};
+    std::atomic<uint64_t> flagged{0};
+    parallel_ranges(0, n, (unsigned)std::max(1, n_threads), [&](uint64_t a, uint64_t b) {
+        uint64_t mine = 0;
+        for (uint64_t i = a; i < b; i++) {
+            uint32_t *out = chk + i * CHK_WORDS;
+            if (r->status[i] != WFAHIP_PAIR_OK) {
+                chk_unread(false, out);
+            } else if (chk_ops_range(r->ops_off[i], r->ops_len[i], r->n_ops)) {
+                chk_unread(true, out);
+            } else {
+                const ChkRec    rec = {r->score[i], r->align_len[i], r->matches[i], r->gaps[i], r->gap_regions[i],
+                                       r->qbegin[i], r->qend[i], r->tbegin[i], r->tend[i]};
+                const uint64_t *ops = r->ops_len[i] ? r->ops + r->ops_off[i] : nullptr;
+                if (packed) {
+                    const uint32_t *words = static_cast<const uint32_t *>(seq);
+                    chk_pair<true>(
+                        R, rec, ops, r->ops_len[i], q_len[i], t_len[i],
+                        [&](bool trim, AltWindow *w) {
+                            return alt_pk_window(trim, seq_size, q_off[i], q_len[i], t_off[i], t_len[i], rec.qbegin, rec.qend, rec.tbegin, rec.tend, w);
+                        },
+                        [&]() { return ChkPkSeq{words + q_off[i], words + t_off[i], q_len[i], t_len[i], q_rc != nullptr && q_rc[i] != 0}; }, out);
+                } else {
+                    const uint8_t *blob = static_cast<const uint8_t *>(seq);
+                    chk_pair<false>(
+                        R, rec, ops, r->ops_len[i], q_len[i], t_len[i],
+                        [&](bool trim, AltWindow *w) {
+                            return alt_window(trim, seq_size, q_off[i], q_len[i], t_off[i], t_len[i], rec.qbegin, rec.qend, rec.tbegin, rec.tend, w);
+                        },
+                        [&]() { return ChkByteSeq{blob + q_off[i], blob + t_off[i]}; }, out);
+                }
+            }
+            if (pass) pass[i] = chk_pass(r->status[i], out[CHK_W_FLAGS], flag_mask);
+            if (r->status[i] == WFAHIP_PAIR_OK && (out[CHK_W_FLAGS] & flag_mask) != 0u) mine++;
+        }
+        flagged += mine;
+    });
+    if (n_flagged) *n_flagged = flagged;
+    return WFAHIP_OK;
+}
+
 // wfahip_align_batch_text: the plain path of wfahip_align_batch with the text kernels in place of the result assembly
 int align_batch_text_impl(wfahip_ctx *ctx, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
                           const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, uint64_t n_pairs, int only_aligned,
@@ -970,4 +1291,35 @@ extern "C" int wfahip_align_batch_text(wfahip_ctx *ctx, const wfahip_params *p, 
                                        const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
                                        uint64_t n_pairs, int only_aligned, wfahip_results *out, wfahip_cigars *cig) {
     WFAHIP_GUARD(align_batch_text_impl(ctx, p, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, n_pairs, only_aligned, out, cig))
+}
+
+extern "C" int wfahip_check_alignments_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                              const void *d_seq_blob, uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
+                                              const void *d_t_off, const void *d_t_len, uint64_t n_pairs, uint32_t flag_mask, void *d_chk,
+                                              void *d_pass, uint64_t *n_flagged, void *stream) {
+    WFAHIP_GUARD(check_device_entry(ctx, p, false, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, nullptr,
+                                    n_pairs, flag_mask, d_chk, d_pass, n_flagged, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_check_alignments_packed_device(wfahip_ctx *ctx, const wfahip_params *p, const void *d_rec, const void *d_ops,
+                                                     uint64_t ops_cap, const void *d_packed, uint64_t n_words, const void *d_q_woff,
+                                                     const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc,
+                                                     uint64_t n_pairs, uint32_t flag_mask, void *d_chk, void *d_pass, uint64_t *n_flagged,
+                                                     void *stream) {
+    WFAHIP_GUARD(check_device_entry(ctx, p, true, d_rec, d_ops, ops_cap, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc,
+                                    n_pairs, flag_mask, d_chk, d_pass, n_flagged, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_check_alignments(const wfahip_results *r, const wfahip_params *p, const uint8_t *seq_blob, uint64_t blob_bytes,
+                                       const uint64_t *q_off, const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len,
+                                       uint32_t flag_mask, int n_threads, uint32_t *chk, int32_t *pass, uint64_t *n_flagged) {
+    WFAHIP_GUARD(check_host_entry(r, p, false, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, nullptr, flag_mask, n_threads, chk, pass,
+                                  n_flagged))
+}
+
+extern "C" int wfahip_check_alignments_packed(const wfahip_results *r, const wfahip_params *p, const uint32_t *packed, uint64_t n_words,
+                                              const uint64_t *q_woff, const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                                              const uint8_t *q_rc, uint32_t flag_mask, int n_threads, uint32_t *chk, int32_t *pass,
+                                              uint64_t *n_flagged) {
+    WFAHIP_GUARD(check_host_entry(r, p, true, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, flag_mask, n_threads, chk, pass, n_flagged))
 }
