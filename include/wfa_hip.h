@@ -661,6 +661,94 @@ int  wfahip_alignment_text_packed(const wfahip_results *r, const uint32_t *packe
                                   const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                                   const uint8_t *q_rc /* NULL = none */, int only_aligned, int n_threads, wfahip_align_texts *out);
 
+/* The difference string, rendered where the ops and the sequences are: minimap2's cs tag (short form) of every pair of a batch, the
+ * compact text product that names the bases.  The CIGAR text carries no base; the display rows carry every base three planes wide.
+ * This string writes match runs as counts and spells out only what differs, so that from the TARGET -- the reference sequence of the
+ * string -- and the string the aligned query is rebuilt exactly.  The rule (wfa_amd/csrc/wfa_diff.hpp, one source for the kernels and
+ * the host renderers), per op word letter << 32 | count, in op order:
+ *     M          ':' and the decimal of count (the CIGAR text's u32 decimal)       1 + digits bytes, reads no base
+ *     X          per column '*', lc(target byte), lc(query byte)                   3 count bytes
+ *     I          '-' and lc of the count target bytes (the target alone has them)  1 + count bytes
+ *     D, H       '+' and lc of the count query bytes (the query alone has them)    1 + count bytes
+ * An op of any other letter renders nothing and consumes nothing; an op of count 0 renders nothing.  Bases are consumed exactly as
+ * the display rows consume them.  lc(b) is b + 32 for 'A' <= b <= 'Z'; every other byte is copied verbatim.  Ops are taken at face
+ * value: an M op is never compared with the sequences (WFAHIP_CHK_M_DIFFERS of the check is how a caller sees the reference's rare
+ * mismatching M column), and neighbouring ops of one letter are not merged -- library results never have them, synthetic input
+ * renders one token per op.  Lengths are 64-bit sums: one X op may render 3 x 0xFFFFFFFF bytes.
+ * Which ops render is wfahip_alignment_text_device's, exactly: only_aligned == 0 renders all ops over the whole sequences;
+ * only_aligned != 0 the ops from the first 'M' op to the last over the windows the RECORD names, read as int32 -- query bytes
+ * [QBEGIN - 1, QEND) and target bytes [TBEGIN - 1, TEND).  A pair renders the empty string when its status is not WFAHIP_PAIR_OK,
+ * when OPS_LEN is 0, when trimmed it has no 'M' op, and when none of its ops renders a byte.  The checks are that entry's too, made
+ * by the same functions in the same order for every OK pair with an op that renders: the ops lie in [0, ops_cap); both sequences lie
+ * inside the blob; trimmed, 1 <= BEGIN, BEGIN - 1 <= END and END <= the sequence's length; the bases the ops consume, as 64-bit sums,
+ * fit the windows.  A batch with the wf-adaptive pair whose ops consume one base more than the sequences hold is refused untrimmed
+ * and renders trimmed, as there.
+ *
+ * wfahip_diff_text_device: d_rec / d_ops, the blob and the four arrays as wfahip_alignment_text_device takes them; only bytes inside
+ * the sequences are read, and an M op reads none: the blob needs NO readable bytes behind blob_bytes.  Every pointer is a device
+ * address on the context's GPU and stays the caller's.  Pair i's text is d_text[d_text_off[i] .. d_text_off[i + 1]), without
+ * terminators; d_text_off (u64[n_pairs + 1], 8-byte aligned) starts at 0 and ends at the total, which *text_needed (if non-NULL)
+ * receives.  No byte of d_text at or beyond the total is written; no input is written.  text_cap below the total: WFAHIP_ERR_OOM
+ * with d_text untouched and d_text_off filled -- a caller sizes with d_text = NULL, text_cap = 0 and calls again.  A failed check of
+ * the paragraph above: WFAHIP_ERR_BAD_ARG with d_text untouched, before the kernel that reads a sequence byte to write text is
+ * launched (d_text_off then holds nothing of use).  WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx; with
+ * n_pairs > 0 a null d_rec, d_text_off, d_q_off, d_q_len, d_t_off or d_t_len; a null d_ops with ops_cap > 0; a null d_seq_blob with
+ * blob_bytes > 0; a null d_text with text_cap > 0; n_pairs beyond 0xFFFFFFF0.  n_pairs == 0 returns WFAHIP_OK with *text_needed = 0
+ * and writes d_text_off[0] = 0 when d_text_off is non-null (the only case in which it touches the context or the device).  stream =
+ * hipStream_t (NULL = the context's own).  Synchronous.  wfahip_last_timing is not touched.
+ * Three passes (wfa_cigar.hip): wfa_diff_len_kernel, the display rows' length kernel with a fourth 64-bit sum, the bytes of the text;
+ * the CIGAR entry's scan, in place in d_text_off; wfa_diff_write_kernel, a wave per pair in rounds of 64 ops, wave prefix sums giving
+ * each op its first byte and its first bases -- a lane renders its own op where the text has at most 16 bytes, the whole wave sweeps
+ * each longer op in turn, four bytes to a lane in groups aligned in d_text (one 4-byte store a group where d_text is 4-byte aligned),
+ * so that no lane walks a count (KERNELS.md 4v).  Scratch lives in the context and is the CIGAR entry's; one fetch of 64 bytes of
+ * counters per call crosses PCIe.  WFAHIP_DEBUG_TIMING=1 prints the passes' times to stderr. */
+int  wfahip_diff_text_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                             const void *d_seq_blob, uint64_t blob_bytes, const void *d_q_off, const void *d_q_len,
+                             const void *d_t_off, const void *d_t_len, uint64_t n_pairs, int only_aligned,
+                             void *d_text, uint64_t text_cap, void *d_text_off /* u64[n_pairs + 1] */, uint64_t *text_needed,
+                             void *stream);
+
+/* The difference string from 2-bit packed words, both strands.  For a flagged pair (d_q_rc[i] != 0) the record's coordinates and ops
+ * count on the reverse-complemented query, which exists nowhere a caller can point to: this is the only compact product that names
+ * its bases.  The letter of a code is "actg"[code] (wfa_altext_pk.hpp's letter, lower-cased like any other byte); base p of a flagged
+ * query of len bases is the complement (code ^ 2) of forward base len - 1 - p.  The text equals, byte for byte, what
+ * wfahip_diff_text_device writes for the same records and ops over the corresponding bytes.
+ * d_rec / d_ops, the words, the offsets (u64), lengths (u32) and flags (u8 per pair, NULL = none set) as
+ * wfahip_alignment_text_packed_device takes them, and with that entry's rules word for word: offsets may come in any order, repeat,
+ * alias, and name a prefix of a longer sequence under another length or flag; the offsets of a pair that renders nothing (status not
+ * OK, OPS_LEN 0, no op that renders a byte, no 'M' op under only_aligned) are never looked at; of a sequence that renders only words
+ * in [woff, woff + wfahip_packed_words(len)) are read, no result depends on the bits of its last word beyond its last base or on its
+ * pad word, and d_packed needs NO readable memory behind its n_words words.  The checks are that entry's: the ops lie in [0, ops_cap);
+ * for both sequences woff <= n_words and wfahip_packed_words(len) <= n_words - woff; trimmed, 1 <= BEGIN, BEGIN - 1 <= END and END <=
+ * the sequence's length; the bases consumed fit the windows.  d_text, d_text_off, *text_needed, text_cap, WFAHIP_ERR_OOM,
+ * WFAHIP_ERR_BAD_ARG (d_text untouched, before the kernel that reads a word to write text is launched), n_pairs == 0, stream,
+ * synchrony and wfahip_last_timing (untouched) are wfahip_diff_text_device's, word for word; no input is written.
+ * WFAHIP_ERR_BAD_ARG before the context is dereferenced: a null ctx; with n_pairs > 0 a null d_rec, d_text_off, d_q_woff, d_q_len,
+ * d_t_woff or d_t_len; a null d_ops with ops_cap > 0; a null d_packed with n_words > 0; a null d_text with text_cap > 0; n_pairs
+ * beyond 0xFFFFFFF0.  Three passes: wfa_diff_pk_len_kernel, the scan, wfa_diff_pk_write_kernel -- wfa_diff_write_kernel over the
+ * packed rows' reader, four letters a funnel shift and one v_perm_b32 (KERNELS.md 4v). */
+int  wfahip_diff_text_packed_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap,
+                                    const void *d_packed, uint64_t n_words, const void *d_q_woff, const void *d_q_len,
+                                    const void *d_t_woff, const void *d_t_len, const void *d_q_rc /* u8 per pair, NULL = none */,
+                                    uint64_t n_pairs, int only_aligned, void *d_text, uint64_t text_cap,
+                                    void *d_text_off /* u64[n_pairs + 1] */, uint64_t *text_needed, void *stream);
+
+/* Host only, no device, no context: the same bytes and offsets for a wfahip_results in host memory and the blob and arrays (the
+ * words, offsets, lengths and flags) it was aligned from -- n_threads host threads over contiguous ranges of pairs, the same header
+ * functions as the kernels.  The trimmed windows are r->qbegin / qend / tbegin / tend.  out is wfahip_cigar_text's struct: text holds
+ * n_bytes bytes (NULL when n_bytes == 0), off n + 1 offsets, off[0] = 0 and off[n] = n_bytes; both are malloc'd and released with
+ * wfahip_cigars_free.  r->n == 0 gives n = n_bytes = 0, text = NULL and off pointing at one 0.  WFAHIP_ERR_BAD_ARG (out zeroed, when
+ * there is one) as wfahip_alignment_text / wfahip_alignment_text_packed: a null r or out; with r->n > 0 a null status, ops_off,
+ * ops_len, offset or length array, and under only_aligned a null qbegin, qend, tbegin or tend; a null ops with n_ops > 0; a null
+ * seq_blob with blob_bytes > 0 (a null packed with n_words > 0); a pair that fails a check of the device entry (with n_ops as
+ * ops_cap). */
+int  wfahip_diff_text(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                      const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads,
+                      wfahip_cigars *out);
+int  wfahip_diff_text_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
+                             const uint8_t *q_rc /* NULL = none */, int only_aligned, int n_threads, wfahip_cigars *out);
+
 /* The check: is each alignment consistent with its sequences, what does it cost, and which pairs are not?  One pass over records,
  * ops and sequences where they lie; per pair WFAHIP_CHK_WORDS = 8 u32 words -- FLAGS, COST, Q_USED, T_USED, N_BAD, FIRST_BAD, 0, 0 --
  * and, if asked for, a status for the stages behind.  The flags state what IS, not what is wrong: the reference's own results raise

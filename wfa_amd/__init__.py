@@ -8,7 +8,7 @@ from .aligner import (  # noqa: F401
     DefaultPenalties, ErrEmptySeq, ErrOverMaxScore, ErrSeqTooLong, MaskLower32, MaxSeqLen, New, Op, OpD, OpH, OpI, OpM, OpX,
     Options, Penalties, RecycleAligner, RecycleAlignmentResult, RecycleAlignmentText, WfaError, generate_pairs,
     make_blob, plot_component, trimOps, wide_class_bounds, revcomp_packed, best_strand, cigar_text, alignment_text,
-    alignment_text_packed, check_alignments, check_alignments_packed,
+    alignment_text_packed, check_alignments, check_alignments_packed, diff_text, diff_text_packed,
 )
 from ._lib import (  # noqa: F401
     PAIR_CHECK_FAILED, CHK_WORDS, CHK_NAMES, CHK_ALL, CHK_OPS_RANGE, CHK_LETTER, CHK_ZERO, CHK_UNMERGED, CHK_NO_M, CHK_SEQ_RANGE, CHK_Q_OVER,

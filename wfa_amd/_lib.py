@@ -49,6 +49,7 @@ EXPORTS = [
     "wfahip_alignment_text_packed_device", "wfahip_alignment_text_packed",
     "wfahip_check_alignments_device", "wfahip_check_alignments_packed_device", "wfahip_check_alignments",
     "wfahip_check_alignments_packed",
+    "wfahip_diff_text_device", "wfahip_diff_text_packed_device", "wfahip_diff_text", "wfahip_diff_text_packed",
 ]
 
 
@@ -184,6 +185,15 @@ def lib():
         L.wfahip_check_alignments_packed.restype = C.c_int
         L.wfahip_check_alignments_packed.argtypes = [C.POINTER(Results), C.POINTER(Params), vp, u64, vp, vp, vp, vp, vp, u32, C.c_int, vp, vp,
                                                      C.POINTER(u64)]
+        L.wfahip_diff_text_device.restype = C.c_int
+        L.wfahip_diff_text_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, C.c_int, vp, u64, vp, C.POINTER(u64), vp]
+        L.wfahip_diff_text_packed_device.restype = C.c_int
+        L.wfahip_diff_text_packed_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, C.c_int, vp, u64, vp, C.POINTER(u64),
+                                                     vp]
+        L.wfahip_diff_text.restype = C.c_int
+        L.wfahip_diff_text.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Cigars)]
+        L.wfahip_diff_text_packed.restype = C.c_int
+        L.wfahip_diff_text_packed.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Cigars)]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

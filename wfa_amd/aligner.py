@@ -558,6 +558,18 @@ class Aligner:
             raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
         self._want_tensor("ops", ops, torch.int64, dev)
         n = int(rec.shape[0])
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+
+        def entry(text, cap, off, needed, stream):
+            return L.lib().wfahip_cigar_text_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), n, 1 if only_aligned else 0, text, cap,
+                                                    off.data_ptr(), C.byref(needed), stream.cuda_stream)
+        return self._render_text(n, dev, out, stream, entry, "wfahip_cigar_text_device")
+
+    def _render_text(self, n, dev, out, stream, entry, what):
+        """what the methods that return one text share (cigar_tensors, diff_tensors, diff_tensors_packed): out= checked, one sizing call
+        and one that writes (or one into out), the error raised.  entry(text, cap, off, needed, stream) is the C call with the
+        text's pointer (None without a byte of capacity) and its capacity."""
+        import torch
         if out is not None:
             try:
                 text, off = out
@@ -569,18 +581,15 @@ class Aligner:
         stream = self._want_stream(stream, dev)
         if out is None:
             off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        self._order_after_torch(stream, dev)  # (the fill above, and whatever made rec and ops, ran on torch's current stream)
+        self._order_after_torch(stream, dev)  # (the fill above, and whatever made the inputs, ran on torch's current stream)
         if n == 0:
             if out is not None:
                 off[:1] = 0
             return (torch.zeros(0, dtype=torch.uint8, device=dev) if out is None else text), off
-        lib = L.lib()
         needed = C.c_uint64(0)
 
         def call(t):
-            return lib.wfahip_cigar_text_device(self._ctx, rec.data_ptr(), ops.data_ptr() if ops.numel() else None, ops.numel(), n,
-                                                1 if only_aligned else 0, t.data_ptr() if t is not None and t.numel() else None,
-                                                t.numel() if t is not None else 0, off.data_ptr(), C.byref(needed), stream.cuda_stream)
+            return entry(t.data_ptr() if t is not None and t.numel() else None, t.numel() if t is not None else 0, off, needed, stream)
         if out is None:
             rc = call(None)  # the sizing call
             if rc == L.ERR_OOM:
@@ -590,7 +599,7 @@ class Aligner:
                 text = torch.zeros(0, dtype=torch.uint8, device=dev)
         else:
             rc = call(text)
-        L.check(rc, "wfahip_cigar_text_device" + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        L.check(rc, what + (f" ({L.lib().wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
         return text, off
 
     # -- new: the packed entries on device-resident data (include/wfa_hip.h: wfahip_pack_pairs_device, wfahip_align_batch_packed_device)
@@ -896,6 +905,66 @@ class Aligner:
                                                            ptr(q_rc), n, 1 if only_aligned else 0, *rows, cap, off.data_ptr(),
                                                            C.byref(needed), stream.cuda_stream)
         return self._render_rows(n, dev, out, stream, entry, "wfahip_alignment_text_packed_device")
+
+    def diff_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, out=None, stream=None):
+        """The difference string (minimap2's cs tag, short form) of every pair of (rec, ops) -- align_tensors' output -- over the
+        blob and the four tensors that call was given, rendered on the aligner's GPU (include/wfa_hip.h: wfahip_diff_text_device):
+        returns (text uint8, off int64 [n + 1]); pair i's string is text[off[i]:off[i + 1]] -- ':' and a count per M op, '*' target
+        base, query base per X column, '-' and the target's bases per I op, '+' and the query's per D or H op, bases in lower case --
+        and off[n] the total.  The target is the string's reference sequence.  Which ops render, the windows under only_aligned, the
+        empty strings and the refused records are alignment_text_tensors'; out=, the sizing call and the errors are cigar_tensors'.
+        No input is written.  stream and ValueErrors as score_tensors."""
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        self._want_tensor("blob", blob, torch.uint8, dev)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(rec.shape[0])
+        if q_off.numel() != n or q_len.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors must hold one element per record")
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+
+        def entry(text, cap, off, needed, stream):
+            return L.lib().wfahip_diff_text_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(blob), blob.numel(), q_off.data_ptr(),
+                                                   q_len.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n, 1 if only_aligned else 0, text,
+                                                   cap, off.data_ptr(), C.byref(needed), stream.cuda_stream)
+        return self._render_text(n, dev, out, stream, entry, "wfahip_diff_text_device")
+
+    def diff_tensors_packed(self, rec, ops, packed, q_woff, q_len, t_woff, t_len, q_rc=None, only_aligned: bool = False, out=None,
+                            stream=None):
+        """diff_tensors over 2-bit words, both strands (include/wfa_hip.h: wfahip_diff_text_packed_device): (rec, ops) are
+        align_tensors_packed's output, packed / q_woff / q_len / t_woff / t_len / q_rc the tensors that call was given, as
+        alignment_text_tensors_packed takes them.  The string of a flagged pair spells the bases of the reverse complement of its
+        query, the strand its record and ops speak of.  Returns, out=, errors, stream and ValueErrors as diff_tensors; the text
+        equals that method's over the corresponding bytes."""
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        self._want_tensor("packed", packed, torch.int32, dev)
+        for name, t, dtype in (("q_woff", q_woff, torch.int64), ("q_len", q_len, torch.int32), ("t_woff", t_woff, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(rec.shape[0])
+        if q_woff.numel() != n or q_len.numel() != n or t_woff.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors must hold one element per record")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+
+        def entry(text, cap, off, needed, stream):
+            return L.lib().wfahip_diff_text_packed_device(self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(packed), packed.numel(),
+                                                          q_woff.data_ptr(), q_len.data_ptr(), t_woff.data_ptr(), t_len.data_ptr(), ptr(q_rc),
+                                                          n, 1 if only_aligned else 0, text, cap, off.data_ptr(), C.byref(needed),
+                                                          stream.cuda_stream)
+        return self._render_text(n, dev, out, stream, entry, "wfahip_diff_text_packed_device")
 
     def _render_rows(self, n, dev, out, stream, entry, what):
         """what the row methods share: out= checked, one sizing call and one that writes (or one into out), the error raised.
@@ -1288,6 +1357,34 @@ def alignment_text_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_
                           1 if only_aligned else 0, int(n_threads), C.byref(txt)), "wfahip_alignment_text_packed")
 
 
+def diff_text(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len, only_aligned: bool = False, n_threads: int = 8):
+    """The difference string (minimap2's cs tag, short form) of every pair of a BatchResult over the blob and arrays it was aligned
+    from, rendered by host threads (include/wfa_hip.h: wfahip_diff_text; no GPU, no Aligner): returns (text np.uint8, off np.uint64
+    [n + 1]); pair i's string is text[off[i]:off[i + 1]], with the target as its reference sequence -- ':' and a count per M op, '*'
+    target base, query base per X column, '-' and the target's bases per I op, '+' and the query's per D or H op, bases in lower
+    case.  Empty strings, ValueErrors and WfaHipError (ERR_BAD_ARG) as alignment_text."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    return _host_rows(batch_result, blob, "blob", q_off, q_len, t_off, t_len, None, n_threads,
+                      lambda res, q_off, q_len, t_off, t_len, q_rc, cig: L.lib().wfahip_diff_text(
+                          C.byref(res), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len), 1 if only_aligned else 0,
+                          int(n_threads), C.byref(cig)), "wfahip_diff_text", diff=True)
+
+
+def diff_text_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_woff, t_len, q_rc=None, only_aligned: bool = False,
+                     n_threads: int = 8):
+    """diff_text over 2-bit words, both strands (include/wfa_hip.h: wfahip_diff_text_packed; no GPU, no Aligner): the strings of a
+    BatchResult of align_arrays_packed_rc (or align_arrays_packed, q_rc=None) from the words, offsets, lengths and flags it was
+    aligned from.  The string of a flagged pair spells the bases of the reverse complement of its query, the strand its record and
+    ops speak of.  Returns and errors as diff_text."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    return _host_rows(batch_result, packed, "packed", q_woff, q_len, t_woff, t_len, q_rc, n_threads,
+                      lambda res, q_woff, q_len, t_woff, t_len, q_rc, cig: L.lib().wfahip_diff_text_packed(
+                          C.byref(res), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff), vp(t_len), vp(q_rc),
+                          1 if only_aligned else 0, int(n_threads), C.byref(cig)), "wfahip_diff_text_packed", diff=True)
+
+
 def check_alignments(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len, penalties=None, options=None, adaptive=None,
                      mask: int = L.CHK_ALL, n_threads: int = 8):
     """The verdict on every pair of a BatchResult over the blob and arrays it was aligned from, computed by host threads
@@ -1365,9 +1462,10 @@ def _host_check(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, penalties
     return chk, passed, int(cnt.value)
 
 
-def _host_rows(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, n_threads, call, what):
+def _host_rows(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, n_threads, call, what, diff=False):
     """what the host row renderers share: the arrays made contiguous and checked, the wfahip_results view of the BatchResult,
-    call(res, q_off, q_len, t_off, t_len, q_rc, txt) -- the C entry --, and the rows copied out of its struct"""
+    call(res, q_off, q_len, t_off, t_len, q_rc, txt) -- the C entry --, and the rows copied out of its struct.  diff: the struct is a
+    wfahip_cigars and (text, off) is returned -- the difference string's host functions"""
     status = np.ascontiguousarray(br.status, dtype=np.int32)
     ops_off = np.ascontiguousarray(br.ops_off, dtype=np.uint64)
     ops_len = np.ascontiguousarray(br.ops_len, dtype=np.uint32)
@@ -1395,6 +1493,13 @@ def _host_rows(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, n_threads,
     res.ops_len = ops_len.ctypes.data_as(C.POINTER(C.c_uint32))
     res.ops = ops.ctypes.data_as(C.POINTER(C.c_uint64))
     res.qbegin, res.qend, res.tbegin, res.tend = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in windows)
+    if diff:
+        cig = L.Cigars()
+        L.check(call(res, q_off, q_len, t_off, t_len, q_rc, cig), what)
+        try:
+            return _take_cigars(cig)
+        finally:
+            L.lib().wfahip_cigars_free(C.byref(cig))
     txt = L.AlignTexts()
     L.check(call(res, q_off, q_len, t_off, t_len, q_rc, txt), what)
     try:

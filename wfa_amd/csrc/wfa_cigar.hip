@@ -23,6 +23,10 @@
 // wfa_altext_pk_write_kernel, whose lanes take four letters out of two words by a funnel shift where the byte kernel loads four
 // bytes, a flagged query's from the far end of its words, reversed and complemented (KERNELS.md 4t).
 //
+// The difference string (wfahip_diff_text_device, wfahip_diff_text_packed_device and their host entries; the rule is wfa_diff.hpp's):
+// the rows' length pass with the bytes of the text as a fourth sum, the same scan, and wfa_diff_write_kernel /
+// wfa_diff_pk_write_kernel -- a lane renders its own op where the token is short, the whole wave sweeps a long op (KERNELS.md 4v).
+//
 // The check (wfahip_check_alignments_device, wfahip_check_alignments_packed_device and their host entries; the rule is
 // wfa_check.hpp's): ONE pass, wfa_check_kernel / wfa_check_pk_kernel, the write kernels' rounds and their column sweep (alt_sweep)
 // with a sink that compares an M or X column's two bases where the write kernels store them; eight words and a status a pair,
@@ -33,6 +37,7 @@
 #include "wfa_altext.hpp"
 #include "wfa_altext_pk.hpp"
 #include "wfa_check.hpp"
+#include "wfa_diff.hpp"
 
 using namespace wfa;
 
@@ -57,6 +62,7 @@ struct CigParams {
 };
 
 // the display rows: C's text_off is the rows' offset array (text is not used), CIG_BAD_RANGE is raised by every failed check
+// (the difference string: the same struct with the text in C.text, the planes null and dwords saying that the TEXT is 4-byte aligned)
 struct AltParams {
     CigParams       C;
     const uint8_t  *blob;
@@ -258,7 +264,9 @@ __device__ __forceinline__ uint32_t alt_load4(const uint8_t *p) {  // four bytes
 // the sequences and the windows -- window(i, &w) gives pair i's windows, false where they fail.  A pair that fails a check raises
 // CIG_BAD_RANGE; pass 3 is then not launched.  The byte entry checks the windows of every pair with an op in its range; the packed
 // entry (COLUMNS_ONLY) only those of a pair with a column, so that the offsets of a pair that renders nothing are never looked at.
-template <bool COLUMNS_ONLY, class Window>
+// DIFF: the pass of the difference string (wfa_diff.hpp) -- the same checks, and a fourth sum, the bytes of the text, is what
+// text_off[i] receives in place of the columns (a pair has a byte exactly when it has a column).
+template <bool COLUMNS_ONLY, bool DIFF = false, class Window>
 __device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window) {
     const uint64_t i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
@@ -266,14 +274,19 @@ __device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window
     const uint64_t *ops;
     uint32_t        first, end;
     cig_wave_range(C, i, lane, &ops, &first, &end);
-    AltSums s = {0, 0, 0};
-    for (uint32_t k = first + lane; k < end; k += 64u) alt_add(&s, ops[k]);
+    AltSums            s     = {0, 0, 0};
+    unsigned long long bytes = 0ull;  // (DIFF only)
+    for (uint32_t k = first + lane; k < end; k += 64u) {
+        alt_add(&s, ops[k]);
+        if constexpr (DIFF) bytes += diff_op_bytes(ops[k]);
+    }
     unsigned long long cols = s.cols, qb = s.q, tb = s.t;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         cols += __shfl_xor(cols, o, 64);
         qb += __shfl_xor(qb, o, 64);
         tb += __shfl_xor(tb, o, 64);
+        if constexpr (DIFF) bytes += __shfl_xor(bytes, o, 64);
     }
     if (lane == 0) {
         uint32_t count = end - first;
@@ -286,7 +299,7 @@ __device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window
             }
         }
         if (cols == 0ull) count = 0u;  // (ops without a column: pass 3 has nothing to do)
-        C.text_off[i] = cols;
+        C.text_off[i] = DIFF ? (cols != 0ull ? bytes : 0ull) : cols;
         C.range[i]    = make_uint2(first, count);
     }
 }
@@ -444,6 +457,97 @@ struct AltPkSeq {
 // two words per sequence and one v_perm_b32 from codes to letters; a flagged query reads the four bases that END at len - 1 - p.
 __global__ __launch_bounds__(256) void wfa_altext_pk_write_kernel(const AltPkParams A) {
     alt_write_pass(A, [&](uint64_t i) {
+        AltWindow w;
+        (void)alt_pk_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+        return AltPkSeq{A.words + A.q_woff[i], A.words + A.t_woff[i], A.q_len[i], A.t_len[i], (uint32_t)w.q_at, (uint32_t)w.t_at,
+                        A.q_rc != nullptr && A.q_rc[i] != 0};
+    });
+}
+
+// ---- the difference string (wfa_diff.hpp)
+
+__global__ __launch_bounds__(256) void wfa_diff_len_kernel(const AltParams A) {
+    alt_len_pass<false, true>(A.C, [&](uint64_t i, AltWindow *w) { return alt_pair_window(A, i, w); });
+}
+
+__global__ __launch_bounds__(256) void wfa_diff_pk_len_kernel(const AltPkParams A) {
+    alt_len_pass<true, true>(A.C, [&](uint64_t i, AltWindow *w) { return alt_pk_pair_window(A, i, w); });
+}
+
+// the string, pass 3.  A round is 64 ops, a lane an op: wave prefix sums give every op its first byte of the text (64-bit: one 'X' op
+// may render 3 x 0xFFFFFFFF bytes) and its first query and target base of the windows.  Typical ops are short -- at 5 % error nearly
+// every token has 3 to 6 bytes -- so a lane renders its own op where the text has at most DIFF_LANE_BYTES bytes (diff_render, the
+// host's function: an 'M' op always, an 'X' op of up to 5 columns, a gap of up to 15 letters), as wfa_cigar_write_kernel does.  The
+// longer ops are found by a ballot and the WHOLE wave sweeps each in turn, four bytes to a lane in groups that are aligned in the
+// text buffer: no lane walks a count.  A group inside a gap's letters is one q4 / t4 and one store where d_text is 4-byte aligned;
+// an 'X' op's group, and one cut by the op's first or last byte, gathers byte by byte (diff_op_byte).  The op a sweep works on is
+// uniform, so its start, length and bases come by __shfl from the lane that holds it: the round needs no table in LDS, and no fence.
+// An 'M' op loads no sequence byte, a gap only its own side's.
+template <class Params, class MakeSeq>
+__device__ __forceinline__ void diff_write_pass(const Params &A, MakeSeq &&seq) {
+    const CigParams &C    = A.C;
+    const uint32_t   lane = threadIdx.x & 63;
+    const uint64_t   i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= C.n) return;
+    const uint2 rg = C.range[i];
+    if (rg.y == 0u) return;
+    const auto         S   = seq(i);
+    const uint32_t    *r   = C.rec + i * REC_WORDS;
+    const uint64_t    *ops = C.ops + ((uint64_t)r[REC_OPS_OFF_LO] | ((uint64_t)r[REC_OPS_OFF_HI] << 32)) + rg.x;
+    unsigned long long at  = C.text_off[i];  // the round's first byte, as an index into the text
+    uint32_t           qc = 0u, tc = 0u;     // bases the rounds before consumed (pass 1: at most the windows' lengths)
+    for (uint32_t b = 0; b < rg.y; b += 64u) {
+        const uint64_t           op   = b + lane < rg.y ? ops[b + lane] : 0ull;  // (letter 0: no byte)
+        const uint32_t           kind = alt_kind(op), cnt = alt_cols(op);
+        const uint32_t           myq = (kind & ALT_Q) ? cnt : 0u, myt = (kind & ALT_T) ? cnt : 0u;
+        const unsigned long long mine = diff_op_bytes(op);
+        unsigned long long       bi = mine;
+        uint32_t                 qi = myq, ti = myt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long b2 = __shfl_up(bi, o, 64);
+            const uint32_t           q2 = __shfl_up(qi, o, 64), t2 = __shfl_up(ti, o, 64);
+            if (lane >= (uint32_t)o) bi += b2, qi += q2, ti += t2;
+        }
+        const unsigned long long start = at + bi - mine;
+        const uint32_t           qp = qc + qi - myq, tp = tc + ti - myt;
+        if (mine != 0ull && mine <= DIFF_LANE_BYTES) diff_render(op, S, qp, tp, C.text + start);
+        for (uint64_t big = __ballot(mine > DIFF_LANE_BYTES); big != 0ull; big &= big - 1ull) {  // (an 'X' op or a gap: diff_op_byte's)
+            const int                l  = __builtin_ctzll(big);
+            const unsigned long long a  = __shfl(start, l, 64), e = a + __shfl(mine, l, 64);
+            const uint32_t           kd = __shfl(kind, l, 64), oq = __shfl(qp, l, 64), ot = __shfl(tp, l, 64);
+            for (unsigned long long g = (a & ~3ull) + 4u * lane; g < e; g += 256u) {
+                const unsigned long long lo = g > a ? g : a, hi = g + 4u < e ? g + 4u : e;  // the group's bytes of this op: lo < hi
+                const unsigned long long x  = lo - a;                                       // the first one's place in the op's text
+                const uint32_t           nb = (uint32_t)(hi - lo);
+                uint32_t                 v  = 0u;  // byte lo + j in bits 8 j ..
+                if (nb == 4u && kd != (ALT_Q | ALT_T) && x != 0ull) {
+                    v = diff_lc4(kd == ALT_T ? S.t4(ot + x - 1u) : S.q4(oq + x - 1u));
+                } else {
+                    for (uint32_t j = 0; j < nb; j++) v |= diff_op_byte(kd, S, oq, ot, x + j) << (8u * j);
+                }
+                if (nb == 4u && A.dwords != 0u) {
+                    *reinterpret_cast<uint32_t *>(C.text + g) = v;  // (lo == g)
+                } else {
+                    for (uint32_t j = 0; j < nb; j++) C.text[lo + j] = (uint8_t)(v >> (8u * j));
+                }
+            }
+        }
+        at += __shfl(bi, 63, 64);
+        qc += __shfl(qi, 63, 64), tc += __shfl(ti, 63, 64);
+    }
+}
+
+__global__ __launch_bounds__(256) void wfa_diff_write_kernel(const AltParams A) {
+    diff_write_pass(A, [&](uint64_t i) {
+        AltWindow w;
+        (void)alt_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+        return AltByteSeq{A.blob + w.q_at, A.blob + w.t_at};
+    });
+}
+
+__global__ __launch_bounds__(256) void wfa_diff_pk_write_kernel(const AltPkParams A) {
+    diff_write_pass(A, [&](uint64_t i) {
         AltWindow w;
         (void)alt_pk_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
         return AltPkSeq{A.words + A.q_woff[i], A.words + A.t_woff[i], A.q_len[i], A.t_len[i], (uint32_t)w.q_at, (uint32_t)w.t_at,
@@ -749,6 +853,42 @@ int altext_pk_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops,
         [&](uint32_t grid) { hipLaunchKernelGGL(wfa_altext_pk_write_kernel, dim3(grid), dim3(256), 0, st, A); });
 }
 
+// the difference string's three passes: the rows' parameters with the text in C.text (the planes stay null)
+int diff_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob, uint64_t blob_bytes,
+                     const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n, int only_aligned,
+                     void *d_text, uint64_t text_cap, void *d_text_off, uint64_t *total, hipStream_t st) {
+    AltParams A{};
+    const int rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, d_text_off, &A.C);
+    if (rc) return rc;
+    A.C.text = static_cast<uint8_t *>(d_text);
+    A.blob = static_cast<const uint8_t *>(d_seq_blob), A.blob_bytes = blob_bytes;
+    A.q_off = static_cast<const uint64_t *>(d_q_off), A.t_off = static_cast<const uint64_t *>(d_t_off);
+    A.q_len = static_cast<const uint32_t *>(d_q_len), A.t_len = static_cast<const uint32_t *>(d_t_len);
+    A.dwords = (reinterpret_cast<uintptr_t>(d_text) & 3u) == 0u;
+    return cig_passes(
+        ctx, A.C, text_cap, total, st, "diff text",
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_diff_len_kernel, dim3(grid), dim3(256), 0, st, A); },
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_diff_write_kernel, dim3(grid), dim3(256), 0, st, A); });
+}
+
+int diff_pk_device_impl(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed, uint64_t n_words,
+                        const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc, uint64_t n,
+                        int only_aligned, void *d_text, uint64_t text_cap, void *d_text_off, uint64_t *total, hipStream_t st) {
+    AltPkParams A{};
+    const int   rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, d_text_off, &A.C);
+    if (rc) return rc;
+    A.C.text = static_cast<uint8_t *>(d_text);
+    A.words = static_cast<const uint32_t *>(d_packed), A.n_words = n_words;
+    A.q_woff = static_cast<const uint64_t *>(d_q_woff), A.t_woff = static_cast<const uint64_t *>(d_t_woff);
+    A.q_len = static_cast<const uint32_t *>(d_q_len), A.t_len = static_cast<const uint32_t *>(d_t_len);
+    A.q_rc   = static_cast<const uint8_t *>(d_q_rc);
+    A.dwords = (reinterpret_cast<uintptr_t>(d_text) & 3u) == 0u;
+    return cig_passes(
+        ctx, A.C, text_cap, total, st, "diff text packed",
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_diff_pk_len_kernel, dim3(grid), dim3(256), 0, st, A); },
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_diff_pk_write_kernel, dim3(grid), dim3(256), 0, st, A); });
+}
+
 // what the two row entries share: seq_args_ok is the verdict on the pointers of the sequences (nothing before impl dereferences the
 // context), impl(st, &total) runs the three passes
 template <class Impl>
@@ -796,10 +936,13 @@ int altext_pk_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops
                         });
 }
 
-int cigar_text_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n_pairs, int only_aligned,
-                            void *d_text, uint64_t text_cap, void *d_text_off, uint64_t *text_needed, hipStream_t st) {
+// what the entries that write ONE text share (the CIGAR text, the difference string): seq_args_ok is the verdict on the pointers of
+// the sequences (true where there are none), impl(st, &total) runs the three passes
+template <class Impl>
+int text_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, bool seq_args_ok, uint64_t n_pairs, void *d_text,
+               uint64_t text_cap, void *d_text_off, uint64_t *text_needed, hipStream_t st, Impl &&impl) {
     // (nothing in these checks dereferences the context)
-    if (!ctx || (n_pairs && (!d_rec || !d_text_off)) || (!d_ops && ops_cap) || (!d_text && text_cap)) return WFAHIP_ERR_BAD_ARG;
+    if (!ctx || (n_pairs && (!d_rec || !d_text_off)) || !seq_args_ok || (!d_ops && ops_cap) || (!d_text && text_cap)) return WFAHIP_ERR_BAD_ARG;
     if (n_pairs > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit: no entry leaves records of more pairs)
     if (text_needed) *text_needed = 0;
     if (n_pairs == 0 && !d_text_off) return WFAHIP_OK;
@@ -811,9 +954,40 @@ int cigar_text_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_op
         return WFAHIP_OK;
     }
     uint64_t  total = 0;
-    const int rc    = cigar_device_impl(ctx, d_rec, d_ops, ops_cap, n_pairs, only_aligned, d_text, text_cap, d_text_off, &total, st);
+    const int rc    = impl(st, &total);
     if (text_needed && (rc == WFAHIP_OK || rc == WFAHIP_ERR_OOM)) *text_needed = total;
     return rc;
+}
+
+int cigar_text_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, uint64_t n_pairs, int only_aligned,
+                            void *d_text, uint64_t text_cap, void *d_text_off, uint64_t *text_needed, hipStream_t st) {
+    return text_entry(ctx, d_rec, d_ops, ops_cap, true, n_pairs, d_text, text_cap, d_text_off, text_needed, st,
+                      [&](hipStream_t s, uint64_t *total) {
+                          return cigar_device_impl(ctx, d_rec, d_ops, ops_cap, n_pairs, only_aligned, d_text, text_cap, d_text_off, total, s);
+                      });
+}
+
+int diff_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob, uint64_t blob_bytes,
+                      const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, uint64_t n_pairs, int only_aligned,
+                      void *d_text, uint64_t text_cap, void *d_text_off, uint64_t *text_needed, hipStream_t st) {
+    const bool seq_ok = !(n_pairs && (!d_q_off || !d_q_len || !d_t_off || !d_t_len)) && !(!d_seq_blob && blob_bytes);
+    return text_entry(ctx, d_rec, d_ops, ops_cap, seq_ok, n_pairs, d_text, text_cap, d_text_off, text_needed, st,
+                      [&](hipStream_t s, uint64_t *total) {
+                          return diff_device_impl(ctx, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs,
+                                                  only_aligned, d_text, text_cap, d_text_off, total, s);
+                      });
+}
+
+int diff_pk_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed, uint64_t n_words,
+                         const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len, const void *d_q_rc,
+                         uint64_t n_pairs, int only_aligned, void *d_text, uint64_t text_cap, void *d_text_off, uint64_t *text_needed,
+                         hipStream_t st) {
+    const bool seq_ok = !(n_pairs && (!d_q_woff || !d_q_len || !d_t_woff || !d_t_len)) && !(!d_packed && n_words);
+    return text_entry(ctx, d_rec, d_ops, ops_cap, seq_ok, n_pairs, d_text, text_cap, d_text_off, text_needed, st,
+                      [&](hipStream_t s, uint64_t *total) {
+                          return diff_pk_device_impl(ctx, d_rec, d_ops, ops_cap, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc,
+                                                     n_pairs, only_aligned, d_text, text_cap, d_text_off, total, s);
+                      });
 }
 
 void cigars_zero(wfahip_cigars *c) { std::memset(c, 0, sizeof *c); }
@@ -926,6 +1100,23 @@ void align_texts_zero(wfahip_align_texts *t) { std::memset(t, 0, sizeof *t); }
 // blob or the words); window(i, trim, &w) gives the windows of pair i -- asked only for an OK pair with an op that renders --, false
 // where they fail; rows_write(i, ops, count, w, q_row, a_row, t_row) renders the pair.  columns_only: the windows of a pair whose
 // ops have no column are not asked for (the packed entry; the byte entry checks every pair with an op in its range).
+// a pair's rendering ops, its windows and the size of what it renders; false where wfa_altext.hpp's checks fail.  sums(ops, count,
+// &size) gives the ops' AltSums and that size -- the columns of the rows, the bytes of the difference string.  ONE copy of the checks
+// for the host renderers of both.
+template <class Window, class Sums>
+bool host_pair_checked(const wfahip_results *r, uint64_t i, bool trim, bool columns_only, Window &&window, Sums &&sums, const uint64_t **ops,
+                       uint32_t *count, AltWindow *w, uint64_t *size) {
+    if (!host_pair_ops(r, i, trim, ops, count)) return false;
+    *size = 0;
+    if (*count == 0u) return true;
+    uint64_t      sz = 0;
+    const AltSums s  = sums(*ops, *count, &sz);
+    if (columns_only && s.cols == 0) return true;
+    if (!window(i, trim, w) || !alt_fits(s, *w)) return false;
+    *size = s.cols != 0 ? sz : 0;
+    return true;
+}
+
 template <class Window, class RowsWrite>
 int alignment_text_host_impl(const wfahip_results *r, bool seq_args_ok, bool columns_only, int only_aligned, int n_threads,
                              wfahip_align_texts *out, Window &&window, RowsWrite &&rows_write) {
@@ -940,14 +1131,14 @@ int alignment_text_host_impl(const wfahip_results *r, bool seq_args_ok, bool col
     const bool trim = only_aligned != 0;
     // a pair's rendering ops and windows; false where wfa_altext.hpp's checks fail
     const auto pair = [&](uint64_t i, const uint64_t **ops, uint32_t *count, AltWindow *w, uint64_t *cols) {
-        if (!host_pair_ops(r, i, trim, ops, count)) return false;
-        *cols = 0;
-        if (*count == 0u) return true;
-        const AltSums s = alt_sums(*ops, *count);
-        if (columns_only && s.cols == 0) return true;
-        if (!window(i, trim, w) || !alt_fits(s, *w)) return false;
-        *cols = s.cols;
-        return true;
+        return host_pair_checked(
+            r, i, trim, columns_only, window,
+            [](const uint64_t *o, uint32_t c, uint64_t *size) {
+                const AltSums s = alt_sums(o, c);
+                *size           = s.cols;
+                return s;
+            },
+            ops, count, w, cols);
     };
     const int rc = host_render(
         n, n_threads, &off, &total,
@@ -1007,6 +1198,83 @@ int alignment_text_packed_host(const wfahip_results *r, const uint32_t *packed, 
         [&](uint64_t i, const uint64_t *ops, uint32_t count, const AltWindow &w, uint8_t *q_row, uint8_t *a_row, uint8_t *t_row) {
             alt_pk_rows_write(ops, count, packed + q_woff[i], q_len[i], q_rc != nullptr && q_rc[i] != 0, (uint32_t)w.q_at, packed + t_woff[i],
                               t_len[i], (uint32_t)w.t_at, q_row, a_row, t_row);
+        });
+}
+
+// the host renderers of the difference string: alignment_text_host_impl's plan with one text in place of three rows.  make_seq(i, w)
+// gives wfa_diff.hpp's reader of pair i's windows.
+template <class Window, class MakeSeq>
+int diff_text_host_impl(const wfahip_results *r, bool seq_args_ok, bool columns_only, int only_aligned, int n_threads, wfahip_cigars *out,
+                        Window &&window, MakeSeq &&make_seq) {
+    if (out) cigars_zero(out);
+    if (!r || !out) return WFAHIP_ERR_BAD_ARG;
+    const uint64_t n = r->n;
+    if (n && (!r->status || !r->ops_off || !r->ops_len)) return WFAHIP_ERR_BAD_ARG;
+    if (n && only_aligned && (!r->qbegin || !r->qend || !r->tbegin || !r->tend)) return WFAHIP_ERR_BAD_ARG;
+    if ((!r->ops && r->n_ops) || !seq_args_ok) return WFAHIP_ERR_BAD_ARG;
+    char      *text = nullptr;
+    uint64_t  *off = nullptr, total = 0;
+    const bool trim = only_aligned != 0;
+    const auto pair = [&](uint64_t i, const uint64_t **ops, uint32_t *count, AltWindow *w, uint64_t *bytes) {
+        return host_pair_checked(
+            r, i, trim, columns_only, window,
+            [](const uint64_t *o, uint32_t c, uint64_t *size) {
+                const DiffSums s = diff_sums(o, c);
+                *size            = s.bytes;
+                return s.a;
+            },
+            ops, count, w, bytes);
+    };
+    const int rc = host_render(
+        n, n_threads, &off, &total,
+        [&](uint64_t i, uint64_t *bytes) {
+            uint32_t        count;
+            const uint64_t *ops;
+            AltWindow       w;
+            return pair(i, &ops, &count, &w, bytes);
+        },
+        [&](uint64_t bytes) { return (text = static_cast<char *>(std::malloc((size_t)bytes))) != nullptr; },
+        [&](uint64_t i, uint64_t at) {
+            uint32_t        count;
+            const uint64_t *ops;
+            AltWindow       w;
+            uint64_t        bytes;
+            (void)pair(i, &ops, &count, &w, &bytes);
+            diff_write(ops, count, make_seq(i, w), reinterpret_cast<uint8_t *>(text) + at);
+        });
+    if (rc) return rc;
+    out->n       = n;
+    out->n_bytes = total;
+    out->text    = text;
+    out->off     = off;
+    return WFAHIP_OK;
+}
+
+int diff_text_host(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                   const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads, wfahip_cigars *out) {
+    const bool seq_ok = r && !(r->n && (!q_off || !q_len || !t_off || !t_len)) && !(!seq_blob && blob_bytes);
+    return diff_text_host_impl(
+        r, seq_ok, false, only_aligned, n_threads, out,
+        [&](uint64_t i, bool trim, AltWindow *w) {
+            return alt_window(trim, blob_bytes, q_off[i], q_len[i], t_off[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                              trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w);
+        },
+        [&](uint64_t, const AltWindow &w) { return DiffByteSeq{seq_blob + w.q_at, seq_blob + w.t_at}; });
+}
+
+int diff_text_packed_host(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff, const uint32_t *q_len,
+                          const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc, int only_aligned, int n_threads,
+                          wfahip_cigars *out) {
+    const bool seq_ok = r && !(r->n && (!q_woff || !q_len || !t_woff || !t_len)) && !(!packed && n_words);
+    return diff_text_host_impl(
+        r, seq_ok, true, only_aligned, n_threads, out,
+        [&](uint64_t i, bool trim, AltWindow *w) {
+            return alt_pk_window(trim, n_words, q_woff[i], q_len[i], t_woff[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                                 trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w);
+        },
+        [&](uint64_t i, const AltWindow &w) {
+            return DiffPkSeq{packed + q_woff[i], packed + t_woff[i], q_len[i], t_len[i], (uint32_t)w.q_at, (uint32_t)w.t_at,
+                             q_rc != nullptr && q_rc[i] != 0};
         });
 }
 
@@ -1279,6 +1547,34 @@ extern "C" int wfahip_alignment_text_packed(const wfahip_results *r, const uint3
                                             const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc,
                                             int only_aligned, int n_threads, wfahip_align_texts *out) {
     WFAHIP_GUARD(alignment_text_packed_host(r, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, only_aligned, n_threads, out))
+}
+
+extern "C" int wfahip_diff_text_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob,
+                                       uint64_t blob_bytes, const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len,
+                                       uint64_t n_pairs, int only_aligned, void *d_text, uint64_t text_cap, void *d_text_off,
+                                       uint64_t *text_needed, void *stream) {
+    WFAHIP_GUARD(diff_device_entry(ctx, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, n_pairs, only_aligned,
+                                   d_text, text_cap, d_text_off, text_needed, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_diff_text_packed_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed,
+                                              uint64_t n_words, const void *d_q_woff, const void *d_q_len, const void *d_t_woff,
+                                              const void *d_t_len, const void *d_q_rc, uint64_t n_pairs, int only_aligned, void *d_text,
+                                              uint64_t text_cap, void *d_text_off, uint64_t *text_needed, void *stream) {
+    WFAHIP_GUARD(diff_pk_device_entry(ctx, d_rec, d_ops, ops_cap, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc, n_pairs,
+                                      only_aligned, d_text, text_cap, d_text_off, text_needed, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_diff_text(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                                const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads,
+                                wfahip_cigars *out) {
+    WFAHIP_GUARD(diff_text_host(r, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, only_aligned, n_threads, out))
+}
+
+extern "C" int wfahip_diff_text_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                                       const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc,
+                                       int only_aligned, int n_threads, wfahip_cigars *out) {
+    WFAHIP_GUARD(diff_text_packed_host(r, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, only_aligned, n_threads, out))
 }
 
 extern "C" void wfahip_align_texts_free(wfahip_align_texts *t) {
