@@ -10,7 +10,7 @@ HDR     := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inc) include/wfa_hip.h
 OBJDIR  := build/obj
 # one translation unit per penalty shape of the sub-wave forward kernels (wfa_fwd.hpp), one for wfa_duo_kernel, one for the
 # score-only kernels (wfa_score.hip), one for wfa_wide_kernel's packed full-alignment instances and the length-class plan (wfa_wide_pk.hip), one for the
-# long-pair kernels, one for the CIGAR text, display-row, difference-string and check kernels and their entries (wfa_cigar.hip: the check shares the display rows' column sweep, the difference string their length pass), one for the device packer (wfa_packdev.hip), four for the host side (router, host entries, score entries,
+# long-pair kernels, one for the CIGAR text, display-row, difference-string, check and pileup kernels and their entries (wfa_cigar.hip: the check shares the display rows' column sweep, the difference string and the pileup their length pass), one for the device packer (wfa_packdev.hip), four for the host side (router, host entries, score entries,
 # debug aids: wfa_ctx.hpp): they compile side by side (make -j)
 SHAPES  := s24 s13 s12 s23 s22 s33
 UNITS   := wfa_host wfa_entry wfa_score_entry wfa_cigar wfa_packdev wfa_debug wfa_long wfa_duo wfa_score wfa_wide_pk $(addprefix wfa_fwd_,$(SHAPES))

@@ -749,6 +749,83 @@ int  wfahip_diff_text_packed(const wfahip_results *r, const uint32_t *packed, ui
                              const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len,
                              const uint8_t *q_rc /* NULL = none */, int only_aligned, int n_threads, wfahip_cigars *out);
 
+/* The pileup: what a batch's alignments say about every base of the TARGET, counted where the ops and the sequences are.  Every
+ * product above is per pair and leaves the GPU as text; a polisher, a consensus step, a variant screen or a coverage plot wants one
+ * small record per target base, and the entries say already that offsets may repeat: one target may face fifty queries.  A pileup is
+ * a caller-owned array of WFAHIP_PILE_WORDS = 8 u32 words for every base of a WINDOW [pile_at, pile_at + pile_n) of the target's
+ * storage -- for the byte entries the byte index into the blob, for the packed entries the base index 16 * woff + p (the "bytes the
+ * words stand for" of wfahip_align_batch_packed_rc).  32 bytes a base, whatever the depth:
+ *     A, C, T, G     alignments that put that query base over this target base (an M or X column).  The code of a query base is the
+ *                    packer's, (byte >> 1) & 3 of a byte among ACGTacgt -- hence the order A C T G
+ *     OTHER          ... a query byte outside those eight letters (packed input has none)
+ *     GAP            alignments in which this target base faces '-' (an I column)
+ *     EXTRA          runs of query-only bases (D ops) that hang behind this base
+ *     EXTRA_BASES    the bases of those runs
+ * The rule (wfa_amd/csrc/wfa_pile.hpp, one source for the kernels and the host entries), per op word letter << 32 | count, with qs /
+ * ts the bases the ops before it consumed inside the pair's windows and T0 the coordinate of the target window's first base (t_off +
+ * the window's start for bytes, 16 * t_woff + it for words):
+ *     M, X       column c < count: base P = T0 + ts + c gets + 1 in the word of query base qs + c.  Ops are taken at face value: an M
+ *                column is not compared with the target, as in the difference string
+ *     I          column c: base P = T0 + ts + c gets + 1 in GAP
+ *     D          count > 0: one add of 1 to EXTRA and one of count to EXTRA_BASES at base P = T0 + max(ts, 1) - 1 -- the run hangs on
+ *                the target base before it; a run in front of the window's first base shares base 0's counters (trimmed ranges begin
+ *                and end with M, so that happens only untrimmed).  Nothing when the target's window is empty
+ *     H, any other letter, count 0: nothing (H consumes query bases, as in the display rows)
+ * An add happens only when pile_at <= P < pile_at + pile_n, at counts[(P - pile_at) * 8 + word].  The entries ADD and never clear:
+ * the caller zeroes the array, and several batches, both strands or several calls accumulate into one pileup; a large reference is
+ * tiled over calls or GPUs by its window, as the score matrix is by its strided output.  Adds are u32 and wrap; integer adds
+ * commute, so the counters do not depend on scheduling.  A flagged query's base p is code ^ 2 of forward base len - 1 - p.
+ * Which pairs and ops count is wfahip_alignment_text_device's (packed: wfahip_alignment_text_packed_device's), exactly, decided by
+ * the same functions: only_aligned == 0 all ops over the whole sequences, only_aligned != 0 the first M op to the last over the windows
+ * the record names; a pair whose status is not WFAHIP_PAIR_OK, whose OPS_LEN is 0 or that trimmed has no M op adds nothing and its
+ * offsets are never looked at, nor are, in the packed entries, those of a pair whose ops have no column.  The checks are those entries'
+ * too, in the same order for every pair that would count: the ops lie in [0, ops_cap); both sequences lie inside the blob (the words);
+ * trimmed, 1 <= BEGIN, BEGIN - 1 <= END and END <= the sequence's length; the bases consumed fit the windows.  A failed check:
+ * WFAHIP_ERR_BAD_ARG with the counters untouched, before the kernel that reads a sequence byte is launched.  Untrimmed, a batch with
+ * the wf-adaptive pair whose ops consume one base more than the sequences hold is therefore refused: wfahip_check_alignments*'s
+ * d_pass under WFAHIP_CHK_NO_ROWS, copied over the status column of a copy of the records, sets it aside.
+ *
+ * wfahip_pileup_device / wfahip_pileup_packed_device: d_rec / d_ops, the blob (the words), the arrays and the flags as
+ * wfahip_diff_text_device / wfahip_diff_text_packed_device take them, with those entries' rules for pointers, stream (NULL = the
+ * context's own) and synchrony; no input is written; only bytes (words) inside the sequences are read -- the query's under M and X
+ * columns inside the window, the target's never.  d_counts: u32[8 pile_n], 4-byte aligned, the caller's.  The window may lie anywhere,
+ * also outside the blob: it then receives nothing.  *n_piled (if non-NULL) receives the number of pairs whose ops were swept -- the
+ * pairs with a column, whether or not one of them falls into the window -- from the one 64-byte counter fetch of the call.  pile_n ==
+ * 0 or n_pairs == 0 returns WFAHIP_OK with *n_piled = 0 and touches nothing.  WFAHIP_ERR_BAD_ARG before the context is dereferenced:
+ * a null ctx; with n_pairs > 0 a null d_rec, offset or length array; a null d_ops with ops_cap > 0; a null blob (words) of non-zero
+ * size; a null d_counts with pile_n > 0; pile_n beyond 2^61 / 8; n_pairs beyond 0xFFFFFFF0.  wfahip_last_timing is not touched.
+ * Two passes (wfa_cigar.hip): wfa_pile_len_kernel / wfa_pile_pk_len_kernel, the display rows' length pass -- range, sums, checks --
+ * without its offsets and its scan, one atomic a wave counting the pairs; wfa_pile_kernel / wfa_pile_pk_kernel, a wave per pair in
+ * rounds of 64 ops with the rows' table in LDS: a D op's two adds are its own lane's, the target-consuming columns are swept by target
+ * base, consecutive lanes on consecutive bases, each finding its op by a search over the table's target starts, and every column is
+ * one atomic add without a return; no lane walks a count, and only the part of a pair inside the window is walked (KERNELS.md 4w).
+ * WFAHIP_DEBUG_TIMING=1 prints the passes' times to stderr.
+ *
+ * wfahip_pileup / wfahip_pileup_packed: host only, no device, no context, the same header functions: n_threads host threads over
+ * contiguous ranges of pairs, adding with relaxed atomic adds because pairs share targets.  counts is the caller's, 8 pile_n words.
+ * WFAHIP_ERR_BAD_ARG (counts untouched) as wfahip_diff_text / wfahip_diff_text_packed -- a null r; with r->n > 0 a null status,
+ * ops_off, ops_len, offset or length array, and under only_aligned a null qbegin, qend, tbegin or tend; a null ops with n_ops > 0; a
+ * null seq_blob (packed) of non-zero size; a pair that fails a check of the device entry (with n_ops as ops_cap) -- and for a null
+ * counts with pile_n > 0 and pile_n beyond 2^61 / 8.  r->n == 0 or pile_n == 0: WFAHIP_OK, *n_piled = 0, nothing touched. */
+#define WFAHIP_PILE_WORDS 8
+enum { WFAHIP_PILE_W_A = 0, WFAHIP_PILE_W_C, WFAHIP_PILE_W_T, WFAHIP_PILE_W_G, WFAHIP_PILE_W_OTHER, WFAHIP_PILE_W_GAP, WFAHIP_PILE_W_EXTRA,
+       WFAHIP_PILE_W_EXTRA_BASES };
+int  wfahip_pileup_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob,
+                          uint64_t blob_bytes, const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len,
+                          uint64_t n_pairs, int only_aligned, uint64_t pile_at, uint64_t pile_n, void *d_counts /* u32[8 pile_n] */,
+                          uint64_t *n_piled /* may be NULL */, void *stream);
+int  wfahip_pileup_packed_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed,
+                                 uint64_t n_words, const void *d_q_woff, const void *d_q_len, const void *d_t_woff, const void *d_t_len,
+                                 const void *d_q_rc /* u8 per pair, NULL = none */, uint64_t n_pairs, int only_aligned, uint64_t pile_at,
+                                 uint64_t pile_n, void *d_counts /* u32[8 pile_n] */, uint64_t *n_piled /* may be NULL */, void *stream);
+int  wfahip_pileup(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                   const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads, uint64_t pile_at, uint64_t pile_n,
+                   uint32_t *counts /* 8 pile_n */, uint64_t *n_piled /* may be NULL */);
+int  wfahip_pileup_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff, const uint32_t *q_len,
+                          const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc /* NULL = none */, int only_aligned,
+                          int n_threads, uint64_t pile_at, uint64_t pile_n, uint32_t *counts /* 8 pile_n */,
+                          uint64_t *n_piled /* may be NULL */);
+
 /* The check: is each alignment consistent with its sequences, what does it cost, and which pairs are not?  One pass over records,
  * ops and sequences where they lie; per pair WFAHIP_CHK_WORDS = 8 u32 words -- FLAGS, COST, Q_USED, T_USED, N_BAD, FIRST_BAD, 0, 0 --
  * and, if asked for, a status for the stages behind.  The flags state what IS, not what is wrong: the reference's own results raise

@@ -23,6 +23,11 @@ CHK_NAMES = ("OPS_RANGE", "LETTER", "ZERO", "UNMERGED", "NO_M", "SEQ_RANGE", "Q_
  CHK_M_DIFFERS, CHK_X_EQUAL, CHK_NO_ROWS, CHK_NO_ROWS_TRIMMED, CHK_COST_OVER, CHK_COST_UNDER, CHK_STAT_ALIGN_LEN, CHK_STAT_MATCHES,
  CHK_STAT_GAPS, CHK_STAT_GAP_REGIONS) = (1 << k for k in range(20))
 CHK_ALL = (1 << 20) - 1
+# wfahip_pileup*: the counters of a target base (A C T G: the packer's codes)
+PILE_WORDS = 8
+PILE_W_A, PILE_W_C, PILE_W_T, PILE_W_G, PILE_W_OTHER, PILE_W_GAP, PILE_W_EXTRA, PILE_W_EXTRA_BASES = range(8)
+PILE_NAMES = ("A", "C", "T", "G", "OTHER", "GAP", "EXTRA", "EXTRA_BASES")
+PILE_MAX_N = (1 << 61) // PILE_WORDS
 MAX_SEQ_LEN = (1 << 29) - 1
 REC_WORDS = 16
 (REC_STATUS, REC_SCORE, REC_TBEGIN, REC_TEND, REC_QBEGIN, REC_QEND, REC_ALIGN_LEN, REC_MATCHES, REC_GAPS,
@@ -50,6 +55,7 @@ EXPORTS = [
     "wfahip_check_alignments_device", "wfahip_check_alignments_packed_device", "wfahip_check_alignments",
     "wfahip_check_alignments_packed",
     "wfahip_diff_text_device", "wfahip_diff_text_packed_device", "wfahip_diff_text", "wfahip_diff_text_packed",
+    "wfahip_pileup_device", "wfahip_pileup_packed_device", "wfahip_pileup", "wfahip_pileup_packed",
 ]
 
 
@@ -194,6 +200,14 @@ def lib():
         L.wfahip_diff_text.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Cigars)]
         L.wfahip_diff_text_packed.restype = C.c_int
         L.wfahip_diff_text_packed.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(Cigars)]
+        L.wfahip_pileup_device.restype = C.c_int
+        L.wfahip_pileup_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, C.c_int, u64, u64, vp, C.POINTER(u64), vp]
+        L.wfahip_pileup_packed_device.restype = C.c_int
+        L.wfahip_pileup_packed_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, C.c_int, u64, u64, vp, C.POINTER(u64), vp]
+        L.wfahip_pileup.restype = C.c_int
+        L.wfahip_pileup.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, C.c_int, C.c_int, u64, u64, vp, C.POINTER(u64)]
+        L.wfahip_pileup_packed.restype = C.c_int
+        L.wfahip_pileup_packed.argtypes = [C.POINTER(Results), vp, u64, vp, vp, vp, vp, vp, C.c_int, C.c_int, u64, u64, vp, C.POINTER(u64)]
         L.wfahip_last_timing.restype = C.c_int
         L.wfahip_last_timing.argtypes = [vp, C.POINTER(Timing)]
         L.wfahip_set_option.restype = C.c_int

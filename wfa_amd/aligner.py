@@ -966,6 +966,74 @@ class Aligner:
                                                           stream.cuda_stream)
         return self._render_text(n, dev, out, stream, entry, "wfahip_diff_text_packed_device")
 
+    # -- the pileup (include/wfa_hip.h: wfahip_pileup_device, wfahip_pileup_packed_device)
+    def pileup_tensors(self, rec, ops, blob, q_off, q_len, t_off, t_len, pile_at, pile_n, only_aligned: bool = False, out=None, stream=None):
+        """What the alignments of (rec, ops) -- align_tensors' output -- say about every base of the window [pile_at, pile_at +
+        pile_n) of the blob, counted on the aligner's GPU (include/wfa_hip.h: wfahip_pileup_device): returns (counts int32 [pile_n,
+        8], n_piled int).  counts[b] holds, for byte pile_at + b of the blob as a TARGET base, the alignments that put A, C, T, G or
+        another byte over it, those in which it faces a gap, the runs of query-only bases behind it and their bases (the PILE_W_*
+        words of _lib; the C-ABI's uint32 bit for bit); n_piled is the number of pairs whose ops were swept.  out=: a contiguous
+        int32 tensor [pile_n, 8] on that device that the call ADDS to -- several batches, both strands or several calls accumulate
+        into one pileup; without it a zeroed tensor is made.  Which pairs and ops count, the windows under only_aligned and the
+        refused records (WfaHipError ERR_BAD_ARG, the counts untouched) are alignment_text_tensors'.  No input is written.  stream
+        and ValueErrors as score_tensors."""
+        return self._pileup_tensors(False, rec, ops, blob, "blob", q_off, q_len, t_off, t_len, None, pile_at, pile_n, only_aligned, out, stream)
+
+    def pileup_tensors_packed(self, rec, ops, packed, q_woff, q_len, t_woff, t_len, pile_at, pile_n, q_rc=None, only_aligned: bool = False,
+                              out=None, stream=None):
+        """pileup_tensors over 2-bit words, both strands (include/wfa_hip.h: wfahip_pileup_packed_device): (rec, ops) are
+        align_tensors_packed's output, packed / q_woff / q_len / t_woff / t_len / q_rc the tensors that call was given, as
+        alignment_text_tensors_packed takes them.  The window counts in BASES of the words' storage: base p of the sequence at word
+        woff is 16 * woff + p.  A flagged pair adds the bases of the reverse complement of its query, the strand its record and ops
+        speak of.  Returns, out=, errors, stream and ValueErrors as pileup_tensors."""
+        return self._pileup_tensors(True, rec, ops, packed, "packed", q_woff, q_len, t_woff, t_len, q_rc, pile_at, pile_n, only_aligned, out,
+                                    stream)
+
+    def _pileup_tensors(self, is_packed, rec, ops, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, pile_at, pile_n, only_aligned, out,
+                        stream):
+        import torch
+        dev = self._want_tensor("rec", rec, torch.int32, dim=2)
+        if rec.shape[1] != L.REC_WORDS:
+            raise ValueError(f"rec must be [n, {L.REC_WORDS}]")
+        self._want_tensor("ops", ops, torch.int64, dev)
+        self._want_tensor(seqs_name, seqs, torch.int32 if is_packed else torch.uint8, dev)
+        for name, t, dtype in (("q_off", q_off, torch.int64), ("q_len", q_len, torch.int32), ("t_off", t_off, torch.int64),
+                               ("t_len", t_len, torch.int32)):
+            self._want_tensor(name, t, dtype, dev)
+        n = int(rec.shape[0])
+        if q_off.numel() != n or q_len.numel() != n or t_off.numel() != n or t_len.numel() != n:
+            raise ValueError("offset and length tensors must hold one element per record")
+        if q_rc is not None:
+            self._want_tensor("q_rc", q_rc, torch.uint8, dev)
+            if q_rc.numel() != n:
+                raise ValueError("q_rc must hold one flag per pair")
+        pile_at, pile_n = int(pile_at), int(pile_n)
+        if not 0 <= pile_at < 1 << 64 or not 0 <= pile_n <= L.PILE_MAX_N:
+            raise ValueError("pile_at must fit 64 bits and pile_n lie in [0, 2^61 / 8]")
+        if out is not None:
+            self._want_tensor("out", out, torch.int32, dev, dim=2)
+            if tuple(out.shape) != (pile_n, L.PILE_WORDS):
+                raise ValueError(f"out must be [{pile_n}, {L.PILE_WORDS}]")
+        stream = self._want_stream(stream, dev)
+        counts = out if out is not None else torch.zeros((pile_n, L.PILE_WORDS), dtype=torch.int32, device=dev)
+        if n == 0 or pile_n == 0:
+            return counts, 0
+        self._order_after_torch(stream, dev)  # (the fill above, and whatever made the inputs, ran on torch's current stream)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        cnt = C.c_uint64(0)
+        lib = L.lib()
+        head = (self._ctx, rec.data_ptr(), ptr(ops), ops.numel(), ptr(seqs), seqs.numel(), q_off.data_ptr(), q_len.data_ptr(), t_off.data_ptr(),
+                t_len.data_ptr())
+        tail = (n, 1 if only_aligned else 0, pile_at, pile_n, counts.data_ptr(), C.byref(cnt), stream.cuda_stream)
+        if is_packed:
+            what = "wfahip_pileup_packed_device"
+            rc = lib.wfahip_pileup_packed_device(*head, ptr(q_rc), *tail)
+        else:
+            what = "wfahip_pileup_device"
+            rc = lib.wfahip_pileup_device(*head, *tail)
+        L.check(rc, what + (f" ({lib.wfahip_last_error(self._ctx).decode(errors='replace')})" if rc else ""))
+        return counts, int(cnt.value)
+
     def _render_rows(self, n, dev, out, stream, entry, what):
         """what the row methods share: out= checked, one sizing call and one that writes (or one into out), the error raised.
         entry(rows, cap, off, needed, stream) is the C call with three plane pointers of capacity cap."""
@@ -1383,6 +1451,80 @@ def diff_text_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_woff,
                       lambda res, q_woff, q_len, t_woff, t_len, q_rc, cig: L.lib().wfahip_diff_text_packed(
                           C.byref(res), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff), vp(t_len), vp(q_rc),
                           1 if only_aligned else 0, int(n_threads), C.byref(cig)), "wfahip_diff_text_packed", diff=True)
+
+
+def pileup(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len, pile_at, pile_n, only_aligned: bool = False, n_threads: int = 8,
+           out=None):
+    """What the alignments of a BatchResult say about every base of the window [pile_at, pile_at + pile_n) of the blob it was aligned
+    from, counted by host threads (include/wfa_hip.h: wfahip_pileup; no GPU, no Aligner): returns counts np.uint32 [pile_n, 8] -- per
+    byte of the blob as a TARGET base the alignments that put A, C, T, G or another byte over it, those in which it faces a gap, the
+    runs of query-only bases behind it and their bases (the PILE_W_* words).  out=: a C-contiguous uint32 array of that shape that the
+    call ADDS to and returns.  ValueErrors and WfaHipError (ERR_BAD_ARG, the counts untouched) as alignment_text."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    return _host_pileup(batch_result, blob, "blob", q_off, q_len, t_off, t_len, None, n_threads, pile_at, pile_n, out,
+                        lambda res, q_off, q_len, t_off, t_len, q_rc, tail: L.lib().wfahip_pileup(
+                            C.byref(res), vp(blob), blob.size, vp(q_off), vp(q_len), vp(t_off), vp(t_len), 1 if only_aligned else 0,
+                            int(n_threads), *tail), "wfahip_pileup")
+
+
+def pileup_packed(batch_result: "BatchResult", packed, q_woff, q_len, t_woff, t_len, pile_at, pile_n, q_rc=None, only_aligned: bool = False,
+                  n_threads: int = 8, out=None):
+    """pileup over 2-bit words, both strands (include/wfa_hip.h: wfahip_pileup_packed; no GPU, no Aligner): the window counts in bases
+    of the words' storage, base p of the sequence at word woff being 16 * woff + p; a flagged pair adds the bases of the reverse
+    complement of its query.  Returns, out= and errors as pileup."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    return _host_pileup(batch_result, packed, "packed", q_woff, q_len, t_woff, t_len, q_rc, n_threads, pile_at, pile_n, out,
+                        lambda res, q_woff, q_len, t_woff, t_len, q_rc, tail: L.lib().wfahip_pileup_packed(
+                            C.byref(res), vp(packed), packed.size, vp(q_woff), vp(q_len), vp(t_woff), vp(t_len), vp(q_rc),
+                            1 if only_aligned else 0, int(n_threads), *tail), "wfahip_pileup_packed")
+
+
+def _host_pileup(br, seqs, seqs_name, q_off, q_len, t_off, t_len, q_rc, n_threads, pile_at, pile_n, out, call, what):
+    """what the host pileups share: _host_rows' arrays and checks, the window and out= checked, call(res, q_off, q_len, t_off, t_len,
+    q_rc, tail) -- the C entry, tail its last four arguments"""
+    status = np.ascontiguousarray(br.status, dtype=np.int32)
+    ops_off = np.ascontiguousarray(br.ops_off, dtype=np.uint64)
+    ops_len = np.ascontiguousarray(br.ops_len, dtype=np.uint32)
+    ops = np.ascontiguousarray(br.ops, dtype=np.uint64)
+    windows = [np.ascontiguousarray(getattr(br, f), dtype=np.int32) for f in ("qbegin", "qend", "tbegin", "tend")]
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+    t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    t_len = np.ascontiguousarray(t_len, dtype=np.uint32)
+    n = int(status.size)
+    if status.ndim != 1 or ops.ndim != 1 or seqs.ndim != 1:
+        raise ValueError(f"status, ops and {seqs_name} must be one-dimensional")
+    if any(a.shape != (n,) for a in [ops_off, ops_len, q_off, q_len, t_off, t_len] + windows):
+        raise ValueError("ops_off, ops_len, qbegin, qend, tbegin, tend and the offset and length arrays must hold one element per pair")
+    if q_rc is not None:
+        q_rc = np.ascontiguousarray(q_rc, dtype=np.uint8)
+        if q_rc.shape != (n,):
+            raise ValueError("q_rc must hold one flag per pair")
+    if int(n_threads) < 1:
+        raise ValueError("n_threads must be at least 1")
+    pile_at, pile_n = int(pile_at), int(pile_n)
+    if not 0 <= pile_at < 1 << 64 or not 0 <= pile_n <= L.PILE_MAX_N:
+        raise ValueError("pile_at must fit 64 bits and pile_n lie in [0, 2^61 / 8]")
+    if out is None:
+        counts = np.zeros((pile_n, L.PILE_WORDS), dtype=np.uint32)
+    else:
+        counts = out
+        if not isinstance(counts, np.ndarray) or counts.dtype != np.uint32 or counts.shape != (pile_n, L.PILE_WORDS) or \
+                not counts.flags.c_contiguous or not counts.flags.writeable:
+            raise ValueError(f"out must be a writeable C-contiguous uint32 array [{pile_n}, {L.PILE_WORDS}]")
+    res = L.Results()
+    res.n, res.n_ops = n, int(ops.size)
+    res.status = status.ctypes.data_as(C.POINTER(C.c_int32))
+    res.ops_off = ops_off.ctypes.data_as(C.POINTER(C.c_uint64))
+    res.ops_len = ops_len.ctypes.data_as(C.POINTER(C.c_uint32))
+    res.ops = ops.ctypes.data_as(C.POINTER(C.c_uint64))
+    res.qbegin, res.qend, res.tbegin, res.tend = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in windows)
+    cnt = C.c_uint64(0)
+    tail = (pile_at, pile_n, counts.ctypes.data_as(C.c_void_p) if pile_n else None, C.byref(cnt))
+    L.check(call(res, q_off, q_len, t_off, t_len, q_rc, tail), what)
+    return counts
 
 
 def check_alignments(batch_result: "BatchResult", blob, q_off, q_len, t_off, t_len, penalties=None, options=None, adaptive=None,

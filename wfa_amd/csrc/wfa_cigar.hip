@@ -31,6 +31,11 @@
 // wfa_check.hpp's): ONE pass, wfa_check_kernel / wfa_check_pk_kernel, the write kernels' rounds and their column sweep (alt_sweep)
 // with a sink that compares an M or X column's two bases where the write kernels store them; eight words and a status a pair,
 // one counter to the host (KERNELS.md 4u).
+//
+// The pileup (wfahip_pileup_device, wfahip_pileup_packed_device and their host entries; the rule is wfa_pile.hpp's): the first product
+// per TARGET BASE.  Two passes: the rows' length pass without its store and its scan, then wfa_pile_kernel / wfa_pile_pk_kernel -- the
+// write kernels' rounds and table, the target-consuming columns swept by target base, one add without a return per column into
+// the caller's eight counters a base (KERNELS.md 4w).
 #include "wfa_ctx.hpp"
 #include "wfa_hostpack.hpp"
 #include "wfa_cigar.hpp"
@@ -38,6 +43,7 @@
 #include "wfa_altext_pk.hpp"
 #include "wfa_check.hpp"
 #include "wfa_diff.hpp"
+#include "wfa_pile.hpp"
 
 using namespace wfa;
 
@@ -110,6 +116,10 @@ static_assert(CHK_WORDS == WFAHIP_CHK_WORDS && CHK_ALL == WFAHIP_CHK_ALL && CHK_
                   CHK_COST_UNDER == WFAHIP_CHK_COST_UNDER && CHK_STAT_GAP_REGIONS == WFAHIP_CHK_STAT_GAP_REGIONS,
               "wfa_check.hpp's flags are the public header's");
 constexpr uint32_t CHK_MAX_GRID = 2048;  // workgroups of four waves, each wave striding over the pairs
+static_assert(PILE_WORDS == WFAHIP_PILE_WORDS && PILE_W_A == WFAHIP_PILE_W_A && PILE_W_C == WFAHIP_PILE_W_C && PILE_W_T == WFAHIP_PILE_W_T &&
+                  PILE_W_G == WFAHIP_PILE_W_G && PILE_W_OTHER == WFAHIP_PILE_W_OTHER && PILE_W_GAP == WFAHIP_PILE_W_GAP &&
+                  PILE_W_EXTRA == WFAHIP_PILE_W_EXTRA && PILE_W_EXTRA_BASES == WFAHIP_PILE_W_EXTRA_BASES,
+              "wfa_pile.hpp's words are the public header's");
 
 }  // namespace
 
@@ -266,11 +276,10 @@ __device__ __forceinline__ uint32_t alt_load4(const uint8_t *p) {  // four bytes
 // entry (COLUMNS_ONLY) only those of a pair with a column, so that the offsets of a pair that renders nothing are never looked at.
 // DIFF: the pass of the difference string (wfa_diff.hpp) -- the same checks, and a fourth sum, the bytes of the text, is what
 // text_off[i] receives in place of the columns (a pair has a byte exactly when it has a column).
-template <bool COLUMNS_ONLY, bool DIFF = false, class Window>
-__device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window) {
-    const uint64_t i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    if (i >= C.n) return;
+// PILE: the pass of the pileup (wfa_pile.hpp) -- the same checks again; no offset is stored (nothing is scanned), and lane 0 returns
+// whether the pair has a column, which is all the entry counts.
+template <bool COLUMNS_ONLY, bool DIFF = false, bool PILE = false, class Window>
+__device__ __forceinline__ bool alt_len_pair(const CigParams &C, uint64_t i, uint32_t lane, Window &&window) {
     const uint64_t *ops;
     uint32_t        first, end;
     cig_wave_range(C, i, lane, &ops, &first, &end);
@@ -299,9 +308,18 @@ __device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window
             }
         }
         if (cols == 0ull) count = 0u;  // (ops without a column: pass 3 has nothing to do)
-        C.text_off[i] = DIFF ? (cols != 0ull ? bytes : 0ull) : cols;
-        C.range[i]    = make_uint2(first, count);
+        if constexpr (!PILE) C.text_off[i] = DIFF ? (cols != 0ull ? bytes : 0ull) : cols;
+        C.range[i] = make_uint2(first, count);
     }
+    return cols != 0ull;
+}
+
+template <bool COLUMNS_ONLY, bool DIFF = false, class Window>
+__device__ __forceinline__ void alt_len_pass(const CigParams &C, Window &&window) {
+    const uint64_t i    = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (i >= C.n) return;
+    (void)alt_len_pair<COLUMNS_ONLY, DIFF>(C, i, lane, window);
 }
 
 __global__ __launch_bounds__(256) void wfa_altext_len_kernel(const AltParams A) {
@@ -552,6 +570,118 @@ __global__ __launch_bounds__(256) void wfa_diff_pk_write_kernel(const AltPkParam
         (void)alt_pk_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
         return AltPkSeq{A.words + A.q_woff[i], A.words + A.t_woff[i], A.q_len[i], A.t_len[i], (uint32_t)w.q_at, (uint32_t)w.t_at,
                         A.q_rc != nullptr && A.q_rc[i] != 0};
+    });
+}
+
+// ---- the pileup (wfa_pile.hpp)
+
+// pileup, pass 1: the rows' length pass (alt_len_pair) with the waves striding over the pairs, so that ONE atomic a wave feeds the
+// count of the pairs that pass 2 sweeps
+template <bool COLUMNS_ONLY, class Window>
+__device__ __forceinline__ void pile_len_pass(const CigParams &C, Window &&window) {
+    const uint32_t lane  = threadIdx.x & 63;
+    uint32_t       piled = 0u;  // (lane 0's)
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < C.n; i += (uint64_t)gridDim.x * 4)
+        piled += alt_len_pair<COLUMNS_ONLY, false, true>(C, i, lane, window) ? 1u : 0u;
+    if (lane == 0 && piled != 0u) atomicAdd(&C.ctl[CIG_TOTAL], (unsigned long long)piled);
+}
+
+__global__ __launch_bounds__(256) void wfa_pile_len_kernel(const AltParams A) {
+    pile_len_pass<false>(A.C, [&](uint64_t i, AltWindow *w) { return alt_pair_window(A, i, w); });
+}
+
+__global__ __launch_bounds__(256) void wfa_pile_pk_len_kernel(const AltPkParams A) {
+    pile_len_pass<true>(A.C, [&](uint64_t i, AltWindow *w) { return alt_pk_pair_window(A, i, w); });
+}
+
+// one counter up by v: relaxed, device scope, the result unused -- an add without a return, nothing to wait for
+__device__ __forceinline__ void pile_add(uint32_t *counts, uint64_t idx, uint32_t word, uint32_t v) {
+    (void)__hip_atomic_fetch_add(counts + idx * PILE_WORDS + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// pileup, pass 2.  A wave per pair in rounds of 64 ops, a lane an op: wave prefix sums give every op its first query and target base
+// of the windows, and the table goes to the wave's LDS as in alt_write_pass.  A 'D' op's two adds are its own lane's.  The columns
+// that consume a target base ('M', 'X', 'I') are swept by TARGET BASE, not by op: each of them maps to exactly one base, the round's
+// bases are one run [tc, tc + R), and only the part of it inside the pileup's window is walked (pile_clip) -- consecutive lanes take
+// consecutive bases, so that one wave add falls into 64 x 32 B = 2 KB of the counters, and a lane finds the op of its base by a
+// search over the table's 64 target starts (the last op that starts at or before the base is the one that consumes it: an op
+// without a target base starts where the next one does).  No lane walks a count, and a window that misses the pair costs it one
+// round of prefix sums per 64 ops and no memory access but its ops.  seq(i, &T0, &t_n) gives pair i's query reader, the coordinate
+// of its target window's first base and that window's length, once pass 1 has found the pair valid.
+template <class Params, class MakeSeq>
+__device__ __forceinline__ void pile_pass(const Params &A, const PileWin W, uint32_t *counts, MakeSeq &&seq) {
+    __shared__ uint32_t s_q[4][64], s_t[4][64], s_gap[4][64];  // first query / target base in the windows; != 0: the op is an 'I'
+    const CigParams &C    = A.C;
+    const uint32_t   wv   = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t   i    = (uint64_t)blockIdx.x * 4 + wv;
+    if (i >= C.n) return;
+    const uint2 rg = C.range[i];
+    if (rg.y == 0u) return;
+    uint64_t        T0;
+    uint32_t        t_n;
+    const auto      S   = seq(i, &T0, &t_n);
+    const uint32_t *r   = C.rec + i * REC_WORDS;
+    const uint64_t *ops = C.ops + ((uint64_t)r[REC_OPS_OFF_LO] | ((uint64_t)r[REC_OPS_OFF_HI] << 32)) + rg.x;
+    uint32_t        qc = 0u, tc = 0u;  // bases the rounds before consumed (pass 1: at most the windows' lengths)
+    for (uint32_t b = 0; b < rg.y; b += 64u) {
+        const uint64_t op   = b + lane < rg.y ? ops[b + lane] : 0ull;  // (letter 0: no column)
+        const uint32_t kind = alt_kind(op), cnt = alt_cols(op);
+        const uint32_t myq = (kind & ALT_Q) ? cnt : 0u, myt = (kind & ALT_T) ? cnt : 0u;
+        uint32_t       qi = myq, ti = myt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t q2 = __shfl_up(qi, o, 64), t2 = __shfl_up(ti, o, 64);
+            if (lane >= (uint32_t)o) qi += q2, ti += t2;
+        }
+        const uint32_t qs = qc + qi - myq, ts = tc + ti - myt;  // the op's first bases
+        if ((uint32_t)(op >> 32) == (uint32_t)'D' && cnt != 0u && t_n != 0u) {
+            uint64_t idx;
+            if (pile_in(pile_extra_base(T0, ts), W, &idx)) {
+                pile_add(counts, idx, PILE_W_EXTRA, 1u);
+                pile_add(counts, idx, PILE_W_EXTRA_BASES, cnt);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the round before has read its table)
+        __builtin_amdgcn_wave_barrier();
+        s_q[wv][lane]   = qs;
+        s_t[wv][lane]   = ts;
+        s_gap[wv][lane] = kind == ALT_T ? 1u : 0u;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t R = __shfl(ti, 63, 64);  // the round's target bases: [tc, tc + R) of the window
+        uint64_t       lo, hi;
+        if (pile_clip(T0 + tc, R, W, &lo, &hi)) {
+            const uint64_t idx0 = T0 + tc - W.at;  // (mod 2^64; idx0 + x is the place of the round's base x wherever lo <= x < hi)
+            for (uint64_t x = lo + lane; x < hi; x += 64u) {
+                const uint32_t tb = tc + (uint32_t)x;
+                uint32_t       k  = 0u;  // the last op whose first target base is <= tb: the one that consumes it
+#pragma unroll
+                for (uint32_t step = 32u; step != 0u; step >>= 1)
+                    if (s_t[wv][k + step] <= tb) k += step;
+                const uint32_t word = s_gap[wv][k] != 0u ? (uint32_t)PILE_W_GAP : S.word((uint64_t)s_q[wv][k] + (tb - s_t[wv][k]));
+                pile_add(counts, idx0 + x, word, 1u);
+            }
+        }
+        qc += __shfl(qi, 63, 64), tc += R;
+    }
+}
+
+__global__ __launch_bounds__(256) void wfa_pile_kernel(const AltParams A, const PileWin W, uint32_t *counts) {
+    pile_pass(A, W, counts, [&](uint64_t i, uint64_t *T0, uint32_t *t_n) {
+        AltWindow w;
+        (void)alt_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+        *T0 = w.t_at, *t_n = w.t_n;
+        return PileByteSeq{A.blob + w.q_at};
+    });
+}
+
+// the codes come straight from the words: no letter is made
+__global__ __launch_bounds__(256) void wfa_pile_pk_kernel(const AltPkParams A, const PileWin W, uint32_t *counts) {
+    pile_pass(A, W, counts, [&](uint64_t i, uint64_t *T0, uint32_t *t_n) {
+        AltWindow w;
+        (void)alt_pk_pair_window(A, i, &w);  // (pass 1 found it valid, and the ops inside it)
+        *T0 = 16ull * A.t_woff[i] + w.t_at, *t_n = w.t_n;
+        return PilePkSeq{A.words + A.q_woff[i], A.q_len[i], (uint32_t)w.q_at, A.q_rc != nullptr && A.q_rc[i] != 0};
     });
 }
 
@@ -990,6 +1120,76 @@ int diff_pk_device_entry(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, 
                       });
 }
 
+// the pileup's two passes on stream st: len(grid) launches the length kernel with the waves striding over the pairs, pile(grid) the
+// kernel of a wave per pair that adds.  WFAHIP_ERR_BAD_ARG when the length kernel raised CIG_BAD_RANGE: no counter is touched.
+template <class Len, class Pile>
+int pile_passes(wfahip_ctx *ctx, const CigParams &C, uint64_t *n_piled, hipStream_t st, const char *what, Len &&len, Pile &&pile) {
+    Stamps stamps;
+    HIP_TRY(hipMemsetAsync(C.ctl, 0, CIG_CTL_WORDS * 8, st));
+    stamps.mark(0, st);
+    len((uint32_t)std::min<uint64_t>((C.n + 3) / 4, CHK_MAX_GRID));
+    HIP_TRY(hipGetLastError());
+    stamps.mark(1, st);
+    // (through the context's pinned block, as the text entries fetch their counters)
+    HIP_TRY(hipMemcpyAsync(ctx->hpin + HPIN_CTRL, C.ctl, CIG_CTL_WORDS * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t hc[CIG_CTL_WORDS];
+    std::memcpy(hc, ctx->hpin + HPIN_CTRL, sizeof hc);
+    if (hc[CIG_BAD_RANGE] != 0) return WFAHIP_ERR_BAD_ARG;
+    if (n_piled) *n_piled = hc[CIG_TOTAL];
+    if (hc[CIG_TOTAL] == 0) return WFAHIP_OK;
+    stamps.mark(3, st);
+    pile((uint32_t)((C.n + 3) / 4));
+    HIP_TRY(hipGetLastError());
+    stamps.mark(4, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    if (stamps.on)
+        std::fprintf(stderr, "[wfahip] %s: %llu pairs, %llu piled: len %.4f ms, pile %.4f ms\n", what, (unsigned long long)C.n,
+                     (unsigned long long)hc[CIG_TOTAL], stamps.ms(0, 1), stamps.ms(3, 4));
+    return WFAHIP_OK;
+}
+
+// the two device entries of the pileup: d_seq is the blob or the words, seq_size blob_bytes or n_words, the offsets byte or word
+// offsets, d_q_rc only the words'
+int pile_device_entry(wfahip_ctx *ctx, bool packed, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq,
+                      uint64_t seq_size, const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len, const void *d_q_rc,
+                      uint64_t n, int only_aligned, uint64_t pile_at, uint64_t pile_n, void *d_counts, uint64_t *n_piled, hipStream_t st) {
+    // (nothing in these checks dereferences the context)
+    if (!ctx || (n && (!d_rec || !d_q_off || !d_q_len || !d_t_off || !d_t_len)) || (!d_ops && ops_cap) || (!d_seq && seq_size) ||
+        (!d_counts && pile_n))
+        return WFAHIP_ERR_BAD_ARG;
+    if (pile_n > PILE_MAX_N || n > 0xFFFFFFF0ull) return WFAHIP_ERR_BAD_ARG;  // (align_device's limit: no entry leaves records of more pairs)
+    if (n_piled) *n_piled = 0;
+    if (n == 0 || pile_n == 0) return WFAHIP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!st) st = ctx->stream;
+    const PileWin   W      = {pile_at, pile_n};
+    uint32_t *const counts = static_cast<uint32_t *>(d_counts);
+    if (packed) {
+        AltPkParams A{};
+        const int   rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, nullptr, &A.C);
+        if (rc) return rc;
+        A.words = static_cast<const uint32_t *>(d_seq), A.n_words = seq_size;
+        A.q_woff = static_cast<const uint64_t *>(d_q_off), A.t_woff = static_cast<const uint64_t *>(d_t_off);
+        A.q_len = static_cast<const uint32_t *>(d_q_len), A.t_len = static_cast<const uint32_t *>(d_t_len);
+        A.q_rc = static_cast<const uint8_t *>(d_q_rc);
+        return pile_passes(
+            ctx, A.C, n_piled, st, "pileup packed",
+            [&](uint32_t grid) { hipLaunchKernelGGL(wfa_pile_pk_len_kernel, dim3(grid), dim3(256), 0, st, A); },
+            [&](uint32_t grid) { hipLaunchKernelGGL(wfa_pile_pk_kernel, dim3(grid), dim3(256), 0, st, A, W, counts); });
+    }
+    AltParams A{};
+    const int rc = cig_params(ctx, d_rec, d_ops, ops_cap, n, only_aligned, nullptr, &A.C);
+    if (rc) return rc;
+    A.blob = static_cast<const uint8_t *>(d_seq), A.blob_bytes = seq_size;
+    A.q_off = static_cast<const uint64_t *>(d_q_off), A.t_off = static_cast<const uint64_t *>(d_t_off);
+    A.q_len = static_cast<const uint32_t *>(d_q_len), A.t_len = static_cast<const uint32_t *>(d_t_len);
+    return pile_passes(
+        ctx, A.C, n_piled, st, "pileup",
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_pile_len_kernel, dim3(grid), dim3(256), 0, st, A); },
+        [&](uint32_t grid) { hipLaunchKernelGGL(wfa_pile_kernel, dim3(grid), dim3(256), 0, st, A, W, counts); });
+}
+
 void cigars_zero(wfahip_cigars *c) { std::memset(c, 0, sizeof *c); }
 
 // the ops of pair i of host results that render: *count of them at *ops (none for a pair that is not OK).  false: an OK pair whose
@@ -1275,6 +1475,98 @@ int diff_text_packed_host(const wfahip_results *r, const uint32_t *packed, uint6
         [&](uint64_t i, const AltWindow &w) {
             return DiffPkSeq{packed + q_woff[i], packed + t_woff[i], q_len[i], t_len[i], (uint32_t)w.q_at, (uint32_t)w.t_at,
                              q_rc != nullptr && q_rc[i] != 0};
+        });
+}
+
+// the host entries of the pileup: every pair through the renderers' checks first (host_pair_checked: a failed one leaves counts
+// untouched), then the adds -- n_threads threads over contiguous ranges of pairs, relaxed atomic adds because pairs share targets.
+// seq_args_ok and window as alignment_text_host_impl takes them; make_seq(i, w, &T0) gives wfa_pile.hpp's reader of pair i's query
+// window and the coordinate of its target window's first base.
+template <class Window, class MakeSeq>
+int pileup_host_impl(const wfahip_results *r, bool seq_args_ok, bool columns_only, int only_aligned, int n_threads, uint64_t pile_at,
+                     uint64_t pile_n, uint32_t *counts, uint64_t *n_piled, Window &&window, MakeSeq &&make_seq) {
+    if (!r) return WFAHIP_ERR_BAD_ARG;
+    const uint64_t n = r->n;
+    if (n && (!r->status || !r->ops_off || !r->ops_len)) return WFAHIP_ERR_BAD_ARG;
+    if (n && only_aligned && (!r->qbegin || !r->qend || !r->tbegin || !r->tend)) return WFAHIP_ERR_BAD_ARG;
+    if ((!r->ops && r->n_ops) || !seq_args_ok || (!counts && pile_n) || pile_n > PILE_MAX_N) return WFAHIP_ERR_BAD_ARG;
+    if (n_piled) *n_piled = 0;
+    if (n == 0 || pile_n == 0) return WFAHIP_OK;
+    const bool trim = only_aligned != 0;
+    const auto pair = [&](uint64_t i, const uint64_t **ops, uint32_t *count, AltWindow *w, uint64_t *cols) {
+        return host_pair_checked(
+            r, i, trim, columns_only, window,
+            [](const uint64_t *o, uint32_t c, uint64_t *size) {
+                const AltSums s = alt_sums(o, c);
+                *size           = s.cols;
+                return s;
+            },
+            ops, count, w, cols);
+    };
+    const unsigned        T = (unsigned)std::max(1, n_threads);
+    std::atomic<int>      bad{0};
+    std::atomic<uint64_t> piled{0};
+    parallel_ranges(0, n, T, [&](uint64_t a, uint64_t b) {
+        uint64_t mine = 0;
+        for (uint64_t i = a; i < b; i++) {
+            uint32_t        count;
+            const uint64_t *ops;
+            AltWindow       w;
+            uint64_t        cols = 0;
+            if (!pair(i, &ops, &count, &w, &cols)) bad = 1;
+            else if (cols != 0) mine++;
+        }
+        piled += mine;
+    });
+    if (bad) return WFAHIP_ERR_BAD_ARG;
+    const PileWin W = {pile_at, pile_n};
+    parallel_ranges(0, n, T, [&](uint64_t a, uint64_t b) {
+        for (uint64_t i = a; i < b; i++) {
+            uint32_t        count;
+            const uint64_t *ops;
+            AltWindow       w;
+            uint64_t        cols = 0;
+            (void)pair(i, &ops, &count, &w, &cols);
+            if (cols == 0) continue;
+            uint64_t   T0;
+            const auto S = make_seq(i, w, &T0);
+            pile_pair(ops, count, S, T0, w.t_n, W,
+                      [&](uint64_t idx, uint32_t word, uint32_t v) { (void)__atomic_fetch_add(counts + idx * PILE_WORDS + word, v, __ATOMIC_RELAXED); });
+        }
+    });
+    if (n_piled) *n_piled = piled;
+    return WFAHIP_OK;
+}
+
+int pileup_host(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off, const uint32_t *q_len,
+                const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads, uint64_t pile_at, uint64_t pile_n,
+                uint32_t *counts, uint64_t *n_piled) {
+    const bool seq_ok = r && !(r->n && (!q_off || !q_len || !t_off || !t_len)) && !(!seq_blob && blob_bytes);
+    return pileup_host_impl(
+        r, seq_ok, false, only_aligned, n_threads, pile_at, pile_n, counts, n_piled,
+        [&](uint64_t i, bool trim, AltWindow *w) {
+            return alt_window(trim, blob_bytes, q_off[i], q_len[i], t_off[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                              trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w);
+        },
+        [&](uint64_t, const AltWindow &w, uint64_t *T0) {
+            *T0 = w.t_at;
+            return PileByteSeq{seq_blob + w.q_at};
+        });
+}
+
+int pileup_packed_host(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff, const uint32_t *q_len,
+                       const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc, int only_aligned, int n_threads, uint64_t pile_at,
+                       uint64_t pile_n, uint32_t *counts, uint64_t *n_piled) {
+    const bool seq_ok = r && !(r->n && (!q_woff || !q_len || !t_woff || !t_len)) && !(!packed && n_words);
+    return pileup_host_impl(
+        r, seq_ok, true, only_aligned, n_threads, pile_at, pile_n, counts, n_piled,
+        [&](uint64_t i, bool trim, AltWindow *w) {
+            return alt_pk_window(trim, n_words, q_woff[i], q_len[i], t_woff[i], t_len[i], trim ? r->qbegin[i] : 0, trim ? r->qend[i] : 0,
+                                 trim ? r->tbegin[i] : 0, trim ? r->tend[i] : 0, w);
+        },
+        [&](uint64_t i, const AltWindow &w, uint64_t *T0) {
+            *T0 = 16ull * t_woff[i] + w.t_at;
+            return PilePkSeq{packed + q_woff[i], q_len[i], (uint32_t)w.q_at, q_rc != nullptr && q_rc[i] != 0};
         });
 }
 
@@ -1575,6 +1867,35 @@ extern "C" int wfahip_diff_text_packed(const wfahip_results *r, const uint32_t *
                                        const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc,
                                        int only_aligned, int n_threads, wfahip_cigars *out) {
     WFAHIP_GUARD(diff_text_packed_host(r, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, only_aligned, n_threads, out))
+}
+
+extern "C" int wfahip_pileup_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_seq_blob,
+                                    uint64_t blob_bytes, const void *d_q_off, const void *d_q_len, const void *d_t_off, const void *d_t_len,
+                                    uint64_t n_pairs, int only_aligned, uint64_t pile_at, uint64_t pile_n, void *d_counts, uint64_t *n_piled,
+                                    void *stream) {
+    WFAHIP_GUARD(pile_device_entry(ctx, false, d_rec, d_ops, ops_cap, d_seq_blob, blob_bytes, d_q_off, d_q_len, d_t_off, d_t_len, nullptr,
+                                   n_pairs, only_aligned, pile_at, pile_n, d_counts, n_piled, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_pileup_packed_device(wfahip_ctx *ctx, const void *d_rec, const void *d_ops, uint64_t ops_cap, const void *d_packed,
+                                           uint64_t n_words, const void *d_q_woff, const void *d_q_len, const void *d_t_woff,
+                                           const void *d_t_len, const void *d_q_rc, uint64_t n_pairs, int only_aligned, uint64_t pile_at,
+                                           uint64_t pile_n, void *d_counts, uint64_t *n_piled, void *stream) {
+    WFAHIP_GUARD(pile_device_entry(ctx, true, d_rec, d_ops, ops_cap, d_packed, n_words, d_q_woff, d_q_len, d_t_woff, d_t_len, d_q_rc, n_pairs,
+                                   only_aligned, pile_at, pile_n, d_counts, n_piled, static_cast<hipStream_t>(stream)))
+}
+
+extern "C" int wfahip_pileup(const wfahip_results *r, const uint8_t *seq_blob, uint64_t blob_bytes, const uint64_t *q_off,
+                             const uint32_t *q_len, const uint64_t *t_off, const uint32_t *t_len, int only_aligned, int n_threads,
+                             uint64_t pile_at, uint64_t pile_n, uint32_t *counts, uint64_t *n_piled) {
+    WFAHIP_GUARD(pileup_host(r, seq_blob, blob_bytes, q_off, q_len, t_off, t_len, only_aligned, n_threads, pile_at, pile_n, counts, n_piled))
+}
+
+extern "C" int wfahip_pileup_packed(const wfahip_results *r, const uint32_t *packed, uint64_t n_words, const uint64_t *q_woff,
+                                    const uint32_t *q_len, const uint64_t *t_woff, const uint32_t *t_len, const uint8_t *q_rc,
+                                    int only_aligned, int n_threads, uint64_t pile_at, uint64_t pile_n, uint32_t *counts, uint64_t *n_piled) {
+    WFAHIP_GUARD(pileup_packed_host(r, packed, n_words, q_woff, q_len, t_woff, t_len, q_rc, only_aligned, n_threads, pile_at, pile_n, counts,
+                                    n_piled))
 }
 
 extern "C" void wfahip_align_texts_free(wfahip_align_texts *t) {
